@@ -1,7 +1,18 @@
 #!/usr/bin/env python3
 """bench.py -- aggregate env-steps/s of the batched Memory Gym hot path on N MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--env ID] [--envs-per-gpu M] [--gather [rccl|peer]]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--env ID] [--envs-per-gpu M] [--gather [rccl|peer]] [--full]
+                    [--dump-outputs DIR]
+
+A plain run measures the headline alone: setup, W warm-up steps, K timed steps, the one JSON line (`value`, `ms_per_step`, ...).
+Everything else this file can measure or check -- the spread windows, `value_2000`, the roofline (HIP events, store probes,
+rocprofv3 traffic passes), the CPU baseline, C1, the secondary / other workloads, config 5 of an N > 1 run, the gather check --
+runs only with --full, and the paragraphs below describe such a run.
+
+--dump-outputs DIR: after the timed steps, what the LAST timed step returned to its caller (observations, reward, terminated,
+truncated and the info dictionary's arrays) as DIR/<name>.npy in float32 (float64 for float64 / wide integer outputs); frame-sized
+rows are a fixed seeded sample of DUMP_ROWS instances (their indices in DIR/sample_rows.npy), at most 64 MB in all.  Seeds, actions
+and step counts do not depend on timing, so two runs with the same arguments compute the same outputs.
 
 A "step" is one mg_step() over every instance of the workload: logic kernel + raster kernel (one launch that holds both for
 the mortar family), with
@@ -57,6 +68,56 @@ DEFAULT_ENVS = {"MortarMayhem-Grid-v0": 65536, "MortarMayhem-v0": 65536, "Mortar
                 "MysteryPath-v0": 32768, "MysteryPath-Grid-v0": 32768, "Endless-MysteryPath-v0": 32768, "SearingSpotlights-v0": 16384,
                 "Endless-SearingSpotlights-v0": 16384}
 OBS_ELEM = {"u8_xyc": 1, "f32_chw": 4, "f16_chw": 2, "bf16_chw": 2}
+DUMP_ROWS = 256          # instances whose frames --dump-outputs writes (a fixed seeded sample); per-instance scalars are written whole
+DUMP_LIMIT = 64 << 20    # bytes --dump-outputs may write in all
+
+
+# ---------------------------------------------------------------------------------------------------------------- --dump-outputs
+def step_arrays(ret, prefix=""):
+    """(name, tensor or ndarray) pairs of what one step call returned: (obs, reward, terminated, truncated, info), dicts by key"""
+    if isinstance(ret, tuple):
+        names = ("obs", "reward", "terminated", "truncated", "info")
+        return [kv for name, v in zip(names, ret) for kv in step_arrays(v, prefix + name)]
+    if isinstance(ret, dict):
+        return [kv for k in sorted(ret) for kv in step_arrays(ret[k], prefix + "_" + k)]
+    if hasattr(ret, "shape") and str(getattr(ret, "dtype", "object")) != "object":
+        return [(prefix, ret)]
+    return []
+
+
+def host_outputs(ret, n):
+    """What a step call returned, on the host as float32 / float64 arrays: frame-sized per-instance arrays reduced to the DUMP_ROWS
+    sampled instances (the same rows whatever the build), everything else whole.  Called right behind the timed region."""
+    import numpy as np
+    import torch
+
+    rows = np.sort(np.random.default_rng(0).choice(n, size=min(n, DUMP_ROWS), replace=False))
+    out = {"sample_rows": rows.astype(np.float64)}
+    for name, t in step_arrays(ret):
+        if isinstance(t, torch.Tensor):
+            if t.dim() and t.shape[0] == n and t[0].numel() > 64:
+                t = t[torch.as_tensor(rows, device=t.device)]
+            wide = t.dtype == torch.float64 or (not t.is_floating_point() and t.element_size() >= 4)  # (exact in float64)
+            a = t.detach().to(torch.float64 if wide else torch.float32).cpu().numpy()
+        else:
+            a = np.asarray(t)
+            if a.ndim and a.shape[0] == n and a[0].size > 64:
+                a = a[rows]
+            wide = a.dtype == np.float64 or (a.dtype.kind in "iu" and a.dtype.itemsize >= 4)
+            a = a.astype(np.float64 if wide else np.float32)
+        out[name] = a
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT:
+        raise RuntimeError("--dump-outputs: %d bytes, more than the %d allowed" % (total, DUMP_LIMIT))
+    return out
+
+
+def write_outputs(arrays, d, suffix=""):
+    import numpy as np
+
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + suffix + ".npy"), a)
 
 
 # ---------------------------------------------------------------------------------------------------------------- CPU baseline
@@ -172,8 +233,10 @@ def pygame_baseline(env_id, episodes=30):
 
 # ---------------------------------------------------------------------------------------------------------------- one workload
 def run_workload(env_id, n_local, K, W, settle, world, rank, dev, obs_format="u8_xyc", gather=None, events=True, event_stride=8,
-                 count_done=False, leg="headline", long_window=0, policy=None):
+                 count_done=False, leg="headline", long_window=0, policy=None, full=True, dump=None):
     """Create the environments, settle, warm up, time K steps; returns a dict (identical on every rank).
+    full=False (a plain run's headline): nothing but the K timed steps -- no HIP events, spread windows, store probes, long window or
+    gather check.  dump: a directory -> host_outputs() of the last timed step written there right behind the timed region.
     long_window: after everything else, one more window of that many steps timed the same way (BASELINE.md section 3 asks for
     >= 2,000 timed steps whatever K the caller chose) -> "value_long".
     policy: None = uniform random actions from 64 pre-generated buffers; "follower:EPS" (ids with a ground truth that names the way,
@@ -187,6 +250,8 @@ def run_workload(env_id, n_local, K, W, settle, world, rank, dev, obs_format="u8
     import memory_gym_amd
     from memory_gym_amd.dist import ObsGatherer, PeerObsBuffer, shard_seeds
 
+    events = events and full
+    long_window = long_window if full else 0
     n_total = n_local * world
     peer = None
     note = None
@@ -234,20 +299,20 @@ def run_workload(env_id, n_local, K, W, settle, world, rank, dev, obs_format="u8
         follow = {"gt": env.gt.clone()}  # (reset() above filled env.gt)
 
     def one_step(k):
+        """one step of the workload; returns what the step call returned to its caller"""
         if follow is not None:
             a = torch.where(rnd[k % n_act_bufs], acts[k % n_act_bufs], (follow["gt"].to(torch.float32) @ way).to(torch.int32))
-            _, _, _, _, info = env.step(a)
-            follow["gt"] = info["ground_truth"]
-            return
+            ret = env.step(a)
+            follow["gt"] = ret[4]["ground_truth"]
+            return ret
         if gatherer is not None:
-            gatherer.step(acts[k % n_act_bufs])
-            return
+            return gatherer.step(acts[k % n_act_bufs])
         if venv is not None:
-            venv.step(acts[k % n_act_bufs])
-            return
-        env.step(acts[k % n_act_bufs])
+            return venv.step(acts[k % n_act_bufs])
+        ret = env.step(acts[k % n_act_bufs])
         if peer is not None:  # the frames are already in rank 0's memory; the gather of the packed rewards / dones orders the streams
             peer.fence_with_scalars()
+        return ret
 
     def fence():
         if gatherer is not None:
@@ -261,11 +326,11 @@ def run_workload(env_id, n_local, K, W, settle, world, rank, dev, obs_format="u8
         one_step(k)
     _fault(leg, rank)
     # ... and keep stepping until the rate is flat (C4's first timed window was 5 % below the other five -- 200 steps
-    # do not settle every workload): windows of 50 steps until two in a row are within 1 % of their predecessor, at most 20
+    # do not settle every workload): 20 windows of 50 steps, timed for `settle_windows_ms`.  A fixed count, not "until flat": the
+    # state the timed steps start from (and what --dump-outputs writes) must not depend on how fast this box ran the windows.
     settle_windows = []
     if not (gather and dist_on):
         sa, sb = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        flat = 0
         for w in range(20):
             sa.record()
             for k in range(50):
@@ -273,12 +338,6 @@ def run_workload(env_id, n_local, K, W, settle, world, rank, dev, obs_format="u8
             sb.record()
             torch.cuda.synchronize()
             settle_windows.append(sa.elapsed_time(sb))
-            if w and abs(settle_windows[-1] - settle_windows[-2]) <= 0.01 * settle_windows[-2]:
-                flat += 1
-                if flat >= 2:
-                    break
-            else:
-                flat = 0
         settle += 50 * len(settle_windows)
     for k in range(W):
         one_step(settle + k)
@@ -297,16 +356,18 @@ def run_workload(env_id, n_local, K, W, settle, world, rank, dev, obs_format="u8
     t0 = time.perf_counter()
     ev0.record()  # hipEventRecord on the launch stream (torch's current stream is the one mg_step is given)
     for k in range(K):
-        one_step(settle + W + k)
+        ret = one_step(settle + W + k)
     ev1.record()
     fence()
     dt_wall = time.perf_counter() - t0
     dt_event = ev0.elapsed_time(ev1) * 1e-3
     # everything of a step is enqueued on the launch stream unless a collective runs beside it: then the fences decide
     dt = dt_wall if (gather and dist_on) else dt_event
+    if dump:  # before anything else steps the handle again: the outputs of the last timed step
+        write_outputs(host_outputs(ret, n_local), dump, "_rank%d" % rank if world > 1 else "")
     # spread of the headline: five more windows of K steps each, timed the same way right behind the timed region
     windows = []
-    if not (gather and dist_on):
+    if full and not (gather and dist_on):
         wev = [torch.cuda.Event(enable_timing=True) for _ in range(6)]
         wev[0].record()
         for w in range(5):
@@ -332,7 +393,7 @@ def run_workload(env_id, n_local, K, W, settle, world, rank, dev, obs_format="u8
     # the timed region -- a linear 16-byte fill (the memory system's store ceiling here) and the raster's store shape without
     # any compose work (include/memgym.h: mg_store_probe).  Best and median of 9 launches each after 3 warm-ups.
     box = None
-    if obs_format == "u8_xyc" and peer is None and gatherer is None and hasattr(memory_gym_amd._native.LIB, "mg_store_probe"):  # (a gatherer's buffers are checked below)
+    if full and obs_format == "u8_xyc" and peer is None and gatherer is None and hasattr(memory_gym_amd._native.LIB, "mg_store_probe"):  # (a gatherer's buffers are checked below)
         import ctypes as C
         box = {}
         stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
@@ -404,7 +465,7 @@ def run_workload(env_id, n_local, K, W, settle, world, rank, dev, obs_format="u8
                           if dt_long else None)}
     if policy:
         out["policy"] = policy
-    if gatherer is not None and rank == 0:  # the frames rank 0 received in the last step equal the ranks' own (rank 0's: checked here)
+    if full and gatherer is not None and rank == 0:  # the frames rank 0 received in the last step equal the ranks' own (rank 0's: checked here)
         got, grew, gdone = gatherer.gathered_step()
         k_last = (gatherer.t - 1) & 1
         out["gather_check"] = bool(torch.equal(got[0], gatherer.bufs[k_last]) and torch.equal(grew[0], gatherer.packed[k_last][1])
@@ -851,15 +912,17 @@ def build_headline(args, r, env_id, n_local, K, W, world, ranks):
                    "parallelism": "env-sharded x%d, no data-path collective" % world if not r["gather"] else
                    "env-sharded x%d + %s(obs + reward + done)->rank0" % (world, "peer-mapped stores / packed gather" if r["gather"] == "peer" else "gather")},
         "per_gpu_value": r["value"] / world, "timing": r["timing"], "wall_ms_per_step": r["wall_ms_per_step"],
-        # five consecutive windows of K steps each right behind the timed one (this rank's share x N for N > 1): the spread a
-        # K-step headline carries
-        "value_windows": r["value_windows"],
-        # BASELINE.md section 3's stated timing (>= 2,000 timed steps), whatever --steps was: one such window, timed the same way
-        "value_2000": r.get("value_long"),
         "policy": r.get("policy") or "uniform random",
         # who ran: every rank's device as that rank reports it, the backend, the collective library's version
         "ranks": ranks,
+        "full": bool(args.full),
     }
+    if args.full:
+        # five consecutive windows of K steps each right behind the timed one (this rank's share x N for N > 1): the spread a
+        # K-step headline carries
+        out["value_windows"] = r["value_windows"]
+        # BASELINE.md section 3's stated timing (>= 2,000 timed steps), whatever --steps was: one such window, timed the same way
+        out["value_2000"] = r.get("value_long")
     if r["note"]:
         out["note"] = r["note"]
     if "gather_check" in r:
@@ -940,6 +1003,11 @@ def main():
     ap.add_argument("--event-stride", type=int, default=8, help="bracket every N-th step with HIP events (each bracketed step costs ~15 us)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="torch.distributed backend for N > 1 (nccl == RCCL; gloo only for plumbing tests with all ranks on one GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beyond the headline as well (spread windows, value_2000, roofline, CPU baseline, C1, "
+                         "secondary / other workloads, config 5 of an N > 1 run, the gather check); the --no-* options apply to such a run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (float32 / float64 .npy, <= 64 MB; see the module docstring) to DIR")
     ap.add_argument("--cpu-worker", nargs=3, metavar=("ENV", "THREADS", "SECONDS"), help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.cpu_worker:
@@ -1017,7 +1085,7 @@ def main():
     K, W = args.steps, args.warmup
     guard.arm(max(600.0, 2 * args.leg_limit), "the headline workload")
     r = run_workload(env_id, n_local, K, W, args.settle, world, rank, dev, args.obs_format, args.gather, not args.no_events, args.event_stride,
-                     long_window=args.long_window, policy=args.policy)
+                     long_window=args.long_window, policy=args.policy, full=args.full, dump=args.dump_outputs)
     guard.disarm()
 
     out = None
@@ -1027,7 +1095,7 @@ def main():
         sys.stderr.write("bench.py: headline measured (%d GPU%s): %.4g env steps/s -- held by the line guard, printed once at the end\n" % (world, "s" if world > 1 else "", out["value"]))
         sys.stderr.flush()
 
-    if world > 1 and not args.no_secondary and args.obs_format == "u8_xyc":
+    if args.full and world > 1 and not args.no_secondary and args.obs_format == "u8_xyc":
         # BASELINE.json config 5: Endless-MortarMayhem-v0, 32,768 instances per GPU, with and without the gather to rank 0.  Each leg
         # runs under the guard's deadline; the ranks agree on going in and on how it went through the store (no collective), and the
         # first failure anywhere ends the phase for everybody: a rank that raised cannot leave the others waiting in a collective.
@@ -1068,7 +1136,7 @@ def main():
                 break
         guard.disarm()
 
-    if rank == 0:
+    if rank == 0 and args.full:
         if world == 1 and not args.no_cpu_baseline and not fake:
             try:
                 out["cpu_baseline"] = cpu_baseline(env_id)

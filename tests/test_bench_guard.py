@@ -22,7 +22,7 @@ def _run(fault=None, launcher="self", leg_limit=30.0, timeout=120):
     env.pop("MEMGYM_BENCH_TEST_FAULT", None)
     if fault:
         env["MEMGYM_BENCH_TEST_FAULT"] = fault
-    args = ["--gpus", "2", "--backend", "gloo", "--steps", "10", "--warmup", "2", "--leg-limit", str(leg_limit)]
+    args = ["--gpus", "2", "--backend", "gloo", "--steps", "10", "--warmup", "2", "--leg-limit", str(leg_limit), "--full"]
     if launcher == "self":
         cmd = [sys.executable, BENCH] + args
     else:

@@ -125,7 +125,7 @@ def test_rccl_reads_a_balanced_virtual_memory_buffer():
 
 def test_bench_gather_rccl_one_rank():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gather", "rccl", "--env", "Endless-MortarMayhem-v0", "--envs-per-gpu", "8192",
-                          "--steps", "16", "--warmup", "4", "--settle", "20", "--no-cpu-baseline", "--no-secondary", "--no-traffic", "--no-c1"],
+                          "--steps", "16", "--warmup", "4", "--settle", "20", "--no-cpu-baseline", "--no-secondary", "--no-traffic", "--no-c1", "--full"],
                          env=_env(), capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

@@ -1,13 +1,13 @@
 #!/bin/bash
 # tools/ab_bench.sh OUT.tsv ENV_ID N_ENVS 'label|lib|VAR=val VAR=val' ...   -- same-box A/B of library variants / lab switches:
-# every configuration runs `bench.py --steps 200` for one workload (no secondary legs) and contributes one line
+# every configuration runs `bench.py --full --steps 200` for one workload (no secondary legs) and contributes one line
 # (label, M env-steps/s, raster / logic launch averages in us, the five value windows' min-max).  Run the list twice (A/B/A/B) by repeating it.
 out=$1; env_id=$2; n=$3; shift 3
 cd "$(dirname "$0")/.."
 for cfg in "$@"; do
   IFS='|' read -r label lib vars <<< "$cfg"
   [ -z "$lib" ] && lib=endless-memory-gym_amd/lib/lab/libmemgym_hip_lab.so
-  line=$(env MEMGYM_HIP_LIB=$PWD/$lib $vars python bench.py --env "$env_id" --envs-per-gpu "$n" --steps 200 --no-cpu-baseline --no-secondary --no-traffic --no-c1 --no-other 2>/dev/null | grep '^{' | tail -1)
+  line=$(env MEMGYM_HIP_LIB=$PWD/$lib $vars python bench.py --full --env "$env_id" --envs-per-gpu "$n" --steps 200 --no-cpu-baseline --no-secondary --no-traffic --no-c1 --no-other 2>/dev/null | grep '^{' | tail -1)
   python - "$label" "$line" >> "$out" <<'PY'
 import json, sys
 label, line = sys.argv[1], sys.argv[2]

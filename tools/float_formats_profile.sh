@@ -17,7 +17,7 @@ for spec in "$@"; do
   case "$lib" in *:*) extra=${lib#*:}; lib=${lib%%:*};; esac   # e.g. MEMGYM_OBS_FRAME_BYTES=21168: the piece order of rounds 2-5 (tools/fmt_ab.sh)
   for F in $FORMATS; do
     O=gpurun_out/${TAG}_${label}_${F}
-    env $extra MEMGYM_HIP_LIB=$PWD/$lib rocprofv3 --kernel-trace --stats -d ${O}_kt -o kt -- python bench.py $B --obs-format $F --steps 200 --warmup 30 > ${O}_kt.log 2>&1
+    env $extra MEMGYM_HIP_LIB=$PWD/$lib rocprofv3 --kernel-trace --stats -d ${O}_kt -o kt -- python bench.py $B --full --obs-format $F --steps 200 --warmup 30 > ${O}_kt.log 2>&1
     env $extra MEMGYM_HIP_LIB=$PWD/$lib rocprofv3 --pmc $P1 --kernel-trace -d ${O}_p1 -o p -- python bench.py $B --obs-format $F --steps 20 --warmup 5 --no-events > ${O}_p1.log 2>&1
     env $extra MEMGYM_HIP_LIB=$PWD/$lib rocprofv3 --pmc $P2 --kernel-trace -d ${O}_p2 -o p -- python bench.py $B --obs-format $F --steps 20 --warmup 5 --no-events > ${O}_p2.log 2>&1
     {

@@ -2,7 +2,7 @@
 # tools/fmt_ab.sh OUT.tsv LABEL LIB.so FORMAT [ENV_ID N] -- one line per run of `bench.py --obs-format FORMAT --steps 200` with library LIB
 # (same-box A/B of the stream-out of the float output formats; like tools/ab_bench.sh)
 out=$1; label=$2; lib=$3; fmt=$4; envid=${5:-MortarMayhem-Grid-v0}; n=${6:-65536}
-line=$(env MEMGYM_HIP_LIB=$PWD/$lib python bench.py --env $envid --envs-per-gpu $n --obs-format $fmt --steps 200 --no-cpu-baseline --no-secondary --no-traffic --no-c1 --no-other --long-window 0 2>/dev/null | grep '^{' | tail -1)
+line=$(env MEMGYM_HIP_LIB=$PWD/$lib python bench.py --full --env $envid --envs-per-gpu $n --obs-format $fmt --steps 200 --no-cpu-baseline --no-secondary --no-traffic --no-c1 --no-other --long-window 0 2>/dev/null | grep '^{' | tail -1)
 python - "$label" "$fmt" "$line" >> $out <<'PY'
 import json, sys
 label, fmt, line = sys.argv[1:4]
