@@ -35,9 +35,18 @@ constexpr int TILE = SCREEN / G;   // 12 px
 // Endless: AUX_WORDS words per instance.  The first 128-byte line holds what a step may need besides the state and segment records,
 // so that ONE batch of loads fetches it (emp_step_b): words 0..19 the EMP_PRE record (0..12 the segment record, SEG_STRIDE bytes; 13
 // the stream's buffered half; 14 = has_buffered | end_y << 8; 16..19 the stream's 128-bit state behind the segment's draws, low word
-// first), words 20..31 the first twelve fall-off keys; the list goes on behind them (MAX_FALL keys: x | y << 16, y biased by 1024).
+// first), words 20..31 the first twelve fall-off keys; the list goes on behind them (MAX_FALL keys, emp_fall_key).
 constexpr int AUX_FALL = 20, AUX_WORDS = 160;
 static_assert(AUX_FALL + MAX_FALL <= AUX_WORDS && AUX_WORDS % 32 == 0, "the fall-off list must fit behind the record");
+// A fall-off cell's key: column x in bits 0..17, row y + EMP_KEY_YBIAS in bits 18..31.  Injective over every cell an episode can fall
+// into: x in 0 .. 8 * 32,767 - 1 (the agent never moves left of its start; mg_set_capacity's largest segment store ends the episode
+// before it enters segment 32,767) and y in -EMP_KEY_YBIAS .. 2^14 - 1 - EMP_KEY_YBIAS (the unclamped vertical move leaves rows 0..6 by
+// one tile at most).  Rounds 1-6 kept x in 16 bits: cells 65,536 columns apart shared a key (a second fall there ended the episode).
+constexpr int EMP_KEY_XBITS = 18, EMP_KEY_YBIAS = 1024, EMP_MAX_SEG_CAP = 32767;
+static_assert(8 * EMP_MAX_SEG_CAP <= (1 << EMP_KEY_XBITS) && EMP_KEY_YBIAS + 8 <= (1 << (32 - EMP_KEY_XBITS)), "fall-off keys must be injective");
+__host__ __device__ __forceinline__ uint32_t emp_fall_key(int nx, int ny) {
+    return (uint32_t)nx | ((uint32_t)(ny + EMP_KEY_YBIAS) << EMP_KEY_XBITS);
+}
 constexpr int STAMINA_W = 4;      // int(16 * SCALE)
 
 struct MysteryParams {
@@ -57,14 +66,14 @@ struct MysteryParams {
 };
 
 struct __attribute__((aligned(16))) MysteryCore {
-    int16_t ax, ay;
+    int16_t ax, ay;                     // ax: finite variants (endless: EMP_AX)
     uint8_t rot8, off, cross_on, path_len;  // path_len: finite variants; endless: segments OWED to the instance (EMP_OWED below)
     uint8_t sx, sy, ex, ey;
     int16_t cross_x, cross_y;           // fall_off_rect centre
     int32_t fails, t, ep_len, stamina;
     int32_t max_x, tiles_visited, cur_seg, num_seg;
     int32_t cur_node_seg, cur_node_idx, camera_x, n_falloff;
-    uint64_t path_mask, visited_mask;   // finite: bit (x*7+y)
+    uint64_t path_mask, visited_mask;   // finite: bit (x*7+y); endless: EMP_AX (path_mask), EMP_FLO / EMP_FHI (visited_mask)
     double ep_sum;
     uint8_t td[3], have_start;
     int8_t end_y;
@@ -77,6 +86,10 @@ static_assert(sizeof(MysteryCore) == 96, "MysteryCore must be 96 bytes");
 #define EMP_FLO(s) (reinterpret_cast<int32_t*>(&(s).visited_mask)[0])
 #define EMP_FHI(s) (reinterpret_cast<int32_t*>(&(s).visited_mask)[1])
 #define EMP_OWED(s) ((s).path_len)  // endless: segments the instance is owed ("lazy initial segments" below)
+// endless: the agent's absolute x in pixels, 32 bits (the reference's pygame rects are C ints): the low half of the finite variants'
+// path_mask, the high half unused.  Up to 8 x 32,767 columns of 12 px (mg_set_capacity "path_segments"): 3.1 M px.  Rounds 1-6 kept it
+// in `ax`, 16 bits, which wrapped after 32,767 px (segment ~341).  `ay` and the fields relative to the camera stay 16-bit.
+#define EMP_AX(s) (reinterpret_cast<int32_t*>(&(s).path_mask)[0])
 #define EMP_PRE(s) ((s).ex)         // endless: io.aux[i] holds the next episode's first segment (ex / ey: the finite variants' goal)
 // The whole record as six 16-byte loads issued together.  Field by field the compiler split it into eleven odd-sized loads
 // and issued three of them only after the first uses: a second memory round trip (3-4 us on a cold state array) at the head
@@ -531,6 +544,14 @@ __device__ __forceinline__ void move_agent(const MysteryParams& P, MysteryCore& 
     free_move(a0, a1, P.v_axis_i, P.v_diag_i, ax, ay, s.rot8, clamp, P.agent_radius, SCREEN - P.agent_radius, P.agent_radius,
               SCREEN - P.agent_radius);
     s.ax = (int16_t)ax;
+    s.ay = (int16_t)ay;
+}
+// the same for Endless-MysteryPath (unclamped), whose x is EMP_AX
+__device__ __forceinline__ void emp_move_agent(const MysteryParams& P, MysteryCore& s, int a0, int a1) {
+    int ax = EMP_AX(s), ay = s.ay;
+    free_move(a0, a1, P.v_axis_i, P.v_diag_i, ax, ay, s.rot8, false, P.agent_radius, SCREEN - P.agent_radius, P.agent_radius,
+              SCREEN - P.agent_radius);
+    EMP_AX(s) = ax;
     s.ay = (int16_t)ay;
 }
 
@@ -1023,7 +1044,8 @@ __device__ __forceinline__ void emp_post_reset_state(const MysteryParams& P, con
     s.sy = (uint8_t)node_y(b1);
     s.camera_x = P.camera_offset;
     s.bg = 0;
-    s.ax = (int16_t)(s.sx * P.tile + P.agent_radius);
+    s.ax = 0;  // (finite variants only)
+    EMP_AX(s) = s.sx * P.tile + P.agent_radius;
     s.ay = (int16_t)(s.sy * P.tile + P.agent_radius);
     s.rot8 = 6;  // 270 degrees
     s.cur_node_seg = 0;
@@ -1050,7 +1072,7 @@ __device__ void emp_post_reset(const MysteryParams& P, const MysteryIO& io, int 
     emp_post_reset_state(P, io, i, s, gt, R);
     SegRec none;
     none.seg = -1;
-    emp_fill_desc<false>(P, io, i, s, d, s.ax / P.tile, R, none);
+    emp_fill_desc<false>(P, io, i, s, d, EMP_AX(s) / P.tile, R, none);
     d.cross_on = 0;
     if (P.show_stamina) d.stamina_red = 0;
 }
@@ -1062,9 +1084,9 @@ constexpr int EMP_DUE = 1, EMP_CAP = 2;
 __device__ int emp_step_a(const MysteryParams& P, int i, MysteryCore& s, int a, int& nx, int& ny, int* io_err) {
     int a0 = a == 1 ? 2 : 0, a1 = a == 2 ? 1 : (a == 3 ? 2 : 0);
     if (!s.off) {
-        int before = s.ax;
-        move_agent(P, s, a0, a1, false);
-        const int vx = s.ax - before;
+        const int before = EMP_AX(s);
+        emp_move_agent(P, s, a0, a1);
+        const int vx = EMP_AX(s) - before;
         s.camera_x += vx;  // camera follows the agent's x velocity
         // bg_scroll -= velocity.x; once |bg_scroll| >= tile it becomes (|bg_scroll| % |velocity.x|) * sign, which is 0:
         // it has only ever moved in steps of the same velocity.x (endless_mystery_path.py:311-316)
@@ -1072,12 +1094,12 @@ __device__ int emp_step_a(const MysteryParams& P, int i, MysteryCore& s, int a, 
         s.bg = (uint8_t)(bg >= P.tile ? bg % vx : bg);
     } else {
         s.bg = 0;
-        s.ax = (int16_t)(s.sx * P.tile + P.agent_radius);
+        EMP_AX(s) = s.sx * P.tile + P.agent_radius;
         s.ay = (int16_t)(s.sy * P.tile + P.agent_radius);
-        move_agent(P, s, 0, 0, false);
+        emp_move_agent(P, s, 0, 0);
         s.camera_x = P.camera_offset;
     }
-    nx = floordiv_pos(s.ax, P.tile);
+    nx = floordiv_pos(EMP_AX(s), P.tile);
     ny = floordiv_pos(s.ay, P.tile);
     s.cur_seg = nx / (G + 1);
     // `current_segment > num_segments - 2` counts the owed segments as the reference has them; and whatever this step could
@@ -1215,7 +1237,7 @@ __device__ bool emp_step_b(const MysteryParams& P, const MysteryIO& io, int i, M
             done = true;
         } else {
             uint32_t* fl = aux + AUX_FALL;
-            uint32_t key = (uint32_t)(nx & 0xFFFF) | ((uint32_t)(ny + 1024) << 16);
+            const uint32_t key = emp_fall_key(nx, ny);
             const int nf = s.n_falloff;
             bool found = false;
             int k0 = 0;
@@ -1266,7 +1288,7 @@ __device__ bool emp_step_b(const MysteryParams& P, const MysteryIO& io, int i, M
         s.off = 0;
     }
     LAB_STEP_CLOCK(7);
-    s.cross_x = (int16_t)(s.ax - s.camera_x);
+    s.cross_x = (int16_t)(EMP_AX(s) - s.camera_x);  // (relative to the camera, which moves with the agent: a few tiles at most)
     s.cross_y = s.ay;
     reward += P.r_step;
     s.stamina--;
@@ -1314,7 +1336,7 @@ __device__ bool emp_step_b(const MysteryParams& P, const MysteryIO& io, int i, M
         EMP_OWED(s) = 2;
         if (LAB_BUILD && io.stats) atomicAdd(io.stats + 2, 1ull);  // mg_debug_counter "emp_own_resets" (lab build: tests)
         emp_post_reset_state(P, io, i, s, gt, R);
-        nx = s.ax / P.tile;
+        nx = EMP_AX(s) / P.tile;
         fresh = true;
     };
     if (!FINAL) {  // (rounds 3-5, as it was)
@@ -1633,7 +1655,7 @@ __global__ __launch_bounds__(256) void emp_masked_reset_kernel(MysteryParams P, 
     if (LAB_BUILD && io.stats) atomicAdd(io.stats + 2, 1ull);  // mg_debug_counter "emp_own_resets" (lab build: tests)
     emp_post_reset_state(P, io, i, s, gt ? gt + 3 * i : nullptr, R);
     MysteryDesc d;
-    emp_fill_desc<false>(P, io, i, s, d, s.ax / P.tile, R, none);
+    emp_fill_desc<false>(P, io, i, s, d, EMP_AX(s) / P.tile, R, none);
     d.cross_on = 0;
     if (P.show_stamina) d.stamina_red = 0;
     io.core[i] = s;
@@ -1685,7 +1707,7 @@ __device__ void emp_serve_entry(const MysteryParams& P, const MysteryIO& io, con
             return;
         }
         if (me)
-            reset_me = emp_step_b<false, false, FINAL>(P, io, i, s, floordiv_pos(s.ax, P.tile), floordiv_pos(s.ay, P.tile), reward_out, done_out,
+            reset_me = emp_step_b<false, false, FINAL>(P, io, i, s, floordiv_pos(EMP_AX(s), P.tile), floordiv_pos(s.ay, P.tile), reward_out, done_out,
                                          gti, info, autoreset, d, cap) ? 1 : 0;
         reset_me = bcast(reset_me, 0);
     }
@@ -2391,7 +2413,7 @@ class MysteryFamily : public Family {
     // reference's path grows without limit (pygame_assets.py:559); an episode that needs one more segment than this ends (capacity_dev)
     void set_capacity(const std::string& what, int64_t v) override {
         if (!(P_.endless && what == "path_segments")) return Family::set_capacity(what, v);
-        if (v < 4 || v > 32767) throw OptionError{-3, "path_segments: 4 .. 32,767"};
+        if (v < 4 || v > EMP_MAX_SEG_CAP) throw OptionError{-3, "path_segments: 4 .. 32,767"};
         if (seeded_) throw std::runtime_error("mg_set_capacity: before the first reset");
         MG_HIP(hipDeviceSynchronize());
         seg_rows_ = (int)v;

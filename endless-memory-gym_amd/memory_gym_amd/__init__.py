@@ -21,7 +21,7 @@ def make(env_id, num_envs=None, device=None, render_mode=None, obs_format="u8_xy
     if num_envs is None:
         if env_id not in envs.CLASSES:
             raise ValueError("unknown env id %r" % (env_id,))
-        return envs.CLASSES[env_id](render_mode=render_mode, device=device)
+        return envs.CLASSES[env_id](render_mode=render_mode, device=device, capacity=capacity)
     return VecMemoryGym(env_id, num_envs=num_envs, device=device, render_mode=render_mode, obs_format=obs_format,
                         final_observation=final_observation, obs_buffer=obs_buffer, obs_placement=obs_placement,
                         ground_truth64=ground_truth64, on_capacity=on_capacity, capacity=capacity)

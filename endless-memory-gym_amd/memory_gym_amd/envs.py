@@ -6,8 +6,8 @@ from .vec_env import MemoryGymEnv
 
 
 def _bind(name, env_id, ref):
-    def __init__(self, render_mode=None, device=None):
-        MemoryGymEnv.__init__(self, env_id, device=device, render_mode=render_mode)
+    def __init__(self, render_mode=None, device=None, capacity=None):
+        MemoryGymEnv.__init__(self, env_id, device=device, render_mode=render_mode, capacity=capacity)
 
     cls = type(name, (MemoryGymEnv,), {"env_id": env_id, "__init__": __init__, "__module__": __name__,
                                        "__doc__": "%s (reference: memory_gym/%s)" % (env_id, ref)})

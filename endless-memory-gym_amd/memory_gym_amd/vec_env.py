@@ -611,9 +611,9 @@ class MemoryGymEnv(_EnvBase):
     spec = None
     env_id = None  # set by the per-id subclasses in memory_gym_amd.envs
 
-    def __init__(self, env_id=None, device=None, render_mode=None):
+    def __init__(self, env_id=None, device=None, render_mode=None, capacity=None):
         env_id = env_id or self.env_id
-        self.vec = VecMemoryGym(env_id, 1, device, render_mode)
+        self.vec = VecMemoryGym(env_id, 1, device, render_mode, capacity=capacity)
         self.vec.autoreset = False
         self.action_space = self.vec.action_space
         self.observation_space = self.vec.observation_space

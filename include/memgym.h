@@ -122,7 +122,9 @@ int mg_bind_option_sets(mg_env* env, const int32_t* set_of_dev);
  *   "path_segments"  Endless-MysteryPath-v0: segments of an episode's path (EndlessMysteryPath.add_path_segment, pygame_assets.py:559,
  *                    called from endless_mystery_path.py:333-335 whenever the agent enters the last but one); default 128 = 1,024 tiles,
  *                    4 .. 32,767, 52 bytes per segment and instance.  (Not a ring: an agent that falls off is put back to the START of
- *                    its path, endless_mystery_path.py:316-322, and walks every segment again.)
+ *                    its path, endless_mystery_path.py:316-322, and walks every segment again.)  The agent's x is kept in 32 bits and the
+ *                    fall-off cells by column and row, exactly over the whole range (8 x 32,767 columns of 12 px; state version 8 --
+ *                    versions <= 7 kept x in 16 bits, which wrapped after 32,767 px, about segment 341).
  *   "commands"       Endless-MortarMayhem-v0: entries of the command list (endless_mortar_mayhem.py:311-333); default 512, 4 .. 32,768,
  *                    one byte per entry and instance.
  *   "fall_off_cells" Endless-MysteryPath-v0 (read only): 128 distinct cells an episode may fall off at (:385-393).
@@ -220,7 +222,7 @@ int mg_single_step(mg_env* env, int32_t a0, int32_t a1, void* stream);
  * payload bytes, FNV-1a of the env id}; the layout behind it is private to one MG_STATE_VERSION.  mg_set_state refuses
  * (-1, message in mg_last_error) a blob whose magic, version, env id, num_envs or payload size differ from the handle's
  * instead of mis-assigning it. */
-#define MG_STATE_VERSION 7u
+#define MG_STATE_VERSION 8u
 size_t mg_state_size(const mg_env* env);
 int mg_get_state(mg_env* env, void* host_buf, size_t size);
 int mg_set_state(mg_env* env, const void* host_buf, size_t size);

@@ -42,7 +42,8 @@ typedef struct {
     /* EMP state */
     pnode* epath; /* flat, start-first */
     int epath_len, epath_cap;
-    int seg_start[4096], num_segments;
+    int* seg_start; /* num_segments + 1 entries: the reference's list grows without limit (a fixed 4,096 overflowed) */
+    int seg_start_cap, num_segments;
     int have_start, start_y, end_x, end_y;
     int cur_node, cur_seg, stamina, max_x, tiles_visited;
     double camera_offset, camera_x, bg_scroll;
@@ -377,6 +378,10 @@ static void emp_add_segment(mgo_env* e, mp_t* m) {
         len = 0;
     }
     int k = m->num_segments;
+    if (k + 2 > m->seg_start_cap) {
+        m->seg_start_cap = m->seg_start_cap ? m->seg_start_cap * 2 : 256;
+        m->seg_start = (int*)realloc(m->seg_start, sizeof(int) * m->seg_start_cap);
+    }
     int shift = k == 0 ? 0 : k * G + k;
     m->seg_start[k] = m->epath_len;
     for (int i = len - 1; i >= 0; i--) emp_push(m, (pnode){idx[i] / G + shift, idx[i] % G, 0, 0});
@@ -701,6 +706,7 @@ static void mp_destroy(mgo_env* e) {
     mgo_agent_free(&m->agent);
     mgo_surf_free(m->path_surf); mgo_surf_free(m->cross); mgo_surf_free(m->column_surf); mgo_surf_free(m->stamina_surf);
     free(m->epath);
+    free(m->seg_start);
     free(m);
 }
 
