@@ -7,7 +7,6 @@
 
 #include "mg_family.hpp"
 #include "mg_lab.hpp"
-using mg::lab_env;
 
 namespace mg {
 static thread_local std::string g_last_error;

@@ -11,19 +11,13 @@
 
 #include "../../include/memgym.h"
 #include "mg_lab.hpp"
+#include "mg_launch.hpp"
 #include "mg_device.hpp"
 
 namespace mg {
 
 void set_error(const std::string& msg);
 static_assert(MG_MAX_OPTION_SETS == 8, "set_index() (mg_device.hpp) masks an instance's set index with 7");
-
-#define MG_HIP(expr)                                                                                 \
-    do {                                                                                             \
-        hipError_t e_ = (expr);                                                                      \
-        if (e_ != hipSuccess)                                                                        \
-            throw std::runtime_error(std::string(#expr) + " failed: " + hipGetErrorString(e_));      \
-    } while (0)
 
 // RAII device array
 // One error word in pinned, coherent host memory mapped into the device's address space: kernels raise bits with a
@@ -190,8 +184,11 @@ struct KernelProfile {
     }
 };
 
+// What the C ABI (mg_api.hip) sees of an environment family, and the host-side plumbing the three families share: the error
+// word, the RNG streams, the "seeded" / "geometry changed" guards and the debug view's scratch frames.
 class Family {
    public:
+    explicit Family(int n) : n_(n) {}
     KernelProfile prof;
     void end_logic(hipStream_t s) { prof.end(0, s); }
     int obs_format = MG_OBS_U8_XYC;  // stream-out format of the raster kernel (include/memgym.h)
@@ -231,21 +228,55 @@ class Family {
     // checkpoint: list of (device pointer, bytes) making up the state
     virtual std::vector<std::pair<void*, size_t>> state_blobs() = 0;
     // called by mg_set_state after the blobs were restored: the instances now carry seeded RNG streams
-    virtual void on_state_loaded() {}
+    virtual void on_state_loaded() { seeded_ = true; }
     // called before anything looks at the state from outside (mg_get_state, mg_debug_rng, mg_render_debug): work a family has
     // put off without changing any result (Endless Mystery Path: owed path segments) is done now.  Synchronous.
     virtual void sync_state() {}
-    virtual void debug_rng(int i, uint64_t out[6]) = 0;
+    virtual void debug_rng(int i, uint64_t out[6]) { rng_.debug(i, out); }
     // info["ground_truth"] as the reference returns it -- float64 (e.g. endless_mortar_mayhem.py:259,358) -- of every instance,
     // [num_envs][gt_dim], computed from the CURRENT state (the float32 gt_dev of mg_step / mg_reset is its rounding); a small
     // launch of its own, only when a caller asks (mg_info_buffers.gt64_dev, mg_ground_truth64).  No-op for gt_dim() == 0.
     virtual void ground_truth64(double* /*gt64_dev*/, hipStream_t /*s*/) {}
     // device-side error bits accumulated since the last call (0 = none); synchronises
-    virtual int poll_errors() { return 0; }
+    virtual int poll_errors() {
+        MG_HIP(hipDeviceSynchronize());
+        return err_.take();
+    }
     // the same bits as seen right now, without synchronising or clearing
-    virtual int peek_errors() { return 0; }
+    virtual int peek_errors() { return err_.peek(); }
     // test / telemetry counters by name (mg_debug_counter); false = this family has no such counter.  Synchronous.
     virtual bool debug_counter(const std::string& /*name*/, int64_t* /*out*/) { return false; }
+
+   protected:
+    // head of every reset(): without seeds the instances keep their RNG streams, so they must have some
+    void require_seeded(const int64_t* seeds) const {
+        if (!seeds && !seeded_) throw std::runtime_error("reset(seed=None) before any seeded reset");
+    }
+    // head of every step(): the caller's info buffers, all null where it passed none
+    mg_info_buffers begin_step(const mg_info_buffers* info) const {
+        if (dirty_) throw std::runtime_error("options that change geometry need a reset before the next step");
+        mg_info_buffers ib;
+        memset(&ib, 0, sizeof(ib));
+        if (info) ib = *info;
+        return ib;
+    }
+    // raster_debug(): `fill(dbg)` writes the debug view's descriptors of all instances into scratch, `raster(dbg)` draws them
+    template <typename Desc, typename Fill, typename Raster>
+    void debug_frames(hipStream_t s, Fill fill, Raster raster) {
+        if (dirty_) throw std::runtime_error("options that change geometry need a reset before the next render");
+        DevArray<Desc> dbg;
+        dbg.alloc(n_, false);
+        fill(dbg.p);
+        raster(dbg.p);
+        check_launch();
+        MG_HIP(hipStreamSynchronize(s));  // dbg is released on return
+    }
+
+    const int n_;  // instances of the handle
+    ErrorWord err_;
+    RngStore rng_;
+    bool dirty_ = true;    // a geometry option changed: the next reset rebuilds atlases and constants first
+    bool seeded_ = false;  // some reset carried seeds (or a state was loaded)
 };
 
 Family* make_mortar(int variant, int num_envs);
@@ -255,12 +286,8 @@ Family* make_mystery(int variant, int num_envs);
 // Workgroup size of the one-lane-per-instance logic kernels (all are written for any multiple of 64 up to 256).
 // MEMGYM_STEP_BLOCK overrides `shipped` per process (measurements: profiles/r03_step_blocks.md).
 inline int step_block(int shipped) {
-    static const int forced = [] {
-        const char* e = lab_env("MEMGYM_STEP_BLOCK");
-        const int v = e ? atoi(e) : 0;
-        return (v == 64 || v == 128 || v == 256) ? v : 0;
-    }();
-    return forced ? forced : shipped;
+    static const int v = lab_int("MEMGYM_STEP_BLOCK", 0);
+    return (v == 64 || v == 128 || v == 256) ? v : shipped;
 }
 
 inline int to_int_checked(double v, const char* key) {

@@ -20,6 +20,7 @@
 #include "mg_device.hpp"
 #include "mg_family.hpp"
 #include "mg_lab.hpp"
+#include "mg_option_sets.hpp"
 #include "mg_raster_v1.hpp"
 #include "mg_stamps.hpp"
 
@@ -776,7 +777,7 @@ static const double SCALE = 0.25;  // the reference's module constant (e.g. mort
 class MortarFamily : public Family {
    public:
     // variant 3 / 4 = MortarMayhemB-Grid-v0 / MortarMayhemB-v0: the Grid / free machine with taskb set
-    MortarFamily(int variant_id, int n) : opt_(one_set()), P_(opt_[0]->P), n_(n) {
+    MortarFamily(int variant_id, int n) : Family(n), P_(sets_[0].P) {
         memset(&P_, 0, sizeof(P_));
         const int variant = variant_id >= 3 ? variant_id - 3 : variant_id;
         P_.variant = variant;
@@ -793,7 +794,7 @@ class MortarFamily : public Family {
             const int cap = lab_int("MEMGYM_EMM_CMD_CAP", 0);
             if (cap >= 4 && cap <= 512) P_.cmd_cap = cap;
         }
-        MortarOpt& O = *opt_[0];
+        MortarOpt& O = sets_[0];
         O.st_command_count.set(P_.command_count, {10});
         O.st_show_dur.set(P_.show_dur, {3});
         O.st_show_delay.set(P_.show_delay, {1});
@@ -811,11 +812,11 @@ class MortarFamily : public Family {
         err_.alloc();
         claims_.alloc((size_t)((n + 255) / 256) * 4);
         rescues_.alloc(1);
-        sets_dev_.alloc(MG_MAX_OPTION_SETS);
-        hipLaunchKernelGGL(mortar_init_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, n, state_.p);
+        sets_.alloc();
+        launch(mortar_init_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, n, state_.p);
         MG_HIP(hipDeviceSynchronize());
         rebuild();
-        defaults_ = P_;  // (short lists only: no device arrays behind them)
+        sets_.defaults = P_;
     }
 
     // include/memgym.h: mg_set_capacity.  "commands" (Endless-MortarMayhem-v0): entries of the command list per instance -- the reference's
@@ -828,9 +829,7 @@ class MortarFamily : public Family {
         MG_HIP(hipDeviceSynchronize());
         P_.cmd_cap = (int)v;
         cmds_.alloc((size_t)n_ * P_.cmd_cap);
-        for (size_t k = 1; k < opt_.size(); ++k) copy_geometry(opt_[k]->P, P_);
-        copy_geometry(defaults_, P_);
-        sets_dirty_ = true;
+        sets_.refresh_geometry();
     }
     int64_t capacity(const std::string& what) const override {
         if (P_.variant == V_ENDLESS && what == "commands") return P_.cmd_cap;
@@ -840,7 +839,7 @@ class MortarFamily : public Family {
     // one-launch step of a one-instance handle without ground truth can promise that; everything else answers false and the caller puts a
     // stream memory operation behind the step instead.
     bool arm_done_flag(uint32_t* flag_dev, uint32_t ticket) override {
-        if (!(n_ == 1 && obs_format == MG_OBS_U8_XYC && fuse_step() && !per_set() && gt_dim() == 0 && !dirty_)) return false;
+        if (!(n_ == 1 && obs_format == MG_OBS_U8_XYC && fuse_step() && !sets_.per_set() && gt_dim() == 0 && !dirty_)) return false;
         flag_dev_ = flag_dev;
         flag_ticket_ = ticket;
         flag_armed_ = true;
@@ -859,13 +858,7 @@ class MortarFamily : public Family {
     // that does not change the geometry (atlases and templates are shared by the handle's instances).
     void set_option(const std::string& key, const double* v, int n) override { set_option_set(0, key, v, n); }
     void set_option_set(int set, const std::string& key, const double* v, int n) override {
-        if (set < 0 || set >= MG_MAX_OPTION_SETS) throw OptionError{-3, "option set index out of range"};
-        while ((int)opt_.size() <= set) {  // a new set starts from the constructor's defaults (= the reference's), geometry from set 0
-            opt_.emplace_back(new MortarOpt());
-            opt_.back()->P = defaults_;
-            copy_geometry(opt_.back()->P, P_);
-        }
-        MortarOpt& O = *opt_[set];
+        MortarOpt& O = sets_.ensure(set);
         MortarParams& P = O.P;
         const bool endless = P_.variant == V_ENDLESS;
         auto geometry = [&]() {
@@ -919,69 +912,65 @@ class MortarFamily : public Family {
         else if (!endless && key == "reward_episode_success") P.r_ep_succ = v[0];
         else if (P_.variant != V_GRID && key == "agent_speed") { if (set != 0) { if (v[0] != agent_speed_) geometry(); } else { agent_speed_ = v[0]; dirty_ = true; } }
         else throw OptionError{-2, "unknown reset parameter " + key};
-        sets_dirty_ = true;
     }
-    // instance i runs under option set set_of_dev[i] (device array [num_envs], caller-owned; NULL: every instance under set 0)
-    void bind_option_sets(const int32_t* set_of_dev) override { set_of_ = set_of_dev; }
+    void bind_option_sets(const int32_t* set_of_dev) override { sets_.bind(set_of_dev); }
 
     void reset(const int64_t* seeds, const uint8_t* mask, void* obs, float* gt, hipStream_t s) override {
         if (dirty_) rebuild();
-        if (!seeds && !seeded_) throw std::runtime_error("reset(seed=None) before any seeded reset");
-        for (auto& O : opt_) {  // the display schedule (commands x (duration + delay) entries) is indexed with 16 bits
-            const long long n_max = P_.variant == V_ENDLESS ? O->P.initial_count : O->st_command_count.max(O->P.command_count);
-            if (!P_.taskb && n_max * ((long long)O->st_show_dur.max(O->P.show_dur) + O->st_show_delay.max(O->P.show_delay)) > 65535)
+        require_seeded(seeds);
+        for (size_t k = 0; k < sets_.size(); ++k) {  // the display schedule (commands x (duration + delay) entries) is indexed with 16 bits
+            const MortarOpt& O = sets_[k];
+            const long long n_max = P_.variant == V_ENDLESS ? O.P.initial_count : O.st_command_count.max(O.P.command_count);
+            if (!P_.taskb && n_max * ((long long)O.st_show_dur.max(O.P.show_dur) + O.st_show_delay.max(O.P.show_delay)) > 65535)
                 throw OptionError{-3, "command_count x (command_show_duration + command_show_delay) exceeds the 65,535 entries of this build's display schedule"};
         }
         if (seeds) seeded_ = true;  // with a mask the caller is responsible for having seeded the other instances
-        upload_sets(s);
-        if (per_set())
-            hipLaunchKernelGGL(mortar_reset_kernel<true>, dim3((n_ + 255) / 256), dim3(256), 0, s, P_, n_, io(), seeds, mask, gt_dim() ? gt : nullptr);
-        else
-            hipLaunchKernelGGL(mortar_reset_kernel<false>, dim3((n_ + 255) / 256), dim3(256), 0, s, P_, n_, io(), seeds, mask, gt_dim() ? gt : nullptr);
+        sets_.upload(s);
+        with_bool(sets_.per_set(), [&](auto PS) {
+            launch(mortar_reset_kernel<decltype(PS)::value>, dim3((n_ + 255) / 256), dim3(256), 0, s, P_, n_, io(), seeds, mask, gt_dim() ? gt : nullptr);
+        });
         if (mask && sparse_masked_raster()) {  // few frames of many: by the mask, not by a walk over every descriptor (mg_raster_v1.hpp)
             launch_raster_sparse<MortarComposer>(desc_.p, atlas_->dev(), obs, obs_format, n_, s, mask);
-            MG_HIP(hipGetLastError());
+            check_launch();
         } else raster(obs, s);
     }
 
     void step(const int32_t* actions, void* obs, float* reward, uint8_t* done, float* gt, const mg_info_buffers* info,
               int autoreset, hipStream_t s) override {
-        if (dirty_) throw std::runtime_error("options that change geometry need a reset before the next step");
-        mg_info_buffers ib;
-        memset(&ib, 0, sizeof(ib));
-        if (info) ib = *info;
-        upload_sets(s);
+        const mg_info_buffers ib = begin_step(info);
+        sets_.upload(s);
         const MortarStepArgs sa{P_, n_, io(), actions, reward, done, gt_dim() ? gt : nullptr, ib, autoreset, nullptr};
         // one launch: mortar_step_raster_kernel (handles with ONE option set: the per-set step code reads its parameters from memory)
-        if (obs_format == MG_OBS_U8_XYC && fuse_step() && !per_set() && !capturing(s)) {
+        if (obs_format == MG_OBS_U8_XYC && fuse_step() && !sets_.per_set() && !capturing(s)) {
             epoch_ = epoch_ % 255u + 1u;  // 1 .. 255: never the 0 a reset's (or the two-launch step's) descriptors carry
             ++ticket_;                    // claim words hold the ticket of the last one-launch step: never this one
             const int logic_wgs = (n_ + 255) / 256;
-            const int frames = n_ < raster_grid(n_) ? n_ : raster_grid(n_);
+            const int frames = frames_grid(n_);
             // lab build, MEMGYM_LAB_LOGIC_LAST=1: the step workgroups at the END of the grid -- the dispatch order the design must survive
-            static const bool logic_last = lab_int("MEMGYM_LAB_LOGIC_LAST", 0) != 0;
+            static const bool logic_last = lab_flag("MEMGYM_LAB_LOGIC_LAST", false);
+            // (three of the four <FLAG, FINAL> forms exist: an armed done flag and kept terminal observations exclude each other, keeps_final_obs)
+            auto one_launch = [&](auto kernel, const MortarStepArgs& a, uint32_t* flag, uint32_t flag_ticket) {
+                launch(kernel, dim3(logic_wgs + frames), dim3(256), RASTER_LDS, s, a, logic_wgs, logic_last ? frames : 0, epoch_, ticket_,
+                               claims_.p, rescues_.p, atlas_->dev(), obs, flag, flag_ticket);
+            };
             prof.begin(1, s);
             if (flag_armed_ && n_ == 1) {
-                hipLaunchKernelGGL(mortar_step_raster_kernel<true>, dim3(logic_wgs + frames), dim3(256), RASTER_LDS, s, sa, logic_wgs,
-                                   logic_last ? frames : 0, epoch_, ticket_, claims_.p, rescues_.p, atlas_->dev(), obs, flag_dev_, flag_ticket_);
+                one_launch(mortar_step_raster_kernel<true>, sa, flag_dev_, flag_ticket_);
                 flag_armed_ = false;
             } else if (ib.final_obs_dev && autoreset) {  // terminal observations kept by the launch itself (keeps_final_obs)
                 MortarStepArgs fa = sa;
                 fa.tdesc = tdesc_.p;
-                hipLaunchKernelGGL((mortar_step_raster_kernel<false, true>), dim3(logic_wgs + frames), dim3(256), RASTER_LDS, s, fa, logic_wgs,
-                                   logic_last ? frames : 0, epoch_, ticket_, claims_.p, rescues_.p, atlas_->dev(), obs, (uint32_t*)nullptr, 0u);
+                one_launch(mortar_step_raster_kernel<false, true>, fa, nullptr, 0u);
             } else {
-                hipLaunchKernelGGL(mortar_step_raster_kernel<false>, dim3(logic_wgs + frames), dim3(256), RASTER_LDS, s, sa, logic_wgs,
-                                   logic_last ? frames : 0, epoch_, ticket_, claims_.p, rescues_.p, atlas_->dev(), obs, (uint32_t*)nullptr, 0u);
+                one_launch(mortar_step_raster_kernel<false>, sa, nullptr, 0u);
             }
-            MG_HIP(hipGetLastError());
+            check_launch();
             prof.end(1, s);
             return;
         }
         prof.begin(0, s);
         const int sb = step_block(256);
-        if (per_set()) hipLaunchKernelGGL(mortar_step_kernel<true>, dim3((n_ + sb - 1) / sb), dim3(sb), 0, s, sa);
-        else hipLaunchKernelGGL(mortar_step_kernel<false>, dim3((n_ + sb - 1) / sb), dim3(sb), 0, s, sa);
+        with_bool(sets_.per_set(), [&](auto PS) { launch(mortar_step_kernel<decltype(PS)::value>, dim3((n_ + sb - 1) / sb), dim3(sb), 0, s, sa); });
         end_logic(s);
         prof.begin(1, s);
         raster(obs, s);
@@ -994,17 +983,10 @@ class MortarFamily : public Family {
         return v;
     }
 
-    void debug_rng(int i, uint64_t out[6]) override { rng_.debug(i, out); }
     void ground_truth64(double* out, hipStream_t s) override {
         if (!gt_dim() || !out) return;
-        hipLaunchKernelGGL(mortar_gt64_kernel, dim3((n_ + 255) / 256), dim3(256), 0, s, n_, state_.p, out);
-        MG_HIP(hipGetLastError());
+        launch_checked(mortar_gt64_kernel, dim3((n_ + 255) / 256), dim3(256), 0, s, n_, state_.p, out);
     }
-    int poll_errors() override {
-        MG_HIP(hipDeviceSynchronize());
-        return err_.take();
-    }
-    int peek_errors() override { return err_.peek(); }
     bool debug_counter(const std::string& name, int64_t* out) override {
         if (name == "cmd_list_max" || name == "cmd_list_ge12") {  // the instances' command lists as they stand (a scan of the state records)
             std::vector<MortarState> h(n_);
@@ -1033,7 +1015,7 @@ class MortarFamily : public Family {
     uint32_t epoch_ = 0;  // the one-launch step's descriptor epoch, 1 .. 255 (every step rewrites every descriptor, so the only stale
                           // values a frame workgroup can meet are the previous step's and the 0 of a reset / two-launch step)
     static bool fuse_step() {  // lab build: MEMGYM_MORTAR_FUSE=0 selects the two-launch form for A/B measurements
-        static const bool on = lab_int("MEMGYM_MORTAR_FUSE", 1) != 0;
+        static const bool on = lab_flag("MEMGYM_MORTAR_FUSE", true);
         return on;
     }
     static bool capturing(hipStream_t s) {
@@ -1048,8 +1030,8 @@ class MortarFamily : public Family {
         o.desc = desc_.p;
         o.vec = vec_;
         o.err = err_.dev;
-        o.sets = per_set() ? sets_dev_.p : nullptr;
-        o.set_of = per_set() ? set_of_ : nullptr;
+        o.sets = sets_.dev();
+        o.set_of = sets_.set_of();
         return o;
     }
 
@@ -1084,90 +1066,50 @@ class MortarFamily : public Family {
         atlas_->upload();
         P_.glyph_x0 = (int)((SCREEN / 2) - std::floor(88 * SCALE / 2));
         dirty_ = false;
-        for (size_t k = 1; k < opt_.size(); ++k) copy_geometry(opt_[k]->P, P_);
-        copy_geometry(defaults_, P_);
-        sets_dirty_ = true;
+        sets_.refresh_geometry();
     }
 
-    // per-instance option sets
+    // one option set: the parameter block and the lists behind it
     struct MortarOpt {
         MortarParams P;
         OptListStore st_command_count, st_show_dur, st_show_delay, st_expl_dur, st_expl_delay;
+        // what the shared atlases and templates fix for every set of the handle
+        static void copy_geometry(MortarParams& d, const MortarParams& s) {
+            d.variant = s.variant; d.N = s.N; d.taskb = s.taskb; d.cmd_cap = s.cmd_cap; d.arena_x0 = s.arena_x0; d.tile = s.tile;
+            d.radius = s.radius; d.sprite_dim = s.sprite_dim; d.glyph_x0 = s.glyph_x0; d.v_axis_i = s.v_axis_i; d.v_diag_i = s.v_diag_i;
+            d.off_lo = s.off_lo; d.off_hi = s.off_hi; d.v_axis = s.v_axis; d.v_diag = s.v_diag;
+        }
     };
-    static std::vector<std::unique_ptr<MortarOpt>> one_set() {
-        std::vector<std::unique_ptr<MortarOpt>> v;
-        v.emplace_back(new MortarOpt());
-        return v;
-    }
-    // what the shared atlases and templates fix for every set of the handle
-    static void copy_geometry(MortarParams& d, const MortarParams& s) {
-        d.variant = s.variant; d.N = s.N; d.taskb = s.taskb; d.cmd_cap = s.cmd_cap; d.arena_x0 = s.arena_x0; d.tile = s.tile;
-        d.radius = s.radius; d.sprite_dim = s.sprite_dim; d.glyph_x0 = s.glyph_x0; d.v_axis_i = s.v_axis_i; d.v_diag_i = s.v_diag_i;
-        d.off_lo = s.off_lo; d.off_hi = s.off_hi; d.v_axis = s.v_axis; d.v_diag = s.v_diag;
-    }
-    bool per_set() const { return set_of_ != nullptr && opt_.size() > 1; }
-    // the sets as the kernels read them, stream-ordered behind what the stream holds (pageable source: staged before the call returns)
-    void upload_sets(hipStream_t s) {
-        if (!per_set() || !sets_dirty_) return;
-        MortarParams fresh = defaults_;  // a set that was never written: the reference's defaults under the handle's geometry (include/memgym.h)
-        copy_geometry(fresh, P_);
-        std::vector<MortarParams> host(MG_MAX_OPTION_SETS, fresh);
-        for (size_t k = 0; k < opt_.size(); ++k) host[k] = opt_[k]->P;
-        MG_HIP(hipMemcpyAsync(sets_dev_.p, host.data(), sizeof(MortarParams) * host.size(), hipMemcpyHostToDevice, s));
-        MG_HIP(hipStreamSynchronize(s));  // (rare: only after an option of some set changed)
-        sets_dirty_ = false;
-    }
 
     void raster_only(void* obs, const uint8_t* only, hipStream_t s) override {
         launch_raster<MortarComposer>(desc_.p, atlas_->dev(), obs, obs_format, n_, s, only);
-        MG_HIP(hipGetLastError());
+        check_launch();
     }
     // (the one-launch step keeps terminal observations itself: the conditions under which step() takes that launch; lab
     // MEMGYM_MORTAR_FINAL_FUSED=0: the generic path of mg_step)
     bool keeps_final_obs(hipStream_t s) override {
-        static const bool wanted = lab_int("MEMGYM_MORTAR_FINAL_FUSED", 1) != 0;
-        return wanted && obs_format == MG_OBS_U8_XYC && fuse_step() && !per_set() && !capturing(s) && !(flag_armed_ && n_ == 1);
+        static const bool wanted = lab_flag("MEMGYM_MORTAR_FINAL_FUSED", true);
+        return wanted && obs_format == MG_OBS_U8_XYC && fuse_step() && !sets_.per_set() && !capturing(s) && !(flag_armed_ && n_ == 1);
     }
 
-    void raster(void* obs, hipStream_t s) {
-        launch_raster<MortarComposer>(desc_.p, atlas_->dev(), obs, obs_format, n_, s);
-        MG_HIP(hipGetLastError());
-    }
+    void raster(void* obs, hipStream_t s) { raster_only(obs, nullptr, s); }
 
    public:
     void raster_debug(void* frames, hipStream_t s) override {
-        if (dirty_) throw std::runtime_error("options that change geometry need a reset before the next render");
-        DevArray<MortarDesc> dbg;
-        dbg.alloc(n_, false);
-        hipLaunchKernelGGL(mortar_debug_desc_kernel, dim3((n_ + 255) / 256), dim3(256), 0, s, P_, n_, io(), dbg.p);
-        launch_raster<MortarDebugComposer>(dbg.p, atlas_->dev(), frames, MG_OBS_U8_XYC, n_, s);
-        MG_HIP(hipGetLastError());
-        MG_HIP(hipStreamSynchronize(s));  // dbg is released on return
+        debug_frames<MortarDesc>(
+            s, [&](MortarDesc* dbg) { launch(mortar_debug_desc_kernel, dim3((n_ + 255) / 256), dim3(256), 0, s, P_, n_, io(), dbg); },
+            [&](MortarDesc* dbg) { launch_raster<MortarDebugComposer>(dbg, atlas_->dev(), frames, MG_OBS_U8_XYC, n_, s); });
     }
 
    private:
-
-    std::vector<std::unique_ptr<MortarOpt>> opt_;  // [0] = the handle-wide set (P_ below is its parameter block)
-    MortarParams& P_;
-    MortarParams defaults_;
-    const int32_t* set_of_ = nullptr;
-    bool sets_dirty_ = true;
-    DevArray<MortarParams> sets_dev_;
-    int n_;
+    OptionSets<MortarOpt> sets_;
+    MortarParams& P_;  // set 0, the handle-wide set
     std::unique_ptr<Atlas> atlas_;
     double agent_scale_, agent_speed_;
-    bool dirty_ = true, seeded_ = false;
-
-   public:
-    void on_state_loaded() override { seeded_ = true; }
-
-   private:
     float* vec_ = nullptr;
     DevArray<MortarState> state_;
     DevArray<uint8_t> cmds_;
     DevArray<MortarDesc> desc_, tdesc_;  // tdesc_: terminal-frame descriptors (FINAL form of the one-launch step)
-    RngStore rng_;
-    ErrorWord err_;
     DevArray<uint32_t> claims_, rescues_;  // one-launch step: one claim word per 64 instances; slots stepped by frame waves
 };
 

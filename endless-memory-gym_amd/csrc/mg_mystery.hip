@@ -20,6 +20,7 @@
 #include "mg_lab.hpp"
 #include "mg_device.hpp"
 #include "mg_family.hpp"
+#include "mg_option_sets.hpp"
 #include "mg_raster_v1.hpp"
 #include "mg_stamps.hpp"
 
@@ -2344,7 +2345,7 @@ static const double SCALE = 0.25;
 
 class MysteryFamily : public Family {
    public:
-    MysteryFamily(int variant, int n) : n_(n) {  // 0 MysteryPath-v0, 1 Endless-MysteryPath-v0, 2 MysteryPath-Grid-v0
+    MysteryFamily(int variant, int n) : Family(n), P_(sets_[0].P) {  // 0 MysteryPath-v0, 1 Endless-MysteryPath-v0, 2 MysteryPath-Grid-v0
         const int endless = variant == 1;
         memset(&P_, 0, sizeof(P_));
         P_.endless = endless;
@@ -2354,22 +2355,22 @@ class MysteryFamily : public Family {
         agent_speed_ = 12.0 * SCALE;
         P_.visual_feedback = 1;
         // Endless-MysteryPath: 187-189 -> 175-182 us per fused launch (profiles/r03_emp.md); no effect on MysteryPath-Grid's
-        P_.svc_prio = [endless] { const char* e = lab_env("MEMGYM_SVC_PRIO"); return e ? atoi(e) : (endless ? 1 : 0); }();
-        P_.path_help = [] { const char* e = lab_env("MEMGYM_PATH_HELP"); return e ? atoi(e) : 1; }();
+        P_.svc_prio = lab_int("MEMGYM_SVC_PRIO", endless ? 1 : 0);
+        P_.path_help = lab_int("MEMGYM_PATH_HELP", 1);
         P_.bg_coop = lab_int("MEMGYM_EMP_BG_COOP", n <= 20480 ? 1 : 0);
         P_.seg_cap = std::min(MAX_SEG, std::max(4, lab_int("MEMGYM_EMP_SEG_CAP", MAX_SEG)));    // (lab build: tests reach the capacities in a few
         P_.fall_cap = std::min(MAX_FALL, std::max(1, lab_int("MEMGYM_EMP_FALL_CAP", MAX_FALL)));  // hundred steps, tests/test_gpu_capacity.py)
-        lazy_wanted_ = endless && [] { const char* e = lab_env("MEMGYM_EMP_LAZY"); return e ? atoi(e) != 0 : true; }();
+        lazy_wanted_ = endless && lab_flag("MEMGYM_EMP_LAZY", true);
         // the next episode's first segment ahead of time (EMP_PRE): with the lane-per-path background jobs of the larger launches
         // (as entries of the service queue -- bg_coop -- a record ahead of time costs the path it saves)
-        pre_wanted_ = endless && !P_.bg_coop && lab_int("MEMGYM_EMP_PRE", 1) != 0;
+        pre_wanted_ = endless && !P_.bg_coop && lab_flag("MEMGYM_EMP_PRE", true);
         P_.r_fall = 0.0; P_.r_progress = 0.1; P_.r_step = 0.0;
         if (endless) {
             P_.max_steps = -1; P_.show_past_path = 1; camera_offset_scale_ = 5.0; P_.stamina_level = 20;
         } else {
             P_.max_steps = P_.grid ? 128 : 512;
             if (P_.grid) P_.r_progress = 0.0;
-            st_cardinal_.set(P_.cardinal, {0, 1, 2, 3});
+            sets_[0].st_cardinal.set(P_.cardinal, {0, 1, 2, 3});
             P_.r_goal = 1.0;
         }
         core_.alloc(n);
@@ -2402,11 +2403,11 @@ class MysteryFamily : public Family {
             segs_.alloc(16);
             aux_.alloc(4);
         }
-        sets_dev_.alloc(MG_MAX_OPTION_SETS);
-        hipLaunchKernelGGL(mystery_init_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, n, core_.p);
+        sets_.alloc();
+        launch(mystery_init_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, n, core_.p);
         MG_HIP(hipDeviceSynchronize());
         rebuild();
-        defaults_ = P_;  // (the cardinal list is short: no device array behind it)
+        sets_.defaults = P_;
     }
 
     // include/memgym.h: mg_set_capacity.  "path_segments" (Endless-MysteryPath-v0): records of the segment store per instance -- the
@@ -2419,9 +2420,7 @@ class MysteryFamily : public Family {
         seg_rows_ = (int)v;
         segs_.alloc((size_t)n_ * seg_rows_ * SEG_STRIDE);
         P_.seg_cap = seg_rows_;
-        for (auto& e : extra_) e->P.seg_cap = seg_rows_;
-        defaults_.seg_cap = seg_rows_;
-        sets_dirty_ = true;
+        sets_.refresh_geometry();
     }
     int64_t capacity(const std::string& what) const override {
         if (P_.endless && what == "path_segments") return P_.seg_cap;
@@ -2439,14 +2438,8 @@ class MysteryFamily : public Family {
     // does not change the geometry (sprites, camera offset and speeds are shared by the handle's instances).
     void set_option(const std::string& key, const double* v, int n) override { set_option_set(0, key, v, n); }
     void set_option_set(int set, const std::string& key, const double* v, int n) override {
-        if (set < 0 || set >= MG_MAX_OPTION_SETS) throw OptionError{-3, "option set index out of range"};
-        while ((int)extra_.size() < set) {  // a new set starts from the constructor's defaults (= the reference's), geometry from set 0
-            extra_.emplace_back(new MysteryOpt());
-            extra_.back()->P = defaults_;
-            copy_geometry(extra_.back()->P, P_);
-        }
-        MysteryParams& P = set == 0 ? P_ : extra_[set - 1]->P;
-        OptListStore& st_cardinal = set == 0 ? st_cardinal_ : extra_[set - 1]->st_cardinal;
+        MysteryOpt& O = sets_.ensure(set);
+        MysteryParams& P = O.P;
         const bool e = P_.endless;
         auto I = [&](int& dst) { dst = to_int_checked(v[0], key.c_str()); };
         auto B = [&](int& dst) { dst = v[0] != 0.0; };
@@ -2482,74 +2475,60 @@ class MysteryFamily : public Family {
                 const int c = to_int_checked(v[k], key.c_str());
                 vals[k] = (c >= 0 && c <= 2) ? c : 3;
             }
-            st_cardinal.set(P.cardinal, vals);
+            O.st_cardinal.set(P.cardinal, vals);
         }
         else if (!e && key == "show_goal") B(P.show_goal);
         else if (!e && key == "reward_goal") P.r_goal = v[0];
         else throw OptionError{-2, "unknown reset parameter " + key};
-        sets_dirty_ = true;
     }
-    // instance i runs under option set set_of_dev[i] (device array [num_envs], caller-owned; NULL: every instance under set 0)
-    void bind_option_sets(const int32_t* set_of_dev) override { set_of_ = set_of_dev; }
+    void bind_option_sets(const int32_t* set_of_dev) override { sets_.bind(set_of_dev); }
 
     void reset(const int64_t* seeds, const uint8_t* mask, void* obs, float* gt, hipStream_t s) override {
         if (dirty_) rebuild();
-        if (!seeds && !seeded_) throw std::runtime_error("reset(seed=None) before any seeded reset");
+        require_seeded(seeds);
         if (seeds) seeded_ = true;
-        const bool ps = per_set();
+        const bool ps = sets_.per_set();
         if (P_.endless) {
             mg_info_buffers none;
             memset(&none, 0, sizeof(none));
             // a masked reset(seed=None) of a handle whose steps run the fused arrangement: reset like the auto-reset step resets (lazy
             // segments, records ahead of time: emp_masked_reset_kernel); lab MEMGYM_EMP_MASKED_FAST=0: through the queue server like any other
-            static const bool fast_wanted = lab_int("MEMGYM_EMP_MASKED_FAST", 1) != 0;
+            static const bool fast_wanted = lab_flag("MEMGYM_EMP_MASKED_FAST", true);
             const bool fast = fast_wanted && mask && !seeds && !ps && lazy_wanted_ && fuse_serve() && obs_format == MG_OBS_U8_XYC && !big_sprites_;
             P_.lazy = fast ? 1 : 0;  // (otherwise an explicit reset generates all three segments; whatever an old episode is owed comes first)
             P_.pre = (fast && pre_wanted_) ? 1 : 0;
             P_.lazy_append = 0;
             if (fast) owed_possible_ = true;
-            upload_sets(s);
-            if (fast) {
-                hipLaunchKernelGGL(emp_masked_reset_kernel, dim3((n_ + 255) / 256), dim3(256), 0, s, P_, io(), mask, gt);
-                hipLaunchKernelGGL(emp_serve_kernel<false>, dim3(servers(false)), dim3(256), WS_BYTES, s, P_, io(), seeds, 0, (float*)nullptr,
-                                   (uint8_t*)nullptr, gt, none, 0);
+            sets_.upload(s);
+            if (fast) {  // (fast: one option set)
+                launch(emp_masked_reset_kernel, dim3((n_ + 255) / 256), dim3(256), 0, s, P_, io(), mask, gt);
+                serve(false, seeds, nullptr, nullptr, gt, none, 0, s);
             } else if (mask) {
-                hipLaunchKernelGGL(emp_enqueue_kernel, dim3((n_ + 255) / 256), dim3(256), 0, s, n_, io(), mask);
-                if (ps)
-                    hipLaunchKernelGGL(emp_serve_kernel<true>, dim3(servers(false)), dim3(256), WS_BYTES, s, P_, io(), seeds, 0, (float*)nullptr,
-                                       (uint8_t*)nullptr, gt, none, 0);
-                else
-                    hipLaunchKernelGGL(emp_serve_kernel<false>, dim3(servers(false)), dim3(256), WS_BYTES, s, P_, io(), seeds, 0, (float*)nullptr,
-                                       (uint8_t*)nullptr, gt, none, 0);
+                launch(emp_enqueue_kernel, dim3((n_ + 255) / 256), dim3(256), 0, s, n_, io(), mask);
+                serve(false, seeds, nullptr, nullptr, gt, none, 0, s);
             } else if (n_ >= 1024 && reset_by_lanes() && !ps) {  // many paths at once: one lane per instance
-                hipLaunchKernelGGL(emp_reset_lanes_kernel, dim3((n_ + 63) / 64), dim3(64), LW_BYTES, s, P_, io(), seeds, gt);
-            } else if (ps) {
-                hipLaunchKernelGGL(emp_serve_kernel<true>, dim3(servers(true)), dim3(256), WS_BYTES, s, P_, io(), seeds, 1, (float*)nullptr,
-                                   (uint8_t*)nullptr, gt, none, 0);
+                launch(emp_reset_lanes_kernel, dim3((n_ + 63) / 64), dim3(64), LW_BYTES, s, P_, io(), seeds, gt);
             } else {
-                hipLaunchKernelGGL(emp_serve_kernel<false>, dim3(servers(true)), dim3(256), WS_BYTES, s, P_, io(), seeds, 1, (float*)nullptr,
-                                   (uint8_t*)nullptr, gt, none, 0);
+                serve(true, seeds, nullptr, nullptr, gt, none, 0, s);
             }
         } else {
-            upload_sets(s);
-            if (ps) hipLaunchKernelGGL(mystery_reset_kernel<true>, dim3(blocks()), dim3(256), WS_BYTES, s, P_, io(), seeds, mask, nullptr, lpw());
-            else hipLaunchKernelGGL(mystery_reset_kernel<false>, dim3(blocks()), dim3(256), WS_BYTES, s, P_, io(), seeds, mask, nullptr, lpw());
+            sets_.upload(s);
+            with_bool(ps, [&](auto PS) {
+                launch(mystery_reset_kernel<decltype(PS)::value>, dim3(blocks()), dim3(256), WS_BYTES, s, P_, io(), seeds, mask, nullptr, lpw());
+            });
         }
         if (mask && sparse_masked_raster()) {  // few frames of many: by the mask, not by a walk over every descriptor (mg_raster_v1.hpp)
             if (big_sprites_) launch_raster_sparse<MysteryBigComposer>(desc_.p, atlas_->dev(), obs, obs_format, n_, s, mask);
             else launch_raster_sparse<MysteryComposer>(desc_.p, atlas_->dev(), obs, obs_format, n_, s, mask);
-            MG_HIP(hipGetLastError());
+            check_launch();
         } else raster(obs, s);
     }
 
     void step(const int32_t* actions, void* obs, float* reward, uint8_t* done, float* gt, const mg_info_buffers* info,
               int autoreset, hipStream_t s) override {
-        if (dirty_) throw std::runtime_error("options that change geometry need a reset before the next step");
-        mg_info_buffers ib;
-        memset(&ib, 0, sizeof(ib));
-        if (info) ib = *info;
+        const mg_info_buffers ib = begin_step(info);
         prof.begin(0, s);
-        const bool ps = per_set();
+        const bool ps = sets_.per_set();
         if (P_.endless) {
             // lazy initial segments need the fused launch (its frame workgroups carry the background jobs); any other path
             // first generates what earlier fused steps left owed
@@ -2561,14 +2540,16 @@ class MysteryFamily : public Family {
             P_.lazy_append = (P_.lazy && lazy_append) ? 1 : 0;
             if (!P_.lazy && owed_possible_) flush_owed(s);
             if (P_.lazy) owed_possible_ = true;
-            upload_sets(s);
+            sets_.upload(s);
             const int sb = step_block(256);
             // terminal observations (mg_step, mg_info_buffers.final_obs_dev): the FINAL forms of the two launches leave the terminal frame
             // descriptors in tdesc_, a sparse raster launch behind them draws those frames (round 6; keeps_final_obs)
             const bool keep_final = autoreset && ib.final_obs_dev && fused && keeps_final_obs(s);
-            if (ps) hipLaunchKernelGGL(emp_step_kernel<true>, dim3((n_ + sb - 1) / sb), dim3(sb), 0, s, P_, io(), actions, reward, done, gt, ib, autoreset);
-            else if (keep_final) hipLaunchKernelGGL((emp_step_kernel<false, true>), dim3((n_ + sb - 1) / sb), dim3(sb), 0, s, P_, io(), actions, reward, done, gt, ib, autoreset);
-            else hipLaunchKernelGGL(emp_step_kernel<false>, dim3((n_ + sb - 1) / sb), dim3(sb), 0, s, P_, io(), actions, reward, done, gt, ib, autoreset);
+            // (three of the four <PS, FINAL> forms exist: terminal observations are kept by handles with one option set only)
+            auto step_launch = [&](auto kernel) { launch(kernel, dim3((n_ + sb - 1) / sb), dim3(sb), 0, s, P_, io(), actions, reward, done, gt, ib, autoreset); };
+            if (ps) step_launch(emp_step_kernel<true>);
+            else if (keep_final) step_launch(emp_step_kernel<false, true>);
+            else step_launch(emp_step_kernel<false>);
             if (fused) {  // the queue is served inside the raster launch
                 end_logic(s);
                 prof.begin(1, s);
@@ -2582,57 +2563,44 @@ class MysteryFamily : public Family {
                 static const int bg_separate = lab_int("MEMGYM_EMP_BG_SEPARATE", 0);
                 const int bgw_later = bg_separate ? bgw : 0;
                 if (bg_separate) bgw = 0;
-                const int grid = (n_ < raster_grid(n_) ? n_ : raster_grid(n_)) + svc + bgw;  // (service, background, frames)
-                if (keep_final && nt)
-                    hipLaunchKernelGGL((emp_raster_serve_kernel<MG_OBS_U8_XYC, true, true>), dim3(grid), dim3(256), RASTER_LDS, s, desc_.p, atlas_->dev(), obs, n_,
-                                       P_, io(), reward, done, gt, ib, autoreset, svc, bgw, turn_);
-                else if (keep_final)
-                    hipLaunchKernelGGL((emp_raster_serve_kernel<MG_OBS_U8_XYC, false, true>), dim3(grid), dim3(256), RASTER_LDS, s, desc_.p, atlas_->dev(), obs, n_,
-                                       P_, io(), reward, done, gt, ib, autoreset, svc, bgw, turn_);
-                else if (nt)
-                    hipLaunchKernelGGL((emp_raster_serve_kernel<MG_OBS_U8_XYC, true>), dim3(grid), dim3(256), RASTER_LDS, s, desc_.p, atlas_->dev(), obs, n_,
-                                       P_, io(), reward, done, gt, ib, autoreset, svc, bgw, turn_);
-                else
-                    hipLaunchKernelGGL((emp_raster_serve_kernel<MG_OBS_U8_XYC, false>), dim3(grid), dim3(256), RASTER_LDS, s, desc_.p, atlas_->dev(), obs, n_,
-                                       P_, io(), reward, done, gt, ib, autoreset, svc, bgw, turn_);
-                MG_HIP(hipGetLastError());
+                const int grid = frames_grid(n_) + svc + bgw;  // (service, background, frames)
+                auto raster_serve = [&](auto kernel, int wgs, int bg) {
+                    launch(kernel, dim3(wgs), dim3(256), RASTER_LDS, s, desc_.p, atlas_->dev(), obs, n_, P_, io(), reward, done, gt, ib, autoreset, svc, bg, turn_);
+                };
+                with_bool(nt, [&](auto NT) {
+                    with_bool(keep_final, [&](auto FINAL) {
+                        raster_serve(emp_raster_serve_kernel<MG_OBS_U8_XYC, decltype(NT)::value, decltype(FINAL)::value>, grid, bgw);
+                    });
+                });
+                check_launch();
                 if (keep_final)  // every finished instance's flag is in `done` by now (the service workgroups wrote the last of them)
                     launch_raster_sparse<MysteryComposer>(tdesc_.p, atlas_->dev(), ib.final_obs_dev, MG_OBS_U8_XYC, n_, s, done);
                 prof.end(1, s);
                 if (bgw_later)  // (grid = service + background workgroups only: no frames; the queue is empty by now)
-                    hipLaunchKernelGGL((emp_raster_serve_kernel<MG_OBS_U8_XYC, false>), dim3(svc + bgw_later), dim3(256), RASTER_LDS, s, desc_.p, atlas_->dev(), obs, n_,
-                                       P_, io(), reward, done, gt, ib, autoreset, svc, bgw_later, turn_);
+                    raster_serve(emp_raster_serve_kernel<MG_OBS_U8_XYC, false>, svc + bgw_later, bgw_later);
 #ifdef MG_LAB_EMP_CLOCK  // diagnosis: is the next logic kernel slow because the L2 is full of dirty observation lines?
-                static const int wb = [] { const char* e = lab_env("MEMGYM_LAB_WBL2"); return e ? atoi(e) : 0; }();
-                if (wb) hipLaunchKernelGGL(lab_wbl2_kernel, dim3(wb), dim3(64), 0, s);
+                static const int wb = lab_int("MEMGYM_LAB_WBL2", 0);
+                if (wb) launch(lab_wbl2_kernel, dim3(wb), dim3(64), 0, s);
 #endif
                 return;
             }
-            if (ps)
-                hipLaunchKernelGGL(emp_serve_kernel<true>, dim3(servers(false)), dim3(256), WS_BYTES, s, P_, io(), (const int64_t*)nullptr, 0,
-                                   reward, done, gt, ib, autoreset);
-            else
-                hipLaunchKernelGGL(emp_serve_kernel<false>, dim3(servers(false)), dim3(256), WS_BYTES, s, P_, io(), (const int64_t*)nullptr, 0,
-                                   reward, done, gt, ib, autoreset);
+            serve(false, nullptr, reward, done, gt, ib, autoreset, s);
         } else {
             // (per-instance option sets: only this kernel has a <PS> form -- the raster launch's path service reads nothing of the options)
             const int defer = (autoreset && !big_sprites_) ? defer_mode() : 0;
-            upload_sets(s);
+            sets_.upload(s);
+            // (three of the four <PS, FINAL> forms exist: terminal observations are kept by handles with one option set only)
+            auto step_launch = [&](auto kernel) { launch(kernel, dim3(blocks()), dim3(256), WS_BYTES, s, P_, io(), actions, reward, done, nullptr, ib, autoreset, lpw(), defer); };
             if (autoreset && ib.final_obs_dev && keeps_final_obs(s)) {  // terminal observations kept by these two launches (defer != 0, one option set)
-                hipLaunchKernelGGL((mystery_step_kernel<false, true>), dim3(blocks()), dim3(256), WS_BYTES, s, P_, io(), actions, reward, done,
-                                   (float*)nullptr, ib, autoreset, lpw(), defer);
+                step_launch(mystery_step_kernel<false, true>);
                 end_logic(s);
                 prof.begin(1, s);
                 raster_with_paths(obs, s, ib.final_obs_dev);
                 prof.end(1, s);
                 return;
             }
-            if (ps)
-                hipLaunchKernelGGL(mystery_step_kernel<true>, dim3(blocks()), dim3(256), WS_BYTES, s, P_, io(), actions, reward, done,
-                                   (float*)nullptr, ib, autoreset, lpw(), defer);
-            else
-                hipLaunchKernelGGL(mystery_step_kernel<false>, dim3(blocks()), dim3(256), WS_BYTES, s, P_, io(), actions, reward, done,
-                                   (float*)nullptr, ib, autoreset, lpw(), defer);
+            if (ps) step_launch(mystery_step_kernel<true>);
+            else step_launch(mystery_step_kernel<false>);
             if (defer) {  // the paths of this step's resets are generated by the first workgroups of the raster launch
                 end_logic(s);
                 prof.begin(1, s);
@@ -2654,17 +2622,10 @@ class MysteryFamily : public Family {
         rng_.blobs(v);
         return v;
     }
-    void debug_rng(int i, uint64_t out[6]) override { rng_.debug(i, out); }
     void ground_truth64(double* out, hipStream_t s) override {
         if (!gt_dim() || !out) return;
-        hipLaunchKernelGGL(mystery_gt64_kernel, dim3((n_ + 255) / 256), dim3(256), 0, s, n_, core_.p, out);
-        MG_HIP(hipGetLastError());
+        launch_checked(mystery_gt64_kernel, dim3((n_ + 255) / 256), dim3(256), 0, s, n_, core_.p, out);
     }
-    int poll_errors() override {
-        MG_HIP(hipDeviceSynchronize());
-        return err_.take();
-    }
-    int peek_errors() override { return err_.peek(); }
     bool debug_counter(const std::string& name, int64_t* out) override {
         if (name == "emp_segments_sum" || name == "emp_segments_max" || name == "emp_falloff_max") {  // a scan of the state records as they stand
             std::vector<MysteryCore> h(n_);
@@ -2690,19 +2651,13 @@ class MysteryFamily : public Family {
    private:
     // instance-carrying lanes per wave (see instance_of_lane); MEMGYM_MYSTERY_LPW overrides for tuning
     int lpw() const {
-        static const int forced = [] {
-            const char* e = lab_env("MEMGYM_MYSTERY_LPW");
-            return e ? atoi(e) : 0;
-        }();
+        static const int forced = lab_int("MEMGYM_MYSTERY_LPW", 0);
         if (forced == 4 || forced == 8 || forced == 16 || forced == 32 || forced == 64) return forced;
         return 16;  // measured: profiles/r01e_logic_tails.md (the endless variant has its own kernels)
     }
     // workgroups (4 waves each) of emp_serve_kernel; MEMGYM_EMP_SERVERS overrides for tuning
     int servers(bool all) const {
-        static const int forced = [] {
-            const char* e = lab_env("MEMGYM_EMP_SERVERS");
-            return e ? atoi(e) : 0;
-        }();
+        static const int forced = lab_int("MEMGYM_EMP_SERVERS", 0);
         const int want = forced > 0 ? forced : (all ? 1024 : 512);  // measured: profiles/r01e_logic_tails.md section 4
         const int cap = (n_ + 3) / 4;
         return want < cap ? want : cap;
@@ -2714,18 +2669,12 @@ class MysteryFamily : public Family {
     // (280 -> 275 M), so only the grid variant defers by default.  MEMGYM_MYSTERY_DEFER=0 / 1 forces it off / on.
     // MEMGYM_EMP_FUSE=0: separate queue-server launch in front of the raster (the round-1 arrangement)
     bool fuse_serve() const {
-        static const bool on = [] {
-            const char* e = lab_env("MEMGYM_EMP_FUSE");
-            return !(e && atoi(e) == 0);
-        }();
+        static const bool on = lab_flag("MEMGYM_EMP_FUSE", true);
         return on;
     }
     // MEMGYM_EMP_RESET_LANES=0: a full reset through the queue server, one wave per instance (round 1)
     bool reset_by_lanes() const {
-        static const bool on = [] {
-            const char* e = lab_env("MEMGYM_EMP_RESET_LANES");
-            return !(e && atoi(e) == 0);
-        }();
+        static const bool on = lab_flag("MEMGYM_EMP_RESET_LANES", true);
         return on;
     }
     // 0: paths of auto-resets in the step kernel; 1: all of them queued for the raster launch (MysteryPath-Grid: 0.5 % of the
@@ -2733,34 +2682,28 @@ class MysteryFamily : public Family {
     // HYBRID_INLINE of them (MysteryPath-v0: its 512-step episodes reset too rarely to pay for always queueing, but the step
     // in which all survivors are truncated at once was a 450-us launch).  MEMGYM_MYSTERY_DEFER=0 / 1 / 2 forces a mode.
     int defer_mode() const {
-        static const int forced = [] {
-            const char* e = lab_env("MEMGYM_MYSTERY_DEFER");
-            return e ? atoi(e) : -1;
-        }();
+        static const int forced = lab_int("MEMGYM_MYSTERY_DEFER", -1);
         return forced >= 0 && forced <= 2 ? forced : (P_.grid != 0 ? 1 : 2);
     }
+    // the queue server of the endless variant as a launch of its own: `all` = every instance (a full reset), else the queued ones
+    void serve(bool all, const int64_t* seeds, float* reward, uint8_t* done, float* gt, const mg_info_buffers& ib, int autoreset, hipStream_t s) {
+        with_bool(sets_.per_set(), [&](auto PS) {
+            launch(emp_serve_kernel<decltype(PS)::value>, dim3(servers(all)), dim3(256), WS_BYTES, s, P_, io(), seeds, all ? 1 : 0, reward, done, gt, ib, autoreset);
+        });
+    }
     void raster_with_paths(void* obs, hipStream_t s, void* final_obs = nullptr) {
-        const int grid = (n_ < raster_grid(n_) ? n_ : raster_grid(n_)) + PATH_WGS;
-        void* const none = nullptr;
-        if (final_obs)  // (uint8 format: keeps_final_obs)
-            hipLaunchKernelGGL((mystery_raster_paths_kernel<MG_OBS_U8_XYC, true>), dim3(grid), dim3(256), RASTER_LDS, s, desc_.p, atlas_->dev(), obs, n_, P_, io(), final_obs);
-        else if (obs_format == MG_OBS_F32_CYX)
-            hipLaunchKernelGGL((mystery_raster_paths_kernel<MG_OBS_F32_CYX>), dim3(grid), dim3(256), RASTER_LDS, s, desc_.p, atlas_->dev(), obs, n_, P_, io(), none);
-        else if (obs_format == MG_OBS_BF16_CYX)
-            hipLaunchKernelGGL((mystery_raster_paths_kernel<MG_OBS_BF16_CYX>), dim3(grid), dim3(256), RASTER_LDS, s, desc_.p, atlas_->dev(), obs, n_, P_, io(), none);
-        else if (obs_format == MG_OBS_F16_CYX)
-            hipLaunchKernelGGL((mystery_raster_paths_kernel<MG_OBS_F16_CYX>), dim3(grid), dim3(256), RASTER_LDS, s, desc_.p, atlas_->dev(), obs, n_, P_, io(), none);
-        else
-            hipLaunchKernelGGL((mystery_raster_paths_kernel<MG_OBS_U8_XYC>), dim3(grid), dim3(256), RASTER_LDS, s, desc_.p, atlas_->dev(), obs, n_, P_, io(), none);
-        MG_HIP(hipGetLastError());
+        const dim3 grid(frames_grid(n_) + PATH_WGS);
+        auto paths_launch = [&](auto kernel) { launch_checked(kernel, grid, dim3(256), RASTER_LDS, s, desc_.p, atlas_->dev(), obs, n_, P_, io(), final_obs); };
+        if (final_obs) paths_launch(mystery_raster_paths_kernel<MG_OBS_U8_XYC, true>);  // (the FINAL form exists for the uint8 format only: keeps_final_obs)
+        else with_obs_format(obs_format, [&](auto F) { paths_launch(mystery_raster_paths_kernel<decltype(F)::value>); });
     }
     // (the finite variants' step + raster / path-service launches keep terminal observations themselves; lab MEMGYM_MYSTERY_FINAL_FUSED=0: the
     // generic path of mg_step.  Endless Mystery Path: its step kernel and the service waves of its fused launch leave the terminal frame
     // DESCRIPTORS behind, one sparse raster launch draws them -- lab MEMGYM_EMP_FINAL_FUSED=0: the generic path.)
     bool keeps_final_obs(hipStream_t) override {
-        static const bool wanted = lab_int("MEMGYM_MYSTERY_FINAL_FUSED", 1) != 0, emp_wanted = lab_int("MEMGYM_EMP_FINAL_FUSED", 1) != 0;
-        if (P_.endless) return emp_wanted && fuse_serve() && obs_format == MG_OBS_U8_XYC && !big_sprites_ && !per_set();
-        return wanted && obs_format == MG_OBS_U8_XYC && !big_sprites_ && !per_set() && defer_mode() != 0;
+        static const bool wanted = lab_flag("MEMGYM_MYSTERY_FINAL_FUSED", true), emp_wanted = lab_flag("MEMGYM_EMP_FINAL_FUSED", true);
+        if (P_.endless) return emp_wanted && fuse_serve() && obs_format == MG_OBS_U8_XYC && !big_sprites_ && !sets_.per_set();
+        return wanted && obs_format == MG_OBS_U8_XYC && !big_sprites_ && !sets_.per_set() && defer_mode() != 0;
     }
     MysteryIO io() {
         MysteryIO o;
@@ -2778,40 +2721,25 @@ class MysteryFamily : public Family {
         o.aux = aux_.p;
         o.jump = jump_.p;
         o.stats = stats_.p;
-        o.sets = per_set() ? sets_dev_.p : nullptr;
-        o.set_of = per_set() ? set_of_ : nullptr;
+        o.sets = sets_.dev();
+        o.set_of = sets_.set_of();
         o.tdesc = tdesc_.p;
         return o;
     }
 
-    // per-instance option sets
+    // one option set: the parameter block and the list behind it
     struct MysteryOpt {
         MysteryParams P;
         OptListStore st_cardinal;
-    };
-    // what the shared atlas, the camera and the launch arrangement fix for every set of the handle
-    static void copy_geometry(MysteryParams& d, const MysteryParams& s) {
-        d.endless = s.endless; d.grid = s.grid; d.n = s.n; d.depth = s.depth; d.agent_radius = s.agent_radius; d.sprite_dim = s.sprite_dim;
-        d.v_axis_i = s.v_axis_i; d.v_diag_i = s.v_diag_i; d.tile = s.tile; d.cross_dim = s.cross_dim; d.camera_offset = s.camera_offset;
-        d.svc_prio = s.svc_prio; d.lazy = s.lazy; d.path_help = s.path_help; d.bg_coop = s.bg_coop; d.pre = s.pre; d.lazy_append = s.lazy_append;
-        d.seg_cap = s.seg_cap; d.fall_cap = s.fall_cap;
-    }
-    bool per_set() const { return set_of_ != nullptr && !extra_.empty(); }
-    // the sets as the kernels read them, stream-ordered behind what the stream holds (pageable source: staged before the call returns)
-    void upload_sets(hipStream_t s) {
-        if (!per_set() || !sets_dirty_) return;
-        MysteryParams fresh = defaults_;  // a set that was never written: the reference's defaults under the handle's geometry (include/memgym.h)
-        copy_geometry(fresh, P_);
-        std::vector<MysteryParams> host(MG_MAX_OPTION_SETS, fresh);
-        host[0] = P_;
-        for (size_t k = 0; k < extra_.size(); ++k) {
-            host[k + 1] = extra_[k]->P;
-            copy_geometry(host[k + 1], P_);  // (incl. lazy = 0: the plain arrangement generates every segment when it is due)
+        // what the shared atlas, the camera and the launch arrangement fix for every set of the handle (incl. lazy = 0 whenever sets
+        // are in use: the plain arrangement generates every segment when it is due)
+        static void copy_geometry(MysteryParams& d, const MysteryParams& s) {
+            d.endless = s.endless; d.grid = s.grid; d.n = s.n; d.depth = s.depth; d.agent_radius = s.agent_radius; d.sprite_dim = s.sprite_dim;
+            d.v_axis_i = s.v_axis_i; d.v_diag_i = s.v_diag_i; d.tile = s.tile; d.cross_dim = s.cross_dim; d.camera_offset = s.camera_offset;
+            d.svc_prio = s.svc_prio; d.lazy = s.lazy; d.path_help = s.path_help; d.bg_coop = s.bg_coop; d.pre = s.pre; d.lazy_append = s.lazy_append;
+            d.seg_cap = s.seg_cap; d.fall_cap = s.fall_cap;
         }
-        MG_HIP(hipMemcpyAsync(sets_dev_.p, host.data(), sizeof(MysteryParams) * host.size(), hipMemcpyHostToDevice, s));
-        MG_HIP(hipStreamSynchronize(s));  // (rare: only after an option of some set changed)
-        sets_dirty_ = false;
-    }
+    };
 
     void rebuild() {
         int radius = 0;
@@ -2858,20 +2786,14 @@ class MysteryFamily : public Family {
     void raster_only(void* obs, const uint8_t* only, hipStream_t s) override {
         if (big_sprites_) launch_raster<MysteryBigComposer>(desc_.p, atlas_->dev(), obs, obs_format, n_, s, only);
         else launch_raster<MysteryComposer>(desc_.p, atlas_->dev(), obs, obs_format, n_, s, only);
-        MG_HIP(hipGetLastError());
+        check_launch();
     }
 
     void raster(void* obs, hipStream_t s) { raster_only(obs, nullptr, s); }
 
-    int n_;
-    MysteryParams P_;       // option set 0 (the handle-wide set of mg_set_option)
-    MysteryParams defaults_;
-    std::vector<std::unique_ptr<MysteryOpt>> extra_;  // option sets 1 ..
-    const int32_t* set_of_ = nullptr;
-    bool sets_dirty_ = true;
-    DevArray<MysteryParams> sets_dev_;
+    OptionSets<MysteryOpt> sets_;
+    MysteryParams& P_;  // set 0, the handle-wide set
     double agent_scale_, agent_speed_, camera_offset_scale_ = 5.0;
-    bool dirty_ = true, seeded_ = false;
     bool big_sprites_ = false;  // rebuild(): the agent sprites exceed MysteryComposer's registers
 
    public:
@@ -2887,8 +2809,7 @@ class MysteryFamily : public Family {
         }
     }
     void flush_owed(hipStream_t s) {
-        hipLaunchKernelGGL(emp_flush_owed_kernel, dim3((n_ + 63) / 64), dim3(64), LW_BYTES, s, P_, io());
-        MG_HIP(hipGetLastError());
+        launch_checked(emp_flush_owed_kernel, dim3((n_ + 63) / 64), dim3(64), LW_BYTES, s, P_, io());
         owed_possible_ = false;
     }
     void raster_debug(void* frames, hipStream_t s) override;
@@ -2908,22 +2829,21 @@ class MysteryFamily : public Family {
     DevArray<uint4> jump_;  // WaveRng jump constants
     DevArray<unsigned long long> stats_;  // MysteryIO::stats
     DevArray<uint64_t> walls_;  // finite: wall cells of every instance's path generation (debug view)
-    ErrorWord err_;
-    RngStore rng_;
-    OptListStore st_cardinal_;
 };
 
 void MysteryFamily::raster_debug(void* frames, hipStream_t s) {
-    if (dirty_) throw std::runtime_error("options that change geometry need a reset before the next render");
-    DevArray<MysteryDesc> dbg;
-    dbg.alloc(n_, false);
-    upload_sets(s);
-    if (per_set()) hipLaunchKernelGGL(mystery_debug_desc_kernel<true>, dim3((n_ + 255) / 256), dim3(256), 0, s, P_, io(), dbg.p);
-    else hipLaunchKernelGGL(mystery_debug_desc_kernel<false>, dim3((n_ + 255) / 256), dim3(256), 0, s, P_, io(), dbg.p);
-    if (big_sprites_) launch_raster<MysteryDebugBigComposer>(dbg.p, atlas_->dev(), frames, MG_OBS_U8_XYC, n_, s);
-    else launch_raster<MysteryDebugComposer>(dbg.p, atlas_->dev(), frames, MG_OBS_U8_XYC, n_, s);
-    MG_HIP(hipGetLastError());
-    MG_HIP(hipStreamSynchronize(s));  // dbg is released on return
+    debug_frames<MysteryDesc>(
+        s,
+        [&](MysteryDesc* dbg) {
+            sets_.upload(s);
+            with_bool(sets_.per_set(), [&](auto PS) {
+                launch(mystery_debug_desc_kernel<decltype(PS)::value>, dim3((n_ + 255) / 256), dim3(256), 0, s, P_, io(), dbg);
+            });
+        },
+        [&](MysteryDesc* dbg) {
+            if (big_sprites_) launch_raster<MysteryDebugBigComposer>(dbg, atlas_->dev(), frames, MG_OBS_U8_XYC, n_, s);
+            else launch_raster<MysteryDebugComposer>(dbg, atlas_->dev(), frames, MG_OBS_U8_XYC, n_, s);
+        });
 }
 
 Family* make_mystery(int variant, int num_envs) { return new MysteryFamily(variant, num_envs); }

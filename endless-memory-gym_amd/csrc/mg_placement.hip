@@ -25,7 +25,9 @@
 
 #include "mg_family.hpp"
 #include "mg_lab.hpp"
-using mg::lab_env;
+using mg::lab_double;
+using mg::lab_flag;
+using mg::lab_set;
 
 namespace {
 
@@ -40,8 +42,8 @@ constexpr int PROBE_GRID = 14336;
 // thresholds become relative: the geometric mean across the gap between the clusters -/+ 1.5 %.  A
 // search whose earlier decisions the calibrated thresholds would change starts over once.  (A piece paired with ITSELF is no
 // calibration: both windows then hit the same cache lines, 11.6 TB/s.)  MEMGYM_OBS_SAME_TBPS / MEMGYM_OBS_CROSS_TBPS set the prior.
-static const double PRIOR_SAME_TBPS = lab_env("MEMGYM_OBS_SAME_TBPS") ? atof(lab_env("MEMGYM_OBS_SAME_TBPS")) : 5.35;
-static const double PRIOR_CROSS_TBPS = lab_env("MEMGYM_OBS_CROSS_TBPS") ? atof(lab_env("MEMGYM_OBS_CROSS_TBPS")) : 5.85;
+static const double PRIOR_SAME_TBPS = lab_double("MEMGYM_OBS_SAME_TBPS", 5.35);
+static const double PRIOR_CROSS_TBPS = lab_double("MEMGYM_OBS_CROSS_TBPS", 5.85);
 struct Calib {
     // Round 4: the thresholds turn relative only on evidence of TWO clusters -- at least two probes on either side of the
     // widest gap between neighbouring samples, that gap >= 7 % and the whole spread >= 15 %.  The first version switched as soon as
@@ -209,7 +211,7 @@ __global__ __launch_bounds__(256) void store_probe_frames_pairs_kernel(u32x4* ou
 // scribble over memory that belongs to somebody else by now.  A reservation costs address space only (a few GiB of the
 // 128-TiB space per call), so unmapped ranges simply stay reserved.  MEMGYM_OBS_REUSE_VA=1 restores the frees (experiments).
 inline void va_free(void* va, size_t bytes) {
-    static const bool reuse = lab_env("MEMGYM_OBS_REUSE_VA") && atoi(lab_env("MEMGYM_OBS_REUSE_VA")) != 0;
+    static const bool reuse = lab_flag("MEMGYM_OBS_REUSE_VA", false);
     if (reuse) (void)hipMemAddressFree(va, bytes);
 }
 
@@ -265,7 +267,7 @@ hipError_t va_reserve(void** va, size_t bytes) {
 }
 
 bool create_piece(int device, size_t bytes, Piece* out, bool exportable = false) {
-    static const bool no_vmm = lab_env("MEMGYM_OBS_NO_VMM") && atoi(lab_env("MEMGYM_OBS_NO_VMM")) != 0;  // tests: a runtime without hipMemCreate
+    static const bool no_vmm = lab_flag("MEMGYM_OBS_NO_VMM", false);  // tests: a runtime without hipMemCreate
     if (no_vmm) return false;
     hipMemAllocationProp p = prop_for(device);
     if (exportable) p.requestedHandleType = hipMemHandleTypePosixFileDescriptor;
@@ -509,7 +511,7 @@ int mg_obs_alloc_for(int device, size_t bytes, size_t frame_bytes, size_t search
             ~Restore() { (void)hipSetDevice(d); }
         } restore{prev};
         const auto t0 = std::chrono::steady_clock::now();
-        const bool debug = lab_env("MEMGYM_OBS_DEBUG") != nullptr;
+        const bool debug = lab_set("MEMGYM_OBS_DEBUG");
         *out = nullptr;
         size_t free_b = 0, total_b = 0;
         MG_HIP(hipMemGetInfo(&free_b, &total_b));

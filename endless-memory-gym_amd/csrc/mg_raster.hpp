@@ -27,6 +27,7 @@
 
 #include "../../include/memgym.h"
 #include "mg_lab.hpp"
+#include "mg_launch.hpp"
 #include "mg_device.hpp"
 #include "mg_stream_out.hpp"
 
@@ -389,65 +390,43 @@ __global__ __launch_bounds__(256) void raster_sparse_kernel(const typename Compo
 // optimum with plain stores at seven per CU (profiles/r03_spot_store_lab.md: 7,168 / 9,728 / 14,336 -> 60.7 / 59.7 / 64.5 us).
 // At 32,768 frames and beyond 14,336 workgroups win (32,768: 121.4 against 124.1-127.1 us for 7,168-12,288).
 inline int raster_grid(int n) {
-    static const int forced = [] {
-        const char* e = lab_env("MEMGYM_RASTER_GRID");
-        return e ? atoi(e) : 0;
-    }();
-    return forced > 0 ? forced : (n <= 24576 ? RASTER_GRID_SMALL : RASTER_GRID);
+    const int forced = lab_raster_grid();
+    return forced ? forced : (n <= 24576 ? RASTER_GRID_SMALL : RASTER_GRID);
 }
+inline int frames_grid(int n) { return std::min(n, raster_grid(n)); }  // frame workgroups of a launch over n frames
 
 // Store flavour of the uint8 stream for a launch over n frames.  Plain stores are the faster stream (16,384 frames: 59.7 us
 // = 5.8 TB/s against 63.3 us non-temporal) but pass through the caches, and the logic kernel then finds less of its state
 // there: +2-3 us at 16,384 instances (212 vs 208 M env-steps/s, plain wins), +10 us at 65,536 (223 vs 230 M, non-temporal
 // wins).  MEMGYM_RASTER_NT = 0 / 1 forces one (tuning only).  profiles/r03_spot_store_lab.md.
 inline bool raster_nt(int n) {
-    static const int forced = [] {
-        const char* e = lab_env("MEMGYM_RASTER_NT");
-        return e ? (atoi(e) != 0 ? 1 : 0) : -1;
-    }();
+    static const int forced = lab_forced("MEMGYM_RASTER_NT");
     return forced >= 0 ? forced != 0 : n > RASTER_PLAIN_MAX;
 }
 
 template <class Composer>
 inline void launch_raster(const typename Composer::Desc* descs, const RasterAtlas& atlas, void* obs, int fmt, int n, hipStream_t s,
                           const uint8_t* only = nullptr) {
-    const int tuned = raster_grid(n);
     // The kernel needs RASTER_LDS (22,176 B: 7 workgroups per CU).  A NON-TEMPORAL stream is faster with fewer concurrent
     // writers than fit and asks for 25 KiB = SIX per CU (profiles/r03_spot_grid.md, Endless-SearingSpotlights 16,384 frames: six
     // per CU x 8,960-10,240 workgroups 65.4-66.1 us, five x 14,336 (round 2) 71.4, seven x 8,960 68.4, four 80-84); plain
     // stores -- small launches and the float formats -- want all seven (7: 59.7, 6: 62.3 us; profiles/r03_spot_store_lab.md).
     // MEMGYM_RASTER_LDS overrides (tuning only).
-    static const int forced_lds = [] {
-        const char* e = lab_env("MEMGYM_RASTER_LDS");
-        return e && atoi(e) >= RASTER_LDS ? atoi(e) : 0;
-    }();
+    const int forced_lds = lab_raster_lds(RASTER_LDS);
     const bool nt = fmt == MG_OBS_U8_XYC && raster_nt(n);
     const int lds = forced_lds ? forced_lds : (nt ? RASTER_LDS_REQUEST : RASTER_LDS);
-    const int grid = n < tuned ? n : tuned;
-    if (fmt == MG_OBS_F32_CYX)
-        hipLaunchKernelGGL((raster_kernel<Composer, MG_OBS_F32_CYX, false>), dim3(grid), dim3(256), lds, s, descs, atlas, obs, n, only);
-    else if (fmt == MG_OBS_BF16_CYX)
-        hipLaunchKernelGGL((raster_kernel<Composer, MG_OBS_BF16_CYX, false>), dim3(grid), dim3(256), lds, s, descs, atlas, obs, n, only);
-    else if (fmt == MG_OBS_F16_CYX)
-        hipLaunchKernelGGL((raster_kernel<Composer, MG_OBS_F16_CYX, false>), dim3(grid), dim3(256), lds, s, descs, atlas, obs, n, only);
-    else if (nt)
-        hipLaunchKernelGGL((raster_kernel<Composer, MG_OBS_U8_XYC, true>), dim3(grid), dim3(256), lds, s, descs, atlas, obs, n, only);
+    const dim3 grid(frames_grid(n));
+    if (nt)  // (the non-temporal stream exists for the uint8 format only)
+        launch(raster_kernel<Composer, MG_OBS_U8_XYC, true>, grid, dim3(256), lds, s, descs, atlas, obs, n, only);
     else
-        hipLaunchKernelGGL((raster_kernel<Composer, MG_OBS_U8_XYC, false>), dim3(grid), dim3(256), lds, s, descs, atlas, obs, n, only);
+        with_obs_format(fmt, [&](auto F) { launch(raster_kernel<Composer, decltype(F)::value, false>, grid, dim3(256), lds, s, descs, atlas, obs, n, only); });
 }
 
 template <class Composer>
 inline void launch_raster_sparse(const typename Composer::Desc* descs, const RasterAtlas& atlas, void* obs, int fmt, int n, hipStream_t s,
                                  const uint8_t* only) {
-    const int grid = std::min((n + SPARSE_CHUNK - 1) / SPARSE_CHUNK, 8192);
-    if (fmt == MG_OBS_F32_CYX)
-        hipLaunchKernelGGL((raster_sparse_kernel<Composer, MG_OBS_F32_CYX>), dim3(grid), dim3(256), RASTER_LDS, s, descs, atlas, obs, n, only);
-    else if (fmt == MG_OBS_BF16_CYX)
-        hipLaunchKernelGGL((raster_sparse_kernel<Composer, MG_OBS_BF16_CYX>), dim3(grid), dim3(256), RASTER_LDS, s, descs, atlas, obs, n, only);
-    else if (fmt == MG_OBS_F16_CYX)
-        hipLaunchKernelGGL((raster_sparse_kernel<Composer, MG_OBS_F16_CYX>), dim3(grid), dim3(256), RASTER_LDS, s, descs, atlas, obs, n, only);
-    else
-        hipLaunchKernelGGL((raster_sparse_kernel<Composer, MG_OBS_U8_XYC>), dim3(grid), dim3(256), RASTER_LDS, s, descs, atlas, obs, n, only);
+    const dim3 grid(std::min((n + SPARSE_CHUNK - 1) / SPARSE_CHUNK, 8192));
+    with_obs_format(fmt, [&](auto F) { launch(raster_sparse_kernel<Composer, decltype(F)::value>, grid, dim3(256), RASTER_LDS, s, descs, atlas, obs, n, only); });
 }
 
 }  // namespace mg

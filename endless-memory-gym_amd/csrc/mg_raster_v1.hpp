@@ -32,6 +32,7 @@
 
 #include "../../include/memgym.h"
 #include "mg_lab.hpp"
+#include "mg_launch.hpp"
 #include "mg_device.hpp"
 #include "mg_stream_out.hpp"
 
@@ -222,49 +223,29 @@ __global__ __launch_bounds__(256) void raster_sparse_kernel(const typename Compo
 }
 
 // Workgroups of a raster launch over n frames (MEMGYM_RASTER_GRID overrides: tuning experiments)
-inline int raster_grid(int n) {
-    static const int forced = [] {
-        const char* e = lab_env("MEMGYM_RASTER_GRID");
-        return e ? atoi(e) : 0;
-    }();
-    (void)n;
-    return forced > 0 ? forced : RASTER_GRID;
+inline int raster_grid(int) {
+    const int forced = lab_raster_grid();
+    return forced ? forced : RASTER_GRID;
 }
+inline int frames_grid(int n) { return std::min(n, raster_grid(n)); }  // frame workgroups of a launch over n frames
 
 template <class Composer>
 inline void launch_raster(const typename Composer::Desc* descs, const RasterAtlas& atlas, void* obs, int fmt, int n, hipStream_t s,
                           const uint8_t* only = nullptr) {
-    const int tuned = raster_grid(n);
-    const int grid = n < tuned ? n : tuned;
     // MEMGYM_RASTER_LDS inflates the LDS request = fewer resident workgroups per CU (tuning only).  Seven per CU (what
     // fits) is the optimum once the observation buffer sits in a fast allocation (profiles/r01l_placement.md):
     // MortarMayhem-Grid 223.4-224.5 us at 7, 229.4 at 6, 243-244 at 5; in a slow allocation 6 was 1-3 % ahead of 7.
-    static const int lds = [] {
-        const char* e = lab_env("MEMGYM_RASTER_LDS");
-        return e && atoi(e) >= RASTER_LDS ? atoi(e) : RASTER_LDS;
-    }();
-    if (fmt == MG_OBS_F32_CYX)
-        hipLaunchKernelGGL((raster_kernel<Composer, MG_OBS_F32_CYX>), dim3(grid), dim3(256), lds, s, descs, atlas, obs, n, only);
-    else if (fmt == MG_OBS_BF16_CYX)
-        hipLaunchKernelGGL((raster_kernel<Composer, MG_OBS_BF16_CYX>), dim3(grid), dim3(256), lds, s, descs, atlas, obs, n, only);
-    else if (fmt == MG_OBS_F16_CYX)
-        hipLaunchKernelGGL((raster_kernel<Composer, MG_OBS_F16_CYX>), dim3(grid), dim3(256), lds, s, descs, atlas, obs, n, only);
-    else
-        hipLaunchKernelGGL((raster_kernel<Composer, MG_OBS_U8_XYC>), dim3(grid), dim3(256), lds, s, descs, atlas, obs, n, only);
+    const int forced_lds = lab_raster_lds(RASTER_LDS);
+    const int lds = forced_lds ? forced_lds : RASTER_LDS;
+    const dim3 grid(frames_grid(n));
+    with_obs_format(fmt, [&](auto F) { launch(raster_kernel<Composer, decltype(F)::value>, grid, dim3(256), lds, s, descs, atlas, obs, n, only); });
 }
 
 template <class Composer>
 inline void launch_raster_sparse(const typename Composer::Desc* descs, const RasterAtlas& atlas, void* obs, int fmt, int n, hipStream_t s,
                                  const uint8_t* only) {
-    const int grid = std::min((n + SPARSE_CHUNK - 1) / SPARSE_CHUNK, 8192);
-    if (fmt == MG_OBS_F32_CYX)
-        hipLaunchKernelGGL((raster_sparse_kernel<Composer, MG_OBS_F32_CYX>), dim3(grid), dim3(256), RASTER_LDS, s, descs, atlas, obs, n, only);
-    else if (fmt == MG_OBS_BF16_CYX)
-        hipLaunchKernelGGL((raster_sparse_kernel<Composer, MG_OBS_BF16_CYX>), dim3(grid), dim3(256), RASTER_LDS, s, descs, atlas, obs, n, only);
-    else if (fmt == MG_OBS_F16_CYX)
-        hipLaunchKernelGGL((raster_sparse_kernel<Composer, MG_OBS_F16_CYX>), dim3(grid), dim3(256), RASTER_LDS, s, descs, atlas, obs, n, only);
-    else
-        hipLaunchKernelGGL((raster_sparse_kernel<Composer, MG_OBS_U8_XYC>), dim3(grid), dim3(256), RASTER_LDS, s, descs, atlas, obs, n, only);
+    const dim3 grid(std::min((n + SPARSE_CHUNK - 1) / SPARSE_CHUNK, 8192));
+    with_obs_format(fmt, [&](auto F) { launch(raster_sparse_kernel<Composer, decltype(F)::value>, grid, dim3(256), RASTER_LDS, s, descs, atlas, obs, n, only); });
 }
 
 }  // namespace v1

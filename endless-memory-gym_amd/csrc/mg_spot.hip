@@ -23,6 +23,7 @@
 #include "mg_lab.hpp"
 #include "mg_device.hpp"
 #include "mg_family.hpp"
+#include "mg_option_sets.hpp"
 #include "mg_raster.hpp"
 #include "mg_stamps.hpp"
 
@@ -1536,7 +1537,7 @@ static __attribute__((noinline)) double cos_only(double x) { volatile double v =
 
 class SpotFamily : public Family {
    public:
-    SpotFamily(int endless, int n) : opt_(one_set()), P_(opt_[0]->P), n_(n) {
+    SpotFamily(int endless, int n) : Family(n), P_(sets_[0].P) {
         memset(&P_, 0, sizeof(P_));
         P_.endless = endless;
         P_.n = n;
@@ -1551,7 +1552,7 @@ class SpotFamily : public Family {
         } else {
             P_.max_steps = 256; P_.initial_spawns = 4; P_.num_spawns = 30;
             initial_spawn_interval_ = 30; spawn_interval_threshold_ = 10;
-            opt_[0]->st_num_coins.set(P_.num_coins, {1}); P_.agent_health = 5; P_.r_exit = 1.0; P_.use_exit = 1;
+            sets_[0].st_num_coins.set(P_.num_coins, {1}); P_.agent_health = 5; P_.r_exit = 1.0; P_.use_exit = 1;
         }
         core_.alloc(n);
         for (auto* a : {&sp_t_, &sp_speed_}) a->alloc((size_t)SLOTS * n);
@@ -1591,11 +1592,11 @@ class SpotFamily : public Family {
             jump_.upload(jt);
         }
         sin_.upload(st);
-        sets_dev_.alloc(MG_MAX_OPTION_SETS);
-        hipLaunchKernelGGL(spot_init_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, n, core_.p);
+        sets_.alloc();
+        launch(spot_init_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, n, core_.p);
         MG_HIP(hipDeviceSynchronize());
         rebuild();
-        defaults_ = P_;  // (short lists only: no device arrays behind them)
+        sets_.defaults = P_;
     }
 
     int action_dim() const override { return 2; }
@@ -1612,14 +1613,7 @@ class SpotFamily : public Family {
     // option is accepted there when it says what the handle's geometry already is.
     void set_option(const std::string& key, const double* v, int n) override { set_option_set(0, key, v, n); }
     void set_option_set(int set, const std::string& key, const double* v, int n) override {
-        if (set < 0 || set >= MG_MAX_OPTION_SETS) throw OptionError{-3, "option set index out of range"};
-        while ((int)opt_.size() <= set) {  // a new set starts from the constructor's defaults (= the reference's), geometry from set 0
-            opt_.emplace_back(new SpotOpt());
-            opt_.back()->P = defaults_;
-            copy_geometry(opt_.back()->P, P_);
-            derive(*opt_.back());
-        }
-        SpotOpt& O = *opt_[set];
+        SpotOpt& O = sets_.ensure(set, derive);
         SpotParams& P = O.P;
         const bool e = P_.endless;
         // handle-wide values (members of the family) that fix geometry: `member = value` in set 0, "must already be so" elsewhere
@@ -1632,7 +1626,6 @@ class SpotFamily : public Family {
             G(m, (double)value);
             member = (int)m;
         };
-        sets_dirty_ = true;
         auto I = [&](int& dst) { dst = to_int_checked(v[0], key.c_str()); };
         auto B = [&](int& dst) { dst = v[0] != 0.0; };
         auto must_be = [&](bool ok) { if (!ok) throw OptionError{-3, "reset parameter " + key + ": this value is not supported by the MI355X build"}; };
@@ -1701,16 +1694,15 @@ class SpotFamily : public Family {
         else if (!e && key == "reward_max_steps") {}
         else throw OptionError{-2, "unknown reset parameter " + key};
     }
-    // instance i runs under option set set_of_dev[i] (device array [num_envs], caller-owned; NULL: every instance under set 0)
-    void bind_option_sets(const int32_t* set_of_dev) override { set_of_ = set_of_dev; }
+    void bind_option_sets(const int32_t* set_of_dev) override { sets_.bind(set_of_dev); }
 
     void reset(const int64_t* seeds, const uint8_t* mask, void* obs, float* gt, hipStream_t s) override {
         if (dirty_) rebuild();
-        if (!seeds && !seeded_) throw std::runtime_error("reset(seed=None) before any seeded reset");
-        for (auto& O : opt_) {   // 16 spotlight slots per instance.  Refuse option sets that overflow them in ANY episode that lasts as long
+        require_seeded(seeds);
+        for (size_t k = 0; k < sets_.size(); ++k) {   // 16 spotlight slots per instance.  Refuse option sets that overflow them in ANY episode that lasts as long
             // as the fastest spotlight lives (t reaches 1 after ceil(1 / speed) steps, the slot is freed one step later);
             // rarer overflows raise error bit 1, which mg_peek_errors shows without a synchronisation.
-            const SpotParams& Q = O->P;
+            const SpotParams& Q = sets_[k].P;
             if (Q.r_hi <= Q.r_lo) throw OptionError{-3, "spot radius range not supported"};
             const int life_min = (int)std::ceil(1.0 / Q.speed_hi) + 1;
             const int interval = P_.endless ? Q.spawn_interval : P_.interval0;
@@ -1722,69 +1714,63 @@ class SpotFamily : public Family {
                                          " per instance (raise spawn_interval / spot_max_speed or lower initial_spawns)");
         }
         if (seeds) seeded_ = true;
-        upload_sets(s);
+        sets_.upload(s);
         const dim3 rg((n_ * SLOTS + 255) / 256);
-        if (P_.endless) {
-            if (per_set()) hipLaunchKernelGGL((spot_reset_kernel<true, true>), rg, dim3(256), 0, s, P_, io(), seeds, mask, gt);
-            else hipLaunchKernelGGL((spot_reset_kernel<true, false>), rg, dim3(256), 0, s, P_, io(), seeds, mask, gt);
-        } else {
-            if (per_set()) hipLaunchKernelGGL((spot_reset_kernel<false, true>), rg, dim3(256), 0, s, P_, io(), seeds, mask, gt);
-            else hipLaunchKernelGGL((spot_reset_kernel<false, false>), rg, dim3(256), 0, s, P_, io(), seeds, mask, gt);
-        }
+        with_bool(P_.endless, [&](auto EN) {
+            with_bool(sets_.per_set(), [&](auto PS) {
+                launch(spot_reset_kernel<decltype(EN)::value, decltype(PS)::value>, rg, dim3(256), 0, s, P_, io(), seeds, mask, gt);
+            });
+        });
         if (mask && sparse_masked_raster()) {  // few frames of many: by the mask, not by a walk over every descriptor (mg_raster.hpp)
             if (P_.ordered_holes) launch_raster_sparse<SpotBorderComposer>(desc_.p, atlas_->dev(), obs, obs_format, n_, s, mask);
             else launch_raster_sparse<SpotComposer>(desc_.p, atlas_->dev(), obs, obs_format, n_, s, mask);
-            MG_HIP(hipGetLastError());
+            check_launch();
         } else raster(obs, s);
     }
 
     void step(const int32_t* actions, void* obs, float* reward, uint8_t* done, float* gt, const mg_info_buffers* info,
               int autoreset, hipStream_t s) override {
-        if (dirty_) throw std::runtime_error("options that change geometry need a reset before the next step");
-        mg_info_buffers ib;
-        memset(&ib, 0, sizeof(ib));
-        if (info) ib = *info;
-        upload_sets(s);
+        const mg_info_buffers ib = begin_step(info);
+        sets_.upload(s);
         prof.begin(0, s);
         // (resets served inside the raster launch: handles with ONE option set -- the service code takes its parameters from the launch's arguments)
         // (a call that keeps terminal observations: always deferred -- the service workgroup draws the terminal frame from the descriptor this
         // launch leaves, then resets: keeps_final_obs)
         const bool keep_final = autoreset && ib.final_obs_dev && keeps_final_obs(s);
-        const int defer = (autoreset && obs_format == MG_OBS_U8_XYC && (fuse_resets() || keep_final) && !per_set()) ? 1 : 0;
+        const int defer = (autoreset && obs_format == MG_OBS_U8_XYC && (fuse_resets() || keep_final) && !sets_.per_set()) ? 1 : 0;
         const int sb = step_block(256);
         const SpotStepArgs sa{P_, io(), actions, reward, done, gt, ib, autoreset, defer};
         const dim3 sg((n_ * SLOTS + sb - 1) / sb);
-        if (P_.endless) {
-            if (per_set()) hipLaunchKernelGGL((spot_step_kernel<true, true>), sg, dim3(sb), 0, s, sa);
-            else hipLaunchKernelGGL((spot_step_kernel<true, false>), sg, dim3(sb), 0, s, sa);
-        } else {
-            if (per_set()) hipLaunchKernelGGL((spot_step_kernel<false, true>), sg, dim3(sb), 0, s, sa);
-            else hipLaunchKernelGGL((spot_step_kernel<false, false>), sg, dim3(sb), 0, s, sa);
-        }
+        with_bool(P_.endless, [&](auto EN) {
+            with_bool(sets_.per_set(), [&](auto PS) { launch(spot_step_kernel<decltype(EN)::value, decltype(PS)::value>, sg, dim3(sb), 0, s, sa); });
+        });
         end_logic(s);
         prof.begin(1, s);
         if (defer) {
-            const int grid = (n_ < raster_grid(n_) ? n_ : raster_grid(n_)) + SPOT_SVC_WGS;
+            const int grid = frames_grid(n_) + SPOT_SVC_WGS;
             const int forced_batch = lab_int("MEMGYM_SPOT_SVC_BATCH", 0);  // (lab build: exactly this many)
             const bool fb = forced_batch >= 1 && forced_batch <= SPOT_SVC_BATCH;
             const SpotServeArgs va{desc_.p, atlas_->dev(), obs, n_, P_, io(), gt, fb ? forced_batch : (n_ <= 12288 ? 1 : SPOT_SVC_BATCH), fb ? forced_batch : SPOT_SVC_BATCH,
                                    keep_final ? ib.final_obs_dev : nullptr};
             const bool nt = fused_nt();                // non-temporal: with plain stores the fused launch loses 5-15 us at every occupancy
             const int serve_lds = RASTER_LDS_REQUEST;  // 25 KiB: six per CU
-#define SPOT_FUSED2(EN, BO, NT) do { if (keep_final) hipLaunchKernelGGL((spot_raster_serve_kernel<EN, BO, NT, true>), dim3(grid), dim3(256), serve_lds, s, va); \
-                                     else hipLaunchKernelGGL((spot_raster_serve_kernel<EN, BO, NT>), dim3(grid), dim3(256), serve_lds, s, va); } while (0)
-#define SPOT_FUSED(EN, BO) do { if (nt) SPOT_FUSED2(EN, BO, true); else SPOT_FUSED2(EN, BO, false); } while (0)
-            if (P_.endless) { if (P_.ordered_holes) SPOT_FUSED(true, true); else SPOT_FUSED(true, false); }
-            else { if (P_.ordered_holes) SPOT_FUSED(false, true); else SPOT_FUSED(false, false); }
-#undef SPOT_FUSED
-#undef SPOT_FUSED2
-            MG_HIP(hipGetLastError());
+            // (endless x border x non-temporal x kept terminal observations: all sixteen forms are launched)
+            with_bool(P_.endless, [&](auto EN) {
+                with_bool(P_.ordered_holes, [&](auto BO) {
+                    with_bool(nt, [&](auto NT) {
+                        with_bool(keep_final, [&](auto FINAL) {
+                            launch_checked(spot_raster_serve_kernel<decltype(EN)::value, decltype(BO)::value, decltype(NT)::value, decltype(FINAL)::value>,
+                                           dim3(grid), dim3(256), serve_lds, s, va);
+                        });
+                    });
+                });
+            });
         } else {
             raster(obs, s);
         }
         prof.end(1, s);
 #ifdef MG_LAB
-        if (lab_int("MEMGYM_SPOT_WARM", 0)) hipLaunchKernelGGL(spot_warm_kernel, sg, dim3(sb), 0, s, n_, io());
+        if (lab_flag("MEMGYM_SPOT_WARM", false)) launch(spot_warm_kernel, sg, dim3(sb), 0, s, n_, io());
 #endif
     }
 
@@ -1797,18 +1783,11 @@ class SpotFamily : public Family {
         rng_.blobs(v);
         return v;
     }
-    void debug_rng(int i, uint64_t out[6]) override { rng_.debug(i, out); }
     void ground_truth64(double* out, hipStream_t s) override {
         if (!gt_dim() || !out) return;
-        upload_sets(s);
-        hipLaunchKernelGGL(spot_gt64_kernel, dim3((n_ + 255) / 256), dim3(256), 0, s, P_, io(), out);
-        MG_HIP(hipGetLastError());
+        sets_.upload(s);
+        launch_checked(spot_gt64_kernel, dim3((n_ + 255) / 256), dim3(256), 0, s, P_, io(), out);
     }
-    int poll_errors() override {
-        MG_HIP(hipDeviceSynchronize());
-        return err_.take();
-    }
-    int peek_errors() override { return err_.peek(); }
 
    private:
     SpotIO io() {
@@ -1821,8 +1800,8 @@ class SpotFamily : public Family {
         o.err = err_.dev;
         o.queue = queue_.p + SQ_WORDS;
         o.qctr = queue_.p;
-        o.sets = per_set() ? sets_dev_.p : nullptr;
-        o.set_of = per_set() ? set_of_ : nullptr;
+        o.sets = sets_.dev();
+        o.set_of = sets_.set_of();
         return o;
     }
 
@@ -1837,9 +1816,9 @@ class SpotFamily : public Family {
         double inv = 1.0 / std::sqrt(2.0);
         P_.v_axis_i = (int)((1.0 / 1.0) * agent_speed_);
         P_.v_diag_i = (int)(inv * agent_speed_);
-        for (auto& O : opt_) {
-            derive(*O);
-            if (O->P.r_hi <= O->P.r_lo) throw OptionError{-3, "spot radius range not supported"};
+        for (size_t k = 0; k < sets_.size(); ++k) {
+            derive(sets_[k]);
+            if (sets_[k].P.r_hi <= sets_[k].P.r_lo) throw OptionError{-3, "spot radius range not supported"};
         }
         P_.coin_radius = (int)(10 * coin_scale_);
         P_.spawn_clamp = (int)(30 * SCALE);
@@ -1883,15 +1862,13 @@ class SpotFamily : public Family {
         atlas_->set_templates(build_chessboards(SCALE, SCREEN));
         atlas_->upload();
         dirty_ = false;
-        for (size_t k = 1; k < opt_.size(); ++k) copy_geometry(opt_[k]->P, P_);
-        copy_geometry(defaults_, P_);
+        sets_.refresh_geometry();
         {   // (the defaults' own radius / dim values, whatever set 0 holds by now)
             SpotOpt D;
-            D.P = defaults_;
+            D.P = sets_.defaults;
             derive(D);
-            defaults_ = D.P;
+            sets_.defaults = D.P;
         }
-        sets_dirty_ = true;
     }
 
     // The generation new exits belong to = the slot that holds exit_scale_; a new scale takes a free slot.  Slots are only ever
@@ -1923,12 +1900,20 @@ class SpotFamily : public Family {
             throw OptionError{-3, "exits of eight different exit_scale values are still on screen (use_exit = False keeps them); a ninth size needs a reset with use_exit = True first"};
     }
 
-    // per-instance option sets
+    // one option set: the parameter block, the list and the raw values behind it
     struct SpotOpt {
         SpotParams P;
         OptListStore st_num_coins;
         double min_radius = 30.0 * 0.25, max_radius = 55.0 * 0.25;  // spot_min_radius / spot_max_radius (defaults x SCALE)
         int dim_duration = 6;                                      // light_dim_off_duration
+        // what the shared atlases, tables and derived constants fix for every set of the handle
+        static void copy_geometry(SpotParams& d, const SpotParams& s) {
+            d.endless = s.endless; d.n = s.n; d.ordered_holes = s.ordered_holes;
+            d.show_last_action = s.show_last_action; d.agent_radius = s.agent_radius; d.sprite_half = s.sprite_half;
+            d.coin_radius = s.coin_radius; d.v_axis_i = s.v_axis_i; d.v_diag_i = s.v_diag_i; d.spawn_clamp = s.spawn_clamp; d.bar_x = s.bar_x;
+            d.bar_w = s.bar_w; d.quarter = s.quarter; d.bar_h = s.bar_h; d.exit_gen = s.exit_gen; d.exit_halves = s.exit_halves; d.half_diag = s.half_diag;
+            d.exit_radius = s.exit_radius; d.interval0 = s.interval0; d.cos_tab = s.cos_tab; d.sin_tab = s.sin_tab; d.jump = s.jump; d.lab_fallback = s.lab_fallback;
+        }
     };
     // what a set's radius and dim options mean for the kernels (pure logic: the disc span table covers every radius up to DISC_RMAX)
     static void derive(SpotOpt& O) {
@@ -1941,45 +1926,18 @@ class SpotFamily : public Family {
         O.P.dim_duration = O.dim_duration;
         O.P.dim_step = O.dim_duration > 0 ? (int)(255.0 / O.dim_duration) : 0;
     }
-    static std::vector<std::unique_ptr<SpotOpt>> one_set() {
-        std::vector<std::unique_ptr<SpotOpt>> v;
-        v.emplace_back(new SpotOpt());
-        return v;
-    }
-    // what the shared atlases, tables and derived constants fix for every set of the handle
-    static void copy_geometry(SpotParams& d, const SpotParams& s) {
-        d.endless = s.endless; d.n = s.n; d.ordered_holes = s.ordered_holes;
-        d.show_last_action = s.show_last_action; d.agent_radius = s.agent_radius; d.sprite_half = s.sprite_half;
-        d.coin_radius = s.coin_radius; d.v_axis_i = s.v_axis_i; d.v_diag_i = s.v_diag_i; d.spawn_clamp = s.spawn_clamp; d.bar_x = s.bar_x;
-        d.bar_w = s.bar_w; d.quarter = s.quarter; d.bar_h = s.bar_h; d.exit_gen = s.exit_gen; d.exit_halves = s.exit_halves; d.half_diag = s.half_diag;
-        d.exit_radius = s.exit_radius; d.interval0 = s.interval0; d.cos_tab = s.cos_tab; d.sin_tab = s.sin_tab; d.jump = s.jump; d.lab_fallback = s.lab_fallback;
-    }
-    bool per_set() const { return set_of_ != nullptr && opt_.size() > 1; }
-    void upload_sets(hipStream_t s) {
-        if (!per_set() || !sets_dirty_) return;
-        SpotParams fresh = defaults_;  // a set that was never written: the reference's defaults under the handle's geometry (include/memgym.h)
-        copy_geometry(fresh, P_);
-        std::vector<SpotParams> host(MG_MAX_OPTION_SETS, fresh);
-        for (size_t k = 0; k < opt_.size(); ++k) {
-            copy_geometry(opt_[k]->P, P_);  // (ordered_holes may have been switched on since the last rebuild)
-            host[k] = opt_[k]->P;
-        }
-        MG_HIP(hipMemcpyAsync(sets_dev_.p, host.data(), sizeof(SpotParams) * host.size(), hipMemcpyHostToDevice, s));
-        MG_HIP(hipStreamSynchronize(s));  // (rare: only after an option of some set changed)
-        sets_dirty_ = false;
-    }
 
     void raster_only(void* obs, const uint8_t* only, hipStream_t s) override {
         if (P_.ordered_holes) launch_raster<SpotBorderComposer>(desc_.p, atlas_->dev(), obs, obs_format, n_, s, only);
         else launch_raster<SpotComposer>(desc_.p, atlas_->dev(), obs, obs_format, n_, s, only);
-        MG_HIP(hipGetLastError());
+        check_launch();
     }
 
     void raster(void* obs, hipStream_t s) { raster_only(obs, nullptr, s); }
     // (the fused raster / reset launch keeps terminal observations itself; lab MEMGYM_SPOT_FINAL_FUSED=0: the generic path of mg_step)
     bool keeps_final_obs(hipStream_t) override {
-        static const bool wanted = lab_int("MEMGYM_SPOT_FINAL_FUSED", 1) != 0;
-        return wanted && obs_format == MG_OBS_U8_XYC && !per_set();
+        static const bool wanted = lab_flag("MEMGYM_SPOT_FINAL_FUSED", true);
+        return wanted && obs_format == MG_OBS_U8_XYC && !sets_.per_set();
     }
 
     // Resets served inside the raster launch: on for the finite variant up to FUSE_MAX instances (more instances finish per step
@@ -1994,30 +1952,18 @@ class SpotFamily : public Family {
     // store flavour of the fused launch: it runs five workgroups per CU (the reset code's registers), where only the
     // non-temporal stream keeps up; MEMGYM_RASTER_NT forces (tuning only)
     bool fused_nt() const {
-        static const int forced = [] {
-            const char* e = lab_env("MEMGYM_RASTER_NT");
-            return e ? (atoi(e) != 0 ? 1 : 0) : -1;
-        }();
+        static const int forced = lab_forced("MEMGYM_RASTER_NT");
         return forced >= 0 ? forced != 0 : true;
     }
     bool fuse_resets() const {
-        static const int forced = [] {
-            const char* e = lab_env("MEMGYM_SPOT_FUSE");
-            return e ? (atoi(e) != 0 ? 1 : 0) : -1;
-        }();
+        static const int forced = lab_forced("MEMGYM_SPOT_FUSE");
         return forced >= 0 ? forced != 0 : (P_.endless ? n_ > RASTER_PLAIN_MAX : n_ <= FUSE_MAX);
     }
 
-    std::vector<std::unique_ptr<SpotOpt>> opt_;  // [0] = the handle-wide set (P_ below is its parameter block)
-    SpotParams& P_;
-    SpotParams defaults_;
-    const int32_t* set_of_ = nullptr;
-    bool sets_dirty_ = true;
-    DevArray<SpotParams> sets_dev_;
-    int n_;
+    OptionSets<SpotOpt> sets_;
+    SpotParams& P_;  // set 0, the handle-wide set
     double coin_scale_, agent_speed_, agent_scale_, exit_scale_;
     double initial_spawn_interval_ = 30, spawn_interval_threshold_ = 10;
-    bool dirty_ = true, seeded_ = false;
 
    public:
     void on_state_loaded() override {
@@ -2034,7 +1980,7 @@ class SpotFamily : public Family {
             }
             rebuild();
         }
-        sets_dirty_ = true;
+        sets_.touch();
     }
     void raster_debug(void* frames, hipStream_t s) override;
 
@@ -2054,19 +2000,15 @@ class SpotFamily : public Family {
     bool exit_gen_used_[EXIT_GENS] = {false, false, false, false, false, false, false, false};
     DevArray<uint32_t> coins_;
     DevArray<SpotDesc> desc_;
-    ErrorWord err_;
-    RngStore rng_;
 };
 
 void SpotFamily::raster_debug(void* frames, hipStream_t s) {
-    if (dirty_) throw std::runtime_error("options that change geometry need a reset before the next render");
-    DevArray<SpotDesc> dbg;
-    dbg.alloc(n_, false);
-    hipLaunchKernelGGL(spot_debug_desc_kernel, dim3((n_ + 255) / 256), dim3(256), 0, s, P_, io(), dbg.p);
-    if (P_.ordered_holes) launch_raster<SpotBorderDebugComposer>(dbg.p, atlas_->dev(), frames, MG_OBS_U8_XYC, n_, s);
-    else launch_raster<SpotDebugComposer>(dbg.p, atlas_->dev(), frames, MG_OBS_U8_XYC, n_, s);
-    MG_HIP(hipGetLastError());
-    MG_HIP(hipStreamSynchronize(s));  // dbg is released on return
+    debug_frames<SpotDesc>(
+        s, [&](SpotDesc* dbg) { launch(spot_debug_desc_kernel, dim3((n_ + 255) / 256), dim3(256), 0, s, P_, io(), dbg); },
+        [&](SpotDesc* dbg) {
+            if (P_.ordered_holes) launch_raster<SpotBorderDebugComposer>(dbg, atlas_->dev(), frames, MG_OBS_U8_XYC, n_, s);
+            else launch_raster<SpotDebugComposer>(dbg, atlas_->dev(), frames, MG_OBS_U8_XYC, n_, s);
+        });
 }
 
 Family* make_spot(int endless, int num_envs) { return new SpotFamily(endless, num_envs); }
