@@ -35,6 +35,7 @@ struct mg_env {
         size_t o_action = 0, o_seed = 0, o_obs = 0, o_vec = 0, o_reward32 = 0, o_reward = 0, o_done = 0, o_gt32 = 0, o_gt = 0, o_ep_reward = 0,
                o_ep_length = 0, o_aux = 0, o_flag = 0;
         uint32_t ticket = 0;      // completion flag protocol of mg_single_step (see there)
+        bool use_flag = true;     // single_wait: false once this runtime has refused a stream memory operation
     } single;
 };
 
@@ -373,12 +374,11 @@ namespace {
 // with them their stores into the same pinned block), and the host polls that word.  hipStreamSynchronize on this runtime costs
 // more than the step's kernels once the work is this small.  A wait that takes longer than 50 ms (a fault, a debugger) falls back to the
 // synchronising call, which also reports the stream's error; a runtime without stream memory operations synchronises as before.
-void single_wait(mg_env::Single& S, hipStream_t st, bool armed = false) {
-    static bool use_flag = true;
-    if (use_flag) {
-        // armed: the step's own last kernel stores the ticket (Family::arm_done_flag; S.ticket was advanced when it was armed)
-        const uint32_t want = armed ? S.ticket : ++S.ticket;
-        if (armed || hipStreamWriteValue32(st, S.dev + S.o_flag, want, 0) == hipSuccess) {
+void single_wait(mg_env::Single& S, hipStream_t st, bool stored = false) {
+    if (S.use_flag) {
+        // stored: the step's own last kernel stores the ticket (Family::done_flag_stored; S.ticket was advanced when it said so)
+        const uint32_t want = stored ? S.ticket : ++S.ticket;
+        if (stored || hipStreamWriteValue32(st, S.dev + S.o_flag, want, 0) == hipSuccess) {
             volatile uint32_t* flag = (volatile uint32_t*)(S.host + S.o_flag);
             const auto t0 = std::chrono::steady_clock::now();
             for (uint32_t spins = 0;; ++spins) {
@@ -388,7 +388,7 @@ void single_wait(mg_env::Single& S, hipStream_t st, bool armed = false) {
             }
         } else {
             (void)hipGetLastError();
-            use_flag = false;
+            S.use_flag = false;
         }
     }
     MG_HIP(hipStreamSynchronize(st));
@@ -462,12 +462,13 @@ int mg_single_step(mg_env* env, int32_t a0, int32_t a1, void* stream) {
         for (int k = 0; k < MG_INFO_SLOTS; ++k) ib.aux_dev[k] = (float*)(S.dev + S.o_aux + 256 * k);
         ib.reward64_dev = (double*)(S.dev + S.o_reward);
         mg::Family* f = env->fam;
-        const bool armed = f->arm_done_flag((uint32_t*)(S.dev + S.o_flag), S.ticket + 1);
-        if (armed) ++S.ticket;
+        f->want_done_flag((uint32_t*)(S.dev + S.o_flag), S.ticket + 1);
         f->step((const int32_t*)(S.dev + S.o_action), S.dev + S.o_obs, (float*)(S.dev + S.o_reward32), (uint8_t*)(S.dev + S.o_done),
                 f->gt_dim() ? (float*)(S.dev + S.o_gt32) : nullptr, &ib, 0, st);
+        const bool stored = f->done_flag_stored();  // the step's own last kernel stores the ticket: nothing may follow it (gt_dim() is 0 then)
+        if (stored) ++S.ticket;
         f->ground_truth64((double*)(S.dev + S.o_gt), st);
-        single_wait(S, st, armed);
+        single_wait(S, st, stored);
         flags = f->peek_errors();  // (the word lives in pinned host memory: a plain read; saves the caller a second native call per step)
     });
     return rc != 0 ? rc : flags;

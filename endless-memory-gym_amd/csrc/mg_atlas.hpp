@@ -8,23 +8,9 @@
 
 namespace mg {
 
-class Atlas {
+class Atlas : public AtlasStore<AtlasTables, RasterAtlas> {
    public:
-    Atlas() {
-        memset(&tables_, 0, sizeof(tables_));
-        static const uint8_t RGB[][3] = {
-            {0, 0, 0},       {250, 204, 153}, {250, 250, 250}, {50, 50, 50},  {255, 255, 255}, {255, 0, 0},   {0, 255, 0},
-            {0, 0, 255},     {255, 255, 0},   {255, 165, 0},   {50, 50, 50},  {120, 120, 120}, {116, 1, 113}, {255, 94, 14},
-            {210, 210, 210}, {0, 0, 0},       {48, 141, 70},   {55, 55, 55},  {125, 177, 250}};
-        for (int i = 0; i < (int)(sizeof(RGB) / 3); ++i) {
-            tables_.palette[i] = (uint32_t)RGB[i][0] | ((uint32_t)RGB[i][1] << 8) | ((uint32_t)RGB[i][2] << 16);
-            tables_.border_of[i] = (uint32_t)i;
-        }
-        tables_.border_of[C_WHITE] = C_GREY210;
-        tables_.border_of[C_ICY] = C_GREY210;
-    }
-
-    // stamp pixels are palette ids (0 = transparent); stored column-major [x][y] as RGBA words with the column
+    // stamp pixels are stored column-major [x][y] as RGBA words with the column
     // stride padded to a power of two (pixel index p -> x = p >> sh, y = p & (stride - 1): no division in the kernel)
     // max_px: what the composer that draws this stamp can hold in registers (256 pixels per StampRegs slot); a scale
     // option that needs more is refused instead of being drawn truncated
@@ -45,16 +31,8 @@ class Atlas {
             for (int y = 0; y < (1 << sh); ++y) data_.push_back(y < s.h ? rgba(s.get(x, y)) : 0u);
         return id;
     }
-    // palette id -> r | g<<8 | b<<16 | 0xFF<<24 (opaque); id 0 is the colour key -> 0 (transparent)
-    uint32_t rgba(uint8_t id) const { return id ? (tables_.palette[id] | 0xFF000000u) : 0u; }
-    int n_stamps() const { return n_stamps_; }
-    void set_templates(const std::vector<uint8_t>& t) { templates_ = t; }
-
     void upload() {
-        if (data_.empty()) data_.push_back(0);
-        if (templates_.empty()) templates_.resize(16, 0);
-        stamp_dev_.upload(data_);
-        templ_dev_.upload(templates_);
+        upload_shared();
         // disc column spans for r = 0..DISC_RMAX
         std::vector<int8_t> span((size_t)(DISC_RMAX + 1) * 2 * DISC_RMAX * 2, 0);
         for (int r = 0; r <= DISC_RMAX; ++r) {
@@ -79,25 +57,11 @@ class Atlas {
             }
         }
         span_dev_.upload(span);
-        std::vector<AtlasTables> t(1, tables_);
-        tables_dev_.upload(t);
-        dev_.templates = templ_dev_.p;
-        dev_.stamp_data = stamp_dev_.p;
         dev_.disc_span = span_dev_.p;
-        dev_.tables = tables_dev_.p;
     }
-    const RasterAtlas& dev() const { return dev_; }
 
    private:
-    AtlasTables tables_;
-    int n_stamps_ = 0;
-    std::vector<uint32_t> data_;
-    std::vector<uint8_t> templates_;
-    DevArray<uint32_t> stamp_dev_;
-    DevArray<uint8_t> templ_dev_;
     DevArray<int8_t> span_dev_;
-    DevArray<AtlasTables> tables_dev_;
-    RasterAtlas dev_;
 };
 
 }  // namespace mg

@@ -195,9 +195,12 @@ class Family {
     virtual ~Family() {}
     virtual int action_dim() const = 0;
     virtual int gt_dim() const = 0;
-    // mg_single_step (mg_api.hip): can the family's next step() store `ticket` to *flag_dev itself when its results are out?  false: the
-    // caller waits through a stream memory operation behind the step's launches
-    virtual bool arm_done_flag(uint32_t* /*flag_dev*/, uint32_t /*ticket*/) { return false; }
+    // mg_single_step (mg_api.hip) asks the NEXT step() -- that call only, however it ends -- to store `ticket` to *flag_dev (a word the
+    // host polls) from its own last kernel once its results are out.  Whether that happened is decided where step() chooses its launch:
+    // done_flag_stored() is true iff the step() that just returned launched such a kernel (reading it clears it); otherwise the caller
+    // puts a stream memory operation behind the step's launches.  A family without such a kernel ignores the request.
+    virtual void want_done_flag(uint32_t* /*flag_dev*/, uint32_t /*ticket*/) {}
+    virtual bool done_flag_stored() { return false; }
     // capacities of the per-instance lists the reference grows without limit (include/memgym.h: mg_set_capacity / mg_capacity)
     virtual void set_capacity(const std::string& what, int64_t) { throw OptionError{-2, "this env id has no capacity named " + what}; }
     virtual int64_t capacity(const std::string& what) const { throw OptionError{-2, "this env id has no capacity named " + what}; }
@@ -260,6 +263,15 @@ class Family {
         if (info) ib = *info;
         return ib;
     }
+    // tail of every reset(): the frames of the instances that were reset.  With a mask few of many: `sparse(mask)` draws them by the
+    // mask (launch_raster_sparse), not by a walk over every descriptor; otherwise `dense()`, the family's raster launch
+    template <class Sparse, class Dense>
+    void reset_frames(const uint8_t* mask, Sparse sparse, Dense dense) {
+        if (mask && sparse_masked_raster()) {
+            sparse(mask);
+            check_launch();
+        } else dense();
+    }
     // raster_debug(): `fill(dbg)` writes the debug view's descriptors of all instances into scratch, `raster(dbg)` draws them
     template <typename Desc, typename Fill, typename Raster>
     void debug_frames(hipStream_t s, Fill fill, Raster raster) {
@@ -295,5 +307,43 @@ inline int to_int_checked(double v, const char* key) {
     if ((double)i != v) throw OptionError{-3, std::string("option ") + key + " must be integral"};
     return i;
 }
+
+// One key of the reset options as a family's set_option_set() reads it: `n` values at `v` for option set `set` (0 = the handle-wide
+// set of mg_set_option), and what the families do with one.  Codes and messages are mapped by the Python package (vec_env.py: _write_set).
+struct OptionArg {
+    int set;
+    const std::string& key;
+    const double* v;
+    int n;
+    bool& dirty;  // the family's "a geometry option changed" guard
+    int integer(int k = 0) const { return to_int_checked(v[k], key.c_str()); }
+    bool flag() const { return v[0] != 0.0; }
+    // a value the reference accepts and this build does not
+    void must_be(bool ok) const {
+        if (!ok) throw OptionError{-3, "reset parameter " + key + ": this value is not supported by the MI355X build"};
+    }
+    // a handle-wide value (a member of the family) that fixes geometry -- atlases, tables and derived constants are shared by the
+    // handle's instances: assigned in set 0, which then needs a rebuild whether or not the value changed; a set > 0 is accepted
+    // when it says what the handle's geometry already is
+    template <typename T>
+    void geometry(T& member, T value) const {
+        if (set == 0) {
+            member = value;
+            dirty = true;
+        } else if (member != value)
+            throw OptionError{-3, "reset parameter " + key + " changes the geometry shared by the handle's instances: it can only be set for all of them (option set 0)"};
+    }
+    // a "sample one per episode" list of any length (np_random.choice, e.g. mortar_mayhem_grid.py:181,253-254,268-269)
+    std::vector<int> int_list(int lo, int hi) const {
+        if (n < 1) throw OptionError{-3, "option " + key + ": an empty list cannot be sampled"};
+        std::vector<int> vals(n);
+        for (int i = 0; i < n; ++i) {
+            vals[i] = integer(i);
+            if (vals[i] < lo || vals[i] > hi)
+                throw OptionError{-3, "option " + key + ": value out of the supported range " + std::to_string(lo) + ".." + std::to_string(hi)};
+        }
+        return vals;
+    }
+};
 
 }  // namespace mg

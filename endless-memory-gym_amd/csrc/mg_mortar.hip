@@ -835,15 +835,15 @@ class MortarFamily : public Family {
         if (P_.variant == V_ENDLESS && what == "commands") return P_.cmd_cap;
         return Family::capacity(what);
     }
-    // mg_single_step: the NEXT step's last kernel stores `ticket` to *flag (a word the host polls) once its results are out.  Only the
-    // one-launch step of a one-instance handle without ground truth can promise that; everything else answers false and the caller puts a
-    // stream memory operation behind the step instead.
-    bool arm_done_flag(uint32_t* flag_dev, uint32_t ticket) override {
-        if (!(n_ == 1 && obs_format == MG_OBS_U8_XYC && fuse_step() && !sets_.per_set() && gt_dim() == 0 && !dirty_)) return false;
+    // mg_single_step: a request to the next step() alone, which grants it where it takes the one-launch form (see there)
+    void want_done_flag(uint32_t* flag_dev, uint32_t ticket) override {
         flag_dev_ = flag_dev;
         flag_ticket_ = ticket;
-        flag_armed_ = true;
-        return true;
+    }
+    bool done_flag_stored() override {
+        const bool stored = flag_stored_;
+        flag_stored_ = false;
+        return stored;
     }
     int action_dim() const override { return P_.variant == V_GRID ? 1 : 2; }
     int gt_dim() const override { return P_.variant == V_ENDLESS ? 2 : 0; }
@@ -861,56 +861,37 @@ class MortarFamily : public Family {
         MortarOpt& O = sets_.ensure(set);
         MortarParams& P = O.P;
         const bool endless = P_.variant == V_ENDLESS;
-        auto geometry = [&]() {
-            if (set != 0) throw OptionError{-3, "reset parameter " + key + " changes the geometry shared by the handle's instances: it can only be set for all of them (option set 0)"};
-        };
-        auto scalar_i = [&](int& dst) { dst = to_int_checked(v[0], key.c_str()); };
-        // "sample one per episode" lists of any length (np_random.choice, e.g. mortar_mayhem_grid.py:181,253-254,268-269)
-        auto list = [&](OptList& l, OptListStore& st, int lo, int hi) {
-            if (n < 1) throw OptionError{-3, "option " + key + ": an empty list cannot be sampled"};
-            std::vector<int> vals(n);
-            for (int i = 0; i < n; ++i) {
-                vals[i] = to_int_checked(v[i], key.c_str());
-                if (vals[i] < lo || vals[i] > hi)
-                    throw OptionError{-3, "option " + key + ": value out of the supported range " + std::to_string(lo) + ".." + std::to_string(hi)};
-            }
-            st.set(l, vals);
-        };
-        // (a geometry option in a set > 0 is accepted when it says what the handle's geometry already is)
-        if (key == "agent_scale") { if (set != 0) { if (v[0] != agent_scale_) geometry(); } else { agent_scale_ = v[0]; dirty_ = true; } }
+        const OptionArg A{set, key, v, n, dirty_};
+        if (key == "agent_scale") A.geometry(agent_scale_, v[0]);
         else if (key == "allowed_commands") {
-            int a = to_int_checked(v[0], key.c_str());
+            int a = A.integer();
             if (a < 4 || a > 9) throw OptionError{-4, "assert 4 <= allowed_commands <= 9"};
             P.allowed = a;
         }
         // (entries are 16 bits in MortarState; an explosion entry of 0 is the reference's ZeroDivisionError in `% explosion_delay` (:304,343),
         // a show duration of 0 with a delay of 0 its IndexError at the reset's pop(0) (:257))
-        else if (!P_.taskb && key == "command_show_duration") list(P.show_dur, O.st_show_dur, 1, 65535);
-        else if (!P_.taskb && key == "command_show_delay") list(P.show_delay, O.st_show_delay, 0, 65535);
-        else if (key == "explosion_duration") list(P.expl_dur, O.st_expl_dur, 1, 65535);
-        else if (key == "explosion_delay") list(P.expl_delay, O.st_expl_delay, 1, 65535);
-        else if (key == "visual_feedback") P.visual_feedback = v[0] != 0.0;
+        else if (!P_.taskb && key == "command_show_duration") O.st_show_dur.set(P.show_dur, A.int_list(1, 65535));
+        else if (!P_.taskb && key == "command_show_delay") O.st_show_delay.set(P.show_delay, A.int_list(0, 65535));
+        else if (key == "explosion_duration") O.st_expl_dur.set(P.expl_dur, A.int_list(1, 65535));
+        else if (key == "explosion_delay") O.st_expl_delay.set(P.expl_delay, A.int_list(1, 65535));
+        else if (key == "visual_feedback") P.visual_feedback = A.flag();
         else if (key == "reward_command_failure") P.r_fail = v[0];
         else if (key == "reward_command_success") P.r_succ = v[0];
-        else if (endless && key == "max_steps") scalar_i(P.max_steps);
+        else if (endless && key == "max_steps") P.max_steps = A.integer();
         else if (endless && key == "initial_command_count") {
-            int c = to_int_checked(v[0], key.c_str());
+            int c = A.integer();
             if (c < 1 || c > P_.cmd_cap / 2) throw OptionError{-3, "initial_command_count out of the supported range"};
             P.initial_count = c;
         }
         else if (endless && key == "reward_new_command_success") P.r_new = v[0];
         else if (!endless && key == "arena_size") {
-            int a = to_int_checked(v[0], key.c_str());
+            int a = A.integer();
             if (a < 2 || a > 6) throw OptionError{-4, "assert 2 <= arena_size <= 6"};
-            if (set != 0 && a != P_.N) geometry();
-            if (set == 0 && a != P_.N) {
-                P_.N = a;
-                dirty_ = true;
-            }
+            if (a != P_.N) A.geometry(P_.N, a);  // (the one geometry key that asks for a rebuild only when its value changes)
         }
-        else if (!endless && key == "command_count") list(P.command_count, O.st_command_count, 1, P_.taskb ? VEC_DIM / 9 : P_.cmd_cap);
+        else if (!endless && key == "command_count") O.st_command_count.set(P.command_count, A.int_list(1, P_.taskb ? VEC_DIM / 9 : P_.cmd_cap));
         else if (!endless && key == "reward_episode_success") P.r_ep_succ = v[0];
-        else if (P_.variant != V_GRID && key == "agent_speed") { if (set != 0) { if (v[0] != agent_speed_) geometry(); } else { agent_speed_ = v[0]; dirty_ = true; } }
+        else if (P_.variant != V_GRID && key == "agent_speed") A.geometry(agent_speed_, v[0]);
         else throw OptionError{-2, "unknown reset parameter " + key};
     }
     void bind_option_sets(const int32_t* set_of_dev) override { sets_.bind(set_of_dev); }
@@ -929,14 +910,17 @@ class MortarFamily : public Family {
         with_bool(sets_.per_set(), [&](auto PS) {
             launch(mortar_reset_kernel<decltype(PS)::value>, dim3((n_ + 255) / 256), dim3(256), 0, s, P_, n_, io(), seeds, mask, gt_dim() ? gt : nullptr);
         });
-        if (mask && sparse_masked_raster()) {  // few frames of many: by the mask, not by a walk over every descriptor (mg_raster_v1.hpp)
-            launch_raster_sparse<MortarComposer>(desc_.p, atlas_->dev(), obs, obs_format, n_, s, mask);
-            check_launch();
-        } else raster(obs, s);
+        reset_frames(mask, [&](const uint8_t* m) { launch_raster_sparse<MortarComposer>(desc_.p, atlas_->dev(), obs, obs_format, n_, s, m); },
+                     [&] { raster(obs, s); });
     }
 
     void step(const int32_t* actions, void* obs, float* reward, uint8_t* done, float* gt, const mg_info_buffers* info,
               int autoreset, hipStream_t s) override {
+        struct Consume {  // want_done_flag() holds for this call only, whichever way it ends
+            uint32_t*& flag;
+            ~Consume() { flag = nullptr; }
+        } consume{flag_dev_};
+        flag_stored_ = false;
         const mg_info_buffers ib = begin_step(info);
         sets_.upload(s);
         const MortarStepArgs sa{P_, n_, io(), actions, reward, done, gt_dim() ? gt : nullptr, ib, autoreset, nullptr};
@@ -948,15 +932,17 @@ class MortarFamily : public Family {
             const int frames = frames_grid(n_);
             // lab build, MEMGYM_LAB_LOGIC_LAST=1: the step workgroups at the END of the grid -- the dispatch order the design must survive
             static const bool logic_last = lab_flag("MEMGYM_LAB_LOGIC_LAST", false);
-            // (three of the four <FLAG, FINAL> forms exist: an armed done flag and kept terminal observations exclude each other, keeps_final_obs)
+            // The done flag (want_done_flag) is granted here: this launch is the step's last kernel, and with ONE instance and no ground
+            // truth (mg_single_step puts a ground_truth64 launch behind the step) nothing follows it.  (Three of the four <FLAG, FINAL>
+            // forms exist: the flag is asked for by single steps, which pass autoreset = 0, so it never meets kept terminal observations.)
+            const bool store_flag = flag_dev_ && n_ == 1 && gt_dim() == 0;
             auto one_launch = [&](auto kernel, const MortarStepArgs& a, uint32_t* flag, uint32_t flag_ticket) {
                 launch(kernel, dim3(logic_wgs + frames), dim3(256), RASTER_LDS, s, a, logic_wgs, logic_last ? frames : 0, epoch_, ticket_,
                                claims_.p, rescues_.p, atlas_->dev(), obs, flag, flag_ticket);
             };
             prof.begin(1, s);
-            if (flag_armed_ && n_ == 1) {
+            if (store_flag) {
                 one_launch(mortar_step_raster_kernel<true>, sa, flag_dev_, flag_ticket_);
-                flag_armed_ = false;
             } else if (ib.final_obs_dev && autoreset) {  // terminal observations kept by the launch itself (keeps_final_obs)
                 MortarStepArgs fa = sa;
                 fa.tdesc = tdesc_.p;
@@ -965,6 +951,7 @@ class MortarFamily : public Family {
                 one_launch(mortar_step_raster_kernel<false>, sa, nullptr, 0u);
             }
             check_launch();
+            flag_stored_ = store_flag;
             prof.end(1, s);
             return;
         }
@@ -1008,9 +995,9 @@ class MortarFamily : public Family {
     }
 
    private:
-    uint32_t* flag_dev_ = nullptr;  // arm_done_flag
+    uint32_t* flag_dev_ = nullptr;  // want_done_flag: non-null only between the request and the end of the step() that follows it
     uint32_t flag_ticket_ = 0;
-    bool flag_armed_ = false;
+    bool flag_stored_ = false;      // done_flag_stored
     uint32_t ticket_ = 0;  // one-launch step: number of the step, the value a slot's claim word takes when a wave claims it
     uint32_t epoch_ = 0;  // the one-launch step's descriptor epoch, 1 .. 255 (every step rewrites every descriptor, so the only stale
                           // values a frame workgroup can meet are the previous step's and the 0 of a reset / two-launch step)
@@ -1089,7 +1076,7 @@ class MortarFamily : public Family {
     // MEMGYM_MORTAR_FINAL_FUSED=0: the generic path of mg_step)
     bool keeps_final_obs(hipStream_t s) override {
         static const bool wanted = lab_flag("MEMGYM_MORTAR_FINAL_FUSED", true);
-        return wanted && obs_format == MG_OBS_U8_XYC && fuse_step() && !sets_.per_set() && !capturing(s) && !(flag_armed_ && n_ == 1);
+        return wanted && obs_format == MG_OBS_U8_XYC && fuse_step() && !sets_.per_set() && !capturing(s);
     }
 
     void raster(void* obs, hipStream_t s) { raster_only(obs, nullptr, s); }

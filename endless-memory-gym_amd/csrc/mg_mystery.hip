@@ -2441,43 +2441,31 @@ class MysteryFamily : public Family {
         MysteryOpt& O = sets_.ensure(set);
         MysteryParams& P = O.P;
         const bool e = P_.endless;
-        auto I = [&](int& dst) { dst = to_int_checked(v[0], key.c_str()); };
-        auto B = [&](int& dst) { dst = v[0] != 0.0; };
-        auto must_be = [&](bool ok) { if (!ok) throw OptionError{-3, "reset parameter " + key + ": this value is not supported by the MI355X build"}; };
-        // (a geometry option in a set > 0 is accepted when it says what the handle's geometry already is)
-        auto geometry = [&](double& mine) {
-            if (set != 0) {
-                if (v[0] != mine)
-                    throw OptionError{-3, "reset parameter " + key + " changes the geometry shared by the handle's instances: it can only be set for all of them (option set 0)"};
-            } else {
-                mine = v[0];
-                dirty_ = true;
-            }
-        };
-        if (key == "max_steps") I(P.max_steps);
-        else if (key == "agent_scale") geometry(agent_scale_);
-        else if (!P_.grid && key == "agent_speed") geometry(agent_speed_);
-        else if (key == "show_origin") { B(P.show_origin); if (e) P.show_origin = 0; /* dead branch in the reference (:150) */ }
-        else if (key == "visual_feedback") B(P.visual_feedback);
+        const OptionArg A{set, key, v, n, dirty_};
+        if (key == "max_steps") P.max_steps = A.integer();
+        else if (key == "agent_scale") A.geometry(agent_scale_, v[0]);
+        else if (!P_.grid && key == "agent_speed") A.geometry(agent_speed_, v[0]);
+        else if (key == "show_origin") { P.show_origin = A.flag(); if (e) P.show_origin = 0; /* dead branch in the reference (:150) */ }
+        else if (key == "visual_feedback") P.visual_feedback = A.flag();
         else if (key == "reward_fall_off") P.r_fall = v[0];
         else if (key == "reward_path_progress") P.r_progress = v[0];
         else if (key == "reward_step") P.r_step = v[0];
-        else if (e && key == "show_past_path") B(P.show_past_path);
-        else if (e && key == "show_background") B(P.show_background);
-        else if (e && key == "show_stamina") B(P.show_stamina);
-        else if (e && key == "camera_offset_scale") geometry(camera_offset_scale_);
-        else if (e && key == "stamina_level") { I(P.stamina_level); must_be(P.stamina_level > 0); }
+        else if (e && key == "show_past_path") P.show_past_path = A.flag();
+        else if (e && key == "show_background") P.show_background = A.flag();
+        else if (e && key == "show_stamina") P.show_stamina = A.flag();
+        else if (e && key == "camera_offset_scale") A.geometry(camera_offset_scale_, v[0]);
+        else if (e && key == "stamina_level") { P.stamina_level = A.integer(); A.must_be(P.stamina_level > 0); }
         else if (e && key == "reward_path_progress_dense") P.r_dense = v[0];
         else if (!e && key == "cardinal_origin_choice") {
-            must_be(n >= 1);  // any length; every value other than 0, 1, 2 takes the reference's `else` branch (mystery_path.py:155-166)
+            A.must_be(n >= 1);  // any length; every value other than 0, 1, 2 takes the reference's `else` branch (mystery_path.py:155-166)
             std::vector<int> vals(n);
             for (int k = 0; k < n; ++k) {
-                const int c = to_int_checked(v[k], key.c_str());
+                const int c = A.integer(k);
                 vals[k] = (c >= 0 && c <= 2) ? c : 3;
             }
             O.st_cardinal.set(P.cardinal, vals);
         }
-        else if (!e && key == "show_goal") B(P.show_goal);
+        else if (!e && key == "show_goal") P.show_goal = A.flag();
         else if (!e && key == "reward_goal") P.r_goal = v[0];
         else throw OptionError{-2, "unknown reset parameter " + key};
     }
@@ -2517,11 +2505,10 @@ class MysteryFamily : public Family {
                 launch(mystery_reset_kernel<decltype(PS)::value>, dim3(blocks()), dim3(256), WS_BYTES, s, P_, io(), seeds, mask, nullptr, lpw());
             });
         }
-        if (mask && sparse_masked_raster()) {  // few frames of many: by the mask, not by a walk over every descriptor (mg_raster_v1.hpp)
-            if (big_sprites_) launch_raster_sparse<MysteryBigComposer>(desc_.p, atlas_->dev(), obs, obs_format, n_, s, mask);
-            else launch_raster_sparse<MysteryComposer>(desc_.p, atlas_->dev(), obs, obs_format, n_, s, mask);
-            check_launch();
-        } else raster(obs, s);
+        reset_frames(mask, [&](const uint8_t* m) {
+            if (big_sprites_) launch_raster_sparse<MysteryBigComposer>(desc_.p, atlas_->dev(), obs, obs_format, n_, s, m);
+            else launch_raster_sparse<MysteryComposer>(desc_.p, atlas_->dev(), obs, obs_format, n_, s, m);
+        }, [&] { raster(obs, s); });
     }
 
     void step(const int32_t* actions, void* obs, float* reward, uint8_t* done, float* gt, const mg_info_buffers* info,

@@ -29,6 +29,7 @@
 #include "mg_lab.hpp"
 #include "mg_launch.hpp"
 #include "mg_device.hpp"
+#include "mg_palette.hpp"
 #include "mg_stream_out.hpp"
 
 namespace mg {
@@ -47,9 +48,6 @@ __device__ __forceinline__ cptr<T> as_const(const T* p) {
 }
 
 constexpr int DISC_RMAX = 64;
-constexpr int MAX_STAMPS = 48;
-constexpr int PALETTE_SIZE = 32;
-constexpr int MASK_WORDS = 3;                 // 84 bits per column
 constexpr int RASTER_GRID = 256 * 7 * 8;      // workgroups of a launch over many frames (65,536 and more)
 constexpr int RASTER_GRID_SMALL = 256 * 38;   // ... over 24,576 frames or fewer: see raster_grid()
 constexpr int RASTER_PLAIN_MAX = 16384;       // launches up to this many frames use plain stores, larger ones non-temporal: raster_nt()
@@ -77,13 +75,6 @@ struct RasterAtlas {
     const AtlasTables* tables;
 };
 
-// Palette ids shared by all families
-enum : uint8_t {
-    C_KEY = 0, C_BODY = 1, C_HAND = 2, C_OUTLINE = 3, C_WHITE = 4, C_RED = 5, C_GREEN = 6, C_BLUE = 7, C_YELLOW = 8,
-    C_ORANGE = 9, C_GREY50 = 10, C_GREY120 = 11, C_PURPLE = 12, C_ACT_ORANGE = 13, C_GREY210 = 14, C_BLACK = 15,
-    C_EXIT_OPEN = 16, C_EXIT_CLOSED = 17, C_ICY = 18
-};
-
 struct RasterCtx {
     uint8_t* frame;         // LDS, [x][y][c]
     uint32_t* mask;         // LDS, [84][MASK_WORDS] hole mask scratch
@@ -91,13 +82,6 @@ struct RasterCtx {
     RasterAtlas A;
     int tid;
 };
-
-__device__ __forceinline__ void put_rgb(uint8_t* frame, int x, int y, uint32_t rgb) {
-    uint8_t* p = frame + (x * SCREEN + y) * 3;
-    p[0] = (uint8_t)rgb;
-    p[1] = (uint8_t)(rgb >> 8);
-    p[2] = (uint8_t)(rgb >> 16);
-}
 
 // d - floor(d * a / 255) for the four bytes of a dword (SDL ALPHA_BLEND_RGB towards black), two bytes at a time in
 // 16-bit lanes: t = d*a <= 65025 and t + 1 + (t >> 8) <= 65280 never carry into the neighbouring lane, and
@@ -349,7 +333,6 @@ __global__ __launch_bounds__(256, 7) void raster_kernel(const typename Composer:
 
 // A launch that draws FEW of the n frames (a masked reset; round 6, see mg_raster_v1.hpp: raster_sparse_kernel): a workgroup owns
 // SPARSE_CHUNK consecutive instances, reads their descriptors (and the caller's mask) with one vector load and draws the ones a ballot names.
-constexpr int SPARSE_CHUNK = 32;
 template <class Composer, int FMT>
 __global__ __launch_bounds__(256) void raster_sparse_kernel(const typename Composer::Desc* __restrict__ descs, RasterAtlas A,
                                                           void* __restrict__ obs, int n, const uint8_t* __restrict__ only) {
@@ -425,7 +408,7 @@ inline void launch_raster(const typename Composer::Desc* descs, const RasterAtla
 template <class Composer>
 inline void launch_raster_sparse(const typename Composer::Desc* descs, const RasterAtlas& atlas, void* obs, int fmt, int n, hipStream_t s,
                                  const uint8_t* only) {
-    const dim3 grid(std::min((n + SPARSE_CHUNK - 1) / SPARSE_CHUNK, 8192));
+    const dim3 grid(sparse_grid(n));
     with_obs_format(fmt, [&](auto F) { launch(raster_sparse_kernel<Composer, decltype(F)::value>, grid, dim3(256), RASTER_LDS, s, descs, atlas, obs, n, only); });
 }
 

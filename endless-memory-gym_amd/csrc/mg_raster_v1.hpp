@@ -34,14 +34,12 @@
 #include "mg_lab.hpp"
 #include "mg_launch.hpp"
 #include "mg_device.hpp"
+#include "mg_palette.hpp"
 #include "mg_stream_out.hpp"
 
 namespace mg {
 namespace v1 {
 
-constexpr int MAX_STAMPS = 48;
-constexpr int PALETTE_SIZE = 32;
-constexpr int MASK_WORDS = 3;                 // 84 bits per column
 constexpr int RASTER_GRID = 256 * 7 * 8;      // persistent workgroups (bench sweep at seven per CU: best of 2..37 rounds)
 constexpr int RASTER_LDS = FRAME_BYTES + SCREEN * MASK_WORDS * 4;
 
@@ -63,13 +61,6 @@ struct RasterAtlas {
     const AtlasTables* tables;
 };
 
-// Palette ids shared by all families
-enum : uint8_t {
-    C_KEY = 0, C_BODY = 1, C_HAND = 2, C_OUTLINE = 3, C_WHITE = 4, C_RED = 5, C_GREEN = 6, C_BLUE = 7, C_YELLOW = 8,
-    C_ORANGE = 9, C_GREY50 = 10, C_GREY120 = 11, C_PURPLE = 12, C_ACT_ORANGE = 13, C_GREY210 = 14, C_BLACK = 15,
-    C_EXIT_OPEN = 16, C_EXIT_CLOSED = 17, C_ICY = 18
-};
-
 struct RasterCtx {
     uint8_t* frame;         // LDS, [x][y][c]
     uint32_t* mask;         // LDS, [84][MASK_WORDS] hole mask scratch
@@ -77,13 +68,6 @@ struct RasterCtx {
     RasterAtlas A;
     int tid;
 };
-
-__device__ __forceinline__ void put_rgb(uint8_t* frame, int x, int y, uint32_t rgb) {
-    uint8_t* p = frame + (x * SCREEN + y) * 3;
-    p[0] = (uint8_t)rgb;
-    p[1] = (uint8_t)(rgb >> 8);
-    p[2] = (uint8_t)(rgb >> 16);
-}
 
 // all six 16-byte loads are issued before the first LDS write (one L2 round trip, not six)
 __device__ __forceinline__ void fill_template(const RasterCtx& R, int t) {
@@ -195,7 +179,6 @@ __global__ __launch_bounds__(256, 7) void raster_kernel(const typename Composer:
 // its n / grid descriptors one after the other -- ~0.7 us each, 28 us for the ~1,400 frames a gymnasium-convention step of 65,536 instances
 // resets.  Here a workgroup owns SPARSE_CHUNK consecutive instances, reads their descriptors (and the caller's mask) with one vector load
 // and draws the ones a ballot names.  (A kernel of its own: the dense launches are the measured ones and stay as they are.)
-constexpr int SPARSE_CHUNK = 32;
 template <class Composer, int FMT>
 __global__ __launch_bounds__(256) void raster_sparse_kernel(const typename Composer::Desc* __restrict__ descs, RasterAtlas A,
                                                           void* __restrict__ obs, int n, const uint8_t* __restrict__ only) {
@@ -244,7 +227,7 @@ inline void launch_raster(const typename Composer::Desc* descs, const RasterAtla
 template <class Composer>
 inline void launch_raster_sparse(const typename Composer::Desc* descs, const RasterAtlas& atlas, void* obs, int fmt, int n, hipStream_t s,
                                  const uint8_t* only) {
-    const dim3 grid(std::min((n + SPARSE_CHUNK - 1) / SPARSE_CHUNK, 8192));
+    const dim3 grid(sparse_grid(n));
     with_obs_format(fmt, [&](auto F) { launch(raster_sparse_kernel<Composer, decltype(F)::value>, grid, dim3(256), RASTER_LDS, s, descs, atlas, obs, n, only); });
 }
 

@@ -1616,79 +1616,67 @@ class SpotFamily : public Family {
         SpotOpt& O = sets_.ensure(set, derive);
         SpotParams& P = O.P;
         const bool e = P_.endless;
-        // handle-wide values (members of the family) that fix geometry: `member = value` in set 0, "must already be so" elsewhere
-        auto G = [&](double& member, double value) {
-            if (set == 0) { member = value; dirty_ = true; }
-            else if (member != value) throw OptionError{-3, "reset parameter " + key + " changes the geometry shared by the handle's instances: it can only be set for all of them (option set 0)"};
-        };
-        auto GI = [&](int& member, int value) {
-            double m = member;
-            G(m, (double)value);
-            member = (int)m;
-        };
-        auto I = [&](int& dst) { dst = to_int_checked(v[0], key.c_str()); };
-        auto B = [&](int& dst) { dst = v[0] != 0.0; };
-        auto must_be = [&](bool ok) { if (!ok) throw OptionError{-3, "reset parameter " + key + ": this value is not supported by the MI355X build"}; };
-        if (key == "max_steps") I(P.max_steps);
-        else if (key == "initial_spawns") { I(P.initial_spawns); must_be(P.initial_spawns >= 0 && P.initial_spawns <= SLOTS); }
+        const OptionArg A{set, key, v, n, dirty_};
+        if (key == "max_steps") P.max_steps = A.integer();
+        else if (key == "initial_spawns") { P.initial_spawns = A.integer(); A.must_be(P.initial_spawns >= 0 && P.initial_spawns <= SLOTS); }
         else if (key == "spot_min_radius") { O.min_radius = v[0]; derive(O); }
         else if (key == "spot_max_radius") { O.max_radius = v[0]; derive(O); }
         else if (key == "spot_min_speed") P.speed_lo = v[0];
         else if (key == "spot_max_speed") P.speed_hi = v[0];
         else if (key == "spot_damage") P.damage = v[0];
-        else if (key == "visual_feedback") B(P.visual_feedback);
+        else if (key == "visual_feedback") P.visual_feedback = A.flag();
         else if (key == "black_background") {
-            B(P.black_background);
+            P.black_background = A.flag();
             if (P.black_background && !P_.ordered_holes) {  // from now on spotlights may carry a border (sticky, kept in the state)
                 P_.ordered_holes = 1;
                 const int one = 1;
                 MG_HIP(hipMemcpy(flags_.p, &one, sizeof(int), hipMemcpyHostToDevice));
             }
         }
-        else if (key == "hide_chessboard") B(P.hide_chessboard);
-        else if (key == "light_dim_off_duration") { O.dim_duration = to_int_checked(v[0], key.c_str()); derive(O); }
-        else if (key == "light_threshold") I(P.light_threshold);
-        else if (key == "coin_scale") G(coin_scale_, v[0]);
-        else if (key == "coins_visible") B(P.coins_visible);
-        else if (key == "agent_speed") G(agent_speed_, v[0]);
+        else if (key == "hide_chessboard") P.hide_chessboard = A.flag();
+        else if (key == "light_dim_off_duration") { O.dim_duration = A.integer(); derive(O); }
+        else if (key == "light_threshold") P.light_threshold = A.integer();
+        else if (key == "coin_scale") A.geometry(coin_scale_, v[0]);
+        else if (key == "coins_visible") P.coins_visible = A.flag();
+        else if (key == "agent_speed") A.geometry(agent_speed_, v[0]);
         else if (key == "agent_health") P.agent_health = v[0];
-        else if (key == "agent_scale") G(agent_scale_, v[0]);
+        else if (key == "agent_scale") A.geometry(agent_scale_, v[0]);
         else if (key == "agent_visible") P.layer_flags = (P.layer_flags & ~LAYER_AGENT_TOP) | (v[0] != 0.0 ? LAYER_AGENT_TOP : 0);
-        else if (key == "sample_agent_position") B(P.sample_agent_position);
+        else if (key == "sample_agent_position") P.sample_agent_position = A.flag();
         else if (key == "show_last_action") {
             // (the last-reward bar's position and width depend on it, searing_spotlights.py:385-390: geometry)
-            GI(P_.show_last_action, v[0] != 0.0 ? 1 : 0);
+            A.geometry(P_.show_last_action, A.flag() ? 1 : 0);
             // False crashes the ENDLESS reference at its first step (endless_searing_spotlights.py:422 reads action_colors,
             // which :343 only creates when the flag is set); the finite env guards the use (searing_spotlights.py:465)
-            if (e) must_be(v[0] != 0.0);
+            if (e) A.must_be(v[0] != 0.0);
         }
-        else if (key == "show_last_positive_reward") B(P.show_last_positive_reward);
+        else if (key == "show_last_positive_reward") P.show_last_positive_reward = A.flag();
         else if (key == "reward_inside_spotlight") P.r_inside = v[0];
         else if (key == "reward_outside_spotlight") P.r_outside = v[0];
         else if (key == "reward_death") P.r_death = v[0];
         else if (key == "reward_coin") P.r_coin = v[0];
-        else if (e && key == "steps_per_coin") I(P.steps_per_coin);
-        else if (e && key == "spawn_interval") I(P.spawn_interval);
-        else if (e && key == "coin_enabled") B(P.coin_enabled);
-        else if (e && key == "coin_show_duration") I(P.coin_show_duration);
-        else if (!e && key == "num_spawns") { I(P.num_spawns); must_be(P.num_spawns >= 0 && P.num_spawns <= 255); }
-        else if (!e && key == "initial_spawn_interval") G(initial_spawn_interval_, v[0]);
-        else if (!e && key == "spawn_interval_threshold") G(spawn_interval_threshold_, v[0]);
+        else if (e && key == "steps_per_coin") P.steps_per_coin = A.integer();
+        else if (e && key == "spawn_interval") P.spawn_interval = A.integer();
+        else if (e && key == "coin_enabled") P.coin_enabled = A.flag();
+        else if (e && key == "coin_show_duration") P.coin_show_duration = A.integer();
+        else if (!e && key == "num_spawns") { P.num_spawns = A.integer(); A.must_be(P.num_spawns >= 0 && P.num_spawns <= 255); }
+        else if (!e && key == "initial_spawn_interval") A.geometry(initial_spawn_interval_, v[0]);
+        else if (!e && key == "spawn_interval_threshold") A.geometry(spawn_interval_threshold_, v[0]);
         else if (!e && key == "spawn_interval_decay") { /* only intervals[0] is ever read (pop() takes the last) */ }
         else if (!e && key == "num_coins") {
             // any length (searing_spotlights.py:408); the empty list is refused by mg_set_option: the reference ends every such
             // episode with a ZeroDivisionError (searing_spotlights.py:553)
             std::vector<int> vals(n);
             for (int k = 0; k < n; ++k) {
-                vals[k] = to_int_checked(v[k], key.c_str());
-                must_be(vals[k] >= 1 && vals[k] <= MAX_COINS);
+                vals[k] = A.integer(k);
+                A.must_be(vals[k] >= 1 && vals[k] <= MAX_COINS);
             }
             O.st_num_coins.set(P.num_coins, vals);
         }
         // False: legal once the instance has had an exit (its stale one is drawn, spot_reset); before that the reference raises
         // AttributeError and the reset raises error bit 256
-        else if (!e && key == "use_exit") B(P.use_exit);
-        else if (!e && key == "exit_scale") G(exit_scale_, v[0]);
+        else if (!e && key == "use_exit") P.use_exit = A.flag();
+        else if (!e && key == "exit_scale") A.geometry(exit_scale_, v[0]);
         else if (!e && key == "exit_visible") P.layer_flags = (P.layer_flags & ~LAYER_EXIT_ABOVE) | (v[0] != 0.0 ? LAYER_EXIT_ABOVE : 0);
         else if (!e && key == "reward_exit") P.r_exit = v[0];
         else if (!e && key == "reward_max_steps") {}
@@ -1721,11 +1709,10 @@ class SpotFamily : public Family {
                 launch(spot_reset_kernel<decltype(EN)::value, decltype(PS)::value>, rg, dim3(256), 0, s, P_, io(), seeds, mask, gt);
             });
         });
-        if (mask && sparse_masked_raster()) {  // few frames of many: by the mask, not by a walk over every descriptor (mg_raster.hpp)
-            if (P_.ordered_holes) launch_raster_sparse<SpotBorderComposer>(desc_.p, atlas_->dev(), obs, obs_format, n_, s, mask);
-            else launch_raster_sparse<SpotComposer>(desc_.p, atlas_->dev(), obs, obs_format, n_, s, mask);
-            check_launch();
-        } else raster(obs, s);
+        reset_frames(mask, [&](const uint8_t* m) {
+            if (P_.ordered_holes) launch_raster_sparse<SpotBorderComposer>(desc_.p, atlas_->dev(), obs, obs_format, n_, s, m);
+            else launch_raster_sparse<SpotComposer>(desc_.p, atlas_->dev(), obs, obs_format, n_, s, m);
+        }, [&] { raster(obs, s); });
     }
 
     void step(const int32_t* actions, void* obs, float* reward, uint8_t* done, float* gt, const mg_info_buffers* info,

@@ -42,6 +42,40 @@ def test_reference_shaped_loop(env_id):
     e.close()
 
 
+def test_single_and_batched_steps_alternate_on_one_handle():
+    """One MortarMayhem-Grid-v0 handle: single steps (mg_single_step, whose one-launch kernel stores the completion ticket itself), then
+    batched steps on the same handle (mg_step: the same kernel without the flag), then single steps again, in lock-step with the oracle.
+    The batched steps' results are read from the handle's device tensors; the adapter's host views are only written by single steps."""
+    import memory_gym_amd
+    import oracle_lib
+
+    env_id = "MortarMayhem-Grid-v0"
+    e = memory_gym_amd.make(env_id)
+    r = oracle_lib.OracleEnv(env_id)
+    o, _ = e.reset(seed=11)
+    assert np.array_equal(o, r.reset(11))
+    assert e.vec.autoreset is False  # as the adapter set it: episodes are re-started through e.reset()
+    prng = np.random.Generator(np.random.PCG64(3))
+    episodes = 0
+    for phase, batched in enumerate([False, True, False, True, False]):
+        for t in range(60):
+            a = int(prng.integers(0, 4))
+            if batched:
+                e.vec.step(np.array([a], dtype=np.int32))
+                o, rw, d = e.vec.obs[0].cpu().numpy(), float(e.vec.reward64[0].cpu()), bool(e.vec.done_u8[0].cpu())
+            else:
+                o, rw, d, _, _ = e.step(a)
+            o2, r2, d2 = r.step([a, 0])
+            assert np.array_equal(o, o2) and rw == r2 and d == d2, (phase, t)
+            if d:
+                episodes += 1
+                o, _ = e.reset()
+                assert np.array_equal(o, r.reset(None)), (phase, t)
+    assert episodes > 0
+    assert np.array_equal(e.vec.rng_words(0), r.rng_words())
+    e.close()
+
+
 @pytest.mark.parametrize("env_id", ["Endless-MortarMayhem-v0", "Endless-SearingSpotlights-v0", "Endless-MysteryPath-v0"])
 def test_batched_ground_truth_in_float64(env_id):
     """mg_info_buffers.gt64_dev / mg_ground_truth64: info["ground_truth"] as the reference's doubles for every instance of a batch
