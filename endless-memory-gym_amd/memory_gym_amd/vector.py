@@ -108,8 +108,9 @@ class GymnasiumVectorEnv(_Base):
         self._pending_reset = (seed, options)
 
     def reset_wait(self, seed=None, options=None):
-        s, o = getattr(self, "_pending_reset", (seed, options))
-        return self.reset(seed=s, options=o)
+        # what reset_async left is used ONCE; arguments given here go before it (a later reset_wait(seed=2) does not reset with an old seed)
+        s, o = self.__dict__.pop("_pending_reset", (None, None))
+        return self.reset(seed=s if seed is None else seed, options=o if options is None else options)
 
     def close(self, **kwargs):
         if not self.closed:

@@ -233,6 +233,111 @@ void mgo_batch_get(mgo_batch* b, const char* field, double* out) {
     }
 }
 
+/* ---- frame digests: the oracle referees every frame of every step without writing an [n][dim][dim][3] array -----------------
+ * One 64-bit value per observation (tests/frame_digest.py computes the same value from a torch tensor or a numpy array): the
+ * dim * dim * 3 bytes in mgo_array3d's [x][y][c] order, read as little-endian 32-bit words w[k];
+ *     digest = sum_k w[k] * (mgo_mix64(k) | 1)   mod 2^64.
+ * Every multiplier is odd, so a frame that differs in ONE word always has another digest (an odd number times a non-zero
+ * 32-bit difference is non-zero mod 2^64); the multipliers differ from position to position, so moved content shows too. */
+typedef struct {
+    int words;
+    uint64_t* coef;
+} mgo_digest_plan;
+
+static int mgo_digest_plan_init(mgo_digest_plan* p, const mgo_batch* b) {
+    size_t fs = (size_t)b->envs[0]->screen_dim * b->envs[0]->screen_dim * 3;
+    if (fs % 4) return -1;
+    p->words = (int)(fs / 4);
+    p->coef = (uint64_t*)malloc(sizeof(uint64_t) * (size_t)p->words);
+    if (!p->coef) return -1;
+    for (int k = 0; k < p->words; k++) p->coef[k] = mgo_mix64((uint64_t)k) | 1ull;
+    return 0;
+}
+
+/* `buf`: the calling thread's words * 4 bytes */
+static uint64_t mgo_frame_digest(const mgo_digest_plan* p, const mgo_surf* s, uint8_t* buf) {
+    mgo_array3d(s, buf);
+    uint64_t d = 0;
+    for (int k = 0; k < p->words; k++) {
+        const uint8_t* q = buf + 4 * (size_t)k;
+        uint32_t w = (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16) | ((uint32_t)q[3] << 24);
+        d += (uint64_t)w * p->coef[k];
+    }
+    return d;
+}
+
+/* mgo_batch_reset with digest[i] of every instance's first frame in place of the frames */
+int mgo_batch_reset_digest(mgo_batch* b, const int64_t* seeds, uint64_t* digest) {
+    mgo_digest_plan p;
+    if (mgo_digest_plan_init(&p, b) != 0) return -1;
+    int rc = 0;
+#pragma omp parallel
+    {
+        uint8_t* buf = (uint8_t*)malloc(4 * (size_t)p.words);
+#pragma omp for schedule(static)
+        for (int i = 0; i < b->n; i++) {
+            if (mgo_reset(b->envs[i], seeds ? seeds[i] : -1, NULL) != 0 || !buf) {
+#pragma omp atomic write
+                rc = -1;
+                continue;
+            }
+            digest[i] = mgo_frame_digest(&p, b->envs[i]->screen, buf);
+        }
+        free(buf);
+    }
+    free(p.coef);
+    return rc;
+}
+
+/* mgo_batch_step -- the same state, rewards, dones and RNG consumption -- with digests in place of the frames.  digest[i]: the
+ * observation mgo_batch_step would have written for instance i (the new episode's first frame where the instance finished and
+ * autoreset is set).  final_digest[i] (may be NULL): where done[i] and autoreset, the TERMINAL frame, i.e. what the step drew
+ * before the reset; untouched elsewhere. */
+int mgo_batch_step_digest(mgo_batch* b, const int32_t* actions, int autoreset, uint64_t* digest, uint64_t* final_digest,
+                          double* reward, uint8_t* done) {
+    mgo_digest_plan p;
+    if (mgo_digest_plan_init(&p, b) != 0) return -1;
+    int disc = b->envs[0]->vt->discrete;
+    int rc = 0;
+#pragma omp parallel
+    {
+        uint8_t* buf = (uint8_t*)malloc(4 * (size_t)p.words);
+#pragma omp for schedule(static)
+        for (int i = 0; i < b->n; i++) {
+            int a[2] = {actions[disc ? i : 2 * i], disc ? 0 : actions[2 * i + 1]};
+            double r;
+            int d;
+            mgo_step(b->envs[i], a, NULL, &r, &d);
+            if (reward) reward[i] = r;
+            if (done) done[i] = (uint8_t)d;
+            if (!buf) {
+#pragma omp atomic write
+                rc = -1;
+                if (d && autoreset) mgo_reset(b->envs[i], -1, NULL);
+                continue;
+            }
+            if (d && autoreset) {
+                if (final_digest) final_digest[i] = mgo_frame_digest(&p, b->envs[i]->screen, buf);
+                mgo_reset(b->envs[i], -1, NULL);
+            }
+            digest[i] = mgo_frame_digest(&p, b->envs[i]->screen, buf);
+        }
+        free(buf);
+    }
+    free(p.coef);
+    return rc;
+}
+
+/* the CURRENT frame of the chosen instances (what lies on their screens), to show a digest mismatch as pixels: obs [count][dim][dim][3] */
+int mgo_batch_frames(mgo_batch* b, const int32_t* which, int count, uint8_t* obs) {
+    size_t fs = (size_t)b->envs[0]->screen_dim * b->envs[0]->screen_dim * 3;
+    for (int j = 0; j < count; j++)
+        if (which[j] < 0 || which[j] >= b->n) return -1;
+#pragma omp parallel for schedule(static)
+    for (int j = 0; j < count; j++) mgo_array3d(b->envs[which[j]]->screen, obs + fs * j);
+    return 0;
+}
+
 /* Test hook (tests/test_oracle_properties.py): pygame.draw.circle(surface, white, (cx, cy), radius, width) on a black dim x dim
  * surface; out[y * dim + x] = 1 where a pixel was drawn. */
 int mgo_test_circle(int dim, int cx, int cy, int radius, int width, uint8_t* out) {

@@ -49,6 +49,9 @@ def lib():
         L.mgo_batch_step.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mgo_batch_expert.argtypes = [C.c_void_p, C.c_double, C.c_uint64, C.c_uint64, C.c_void_p]
         L.mgo_batch_get.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p]
+        L.mgo_batch_reset_digest.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mgo_batch_step_digest.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mgo_batch_frames.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         _lib = L
     return _lib
 
@@ -203,3 +206,32 @@ class OracleBatch:
         self.L.mgo_batch_step(self.h, a.ctypes.data, int(autoreset), obs.ctypes.data if want_obs else None,
                               rew.ctypes.data, done.ctypes.data)
         return obs, rew, done
+
+    # ---- frame digests (oracle/mgo_api.c; tests/frame_digest.py computes the same values from tensors / arrays)
+    def reset_digest(self, seeds=None, out=None):
+        """reset() that returns uint64 [n] digests of the first frames instead of the frames."""
+        dg = np.empty(self.n, np.uint64) if out is None else out
+        s = None if seeds is None else np.ascontiguousarray(seeds, dtype=np.int64)
+        assert self.L.mgo_batch_reset_digest(self.h, None if s is None else s.ctypes.data, dg.ctypes.data) == 0
+        return dg
+
+    def step_digest(self, actions, autoreset=True, out=None):
+        """step() with digests in place of the frames: (digest uint64 [n], final_digest uint64 [n], reward float64 [n], done uint8 [n]);
+        final_digest[i] is the terminal frame's digest where done[i] (and autoreset), untouched elsewhere.  `out`: these four, preallocated."""
+        a = np.ascontiguousarray(actions, dtype=np.int32)
+        if out is not None:
+            dg, fdg, rew, done = out
+        else:
+            dg, fdg = np.empty(self.n, np.uint64), np.zeros(self.n, np.uint64)
+            rew, done = np.empty(self.n, np.float64), np.empty(self.n, np.uint8)
+        assert self.L.mgo_batch_step_digest(self.h, a.ctypes.data, int(autoreset), dg.ctypes.data, fdg.ctypes.data,
+                                            rew.ctypes.data, done.ctypes.data) == 0
+        return dg, fdg, rew, done
+
+    def frames(self, which, out=None):
+        """uint8 [len(which), dim, dim, 3]: the frames that lie on the screens of the chosen instances right now."""
+        w = np.ascontiguousarray(which, dtype=np.int32)
+        obs = np.empty((len(w), self.dim, self.dim, 3), np.uint8) if out is None else out
+        assert obs.shape == (len(w), self.dim, self.dim, 3) and obs.dtype == np.uint8 and obs.flags.c_contiguous
+        assert self.L.mgo_batch_frames(self.h, w.ctypes.data, len(w), obs.ctypes.data) == 0
+        return obs

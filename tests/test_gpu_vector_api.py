@@ -80,3 +80,26 @@ def test_numpy_mode_layout():
             assert "final_observation" not in infos
     assert seen
     envs.close()
+
+
+def test_reset_wait_forgets_what_reset_async_left():
+    """reset_async(seed=1); reset_wait() resets with seed 1 -- once.  A later reset_wait(seed=2) is reset(seed=2)."""
+    import memory_gym_amd
+    import torch
+
+    n = 40
+    envs = memory_gym_amd.GymnasiumVectorEnv("MysteryPath-Grid-v0", n, device=0)
+    twin = memory_gym_amd.GymnasiumVectorEnv("MysteryPath-Grid-v0", n, device=0)
+    envs.reset_async(seed=1)
+    o1 = envs.reset_wait()[0].clone()
+    assert torch.equal(o1, twin.reset(seed=1)[0])
+    o2 = envs.reset_wait(seed=2)[0].clone()
+    want2 = twin.reset(seed=2)[0]
+    assert torch.equal(o2, want2) and not torch.equal(o2, o1)
+    for i in (0, n - 1):
+        assert np.array_equal(envs.env.rng_words(i), twin.env.rng_words(i))
+    envs.reset_async(seed=3)
+    o3 = envs.reset_wait(seed=4)[0]  # an argument of reset_wait goes before what reset_async left
+    assert torch.equal(o3, twin.reset(seed=4)[0])
+    envs.close()
+    twin.close()
