@@ -31,6 +31,7 @@ struct Pcg {
     uint32_t buf;
     bool has;
 
+    __device__ __forceinline__ void clear() { state = inc = 0; buf = 0; has = false; }  // an empty stream: a lane that carries no instance
     __device__ __forceinline__ void load(const RngSoA& r, int i) {
         state = ((u128)r.s_hi[i] << 64) | r.s_lo[i];
         inc = ((u128)r.inc_hi[i] << 64) | r.inc_lo[i];

@@ -57,6 +57,13 @@ __device__ __forceinline__ int queue_count(const int* counter, int cap) {
     const int c = *counter;
     return c < cap ? c : cap;
 }
+// One thread of every workgroup that serves a queue, when its workgroup is done: the last of the `participants` out clears the counters (entries, pops beyond
+// the static first round, participants that left; bg_count: a second queue's entries, or NULL), so that the launches can be replayed from a HIP graph.
+__device__ __forceinline__ void queue_leave(int* left, int participants, int* count, int* head, int* bg_count = nullptr) {
+    if (atomicAdd(left, 1) != participants - 1) return;
+    *count = 0; *head = 0; *left = 0;  // (in this order)
+    if (bg_count) *bg_count = 0;
+}
 #endif
 
 template <typename T>

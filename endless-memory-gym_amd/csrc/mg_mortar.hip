@@ -642,12 +642,7 @@ __global__ __launch_bounds__(256, 7) void mortar_step_raster_kernel(MortarStepAr
         return;
     }
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    RasterCtx R;
-    R.frame = smem;
-    R.mask = reinterpret_cast<uint32_t*>(smem + FRAME_BYTES);
-    R.A = A;
-    R.T = A.tables;
-    R.tid = tid;
+    RasterCtx R = make_ctx(smem, A);
     const int stride = (int)gridDim.x - logic_wgs;
     for (int v = (int)blockIdx.x < logic_base ? (int)blockIdx.x : (int)blockIdx.x - logic_wgs; v < n; v += stride) {
         const int env = xcd_grouped_frame(v, n);

@@ -82,6 +82,12 @@ struct RasterCtx {
     RasterAtlas A;
     int tid;
 };
+__device__ __forceinline__ RasterCtx make_ctx(uint8_t* smem, const RasterAtlas& A) {  // smem: the workgroup's RASTER_LDS bytes
+    RasterCtx R;
+    R.frame = smem; R.mask = reinterpret_cast<uint32_t*>(smem + FRAME_BYTES);
+    R.A = A; R.T = as_const(A.tables); R.tid = threadIdx.x;
+    return R;
+}
 
 // d - floor(d * a / 255) for the four bytes of a dword (SDL ALPHA_BLEND_RGB towards black), two bytes at a time in
 // 16-bit lanes: t = d*a <= 65025 and t + 1 + (t >> 8) <= 65280 never carry into the neighbouring lane, and
@@ -309,12 +315,7 @@ template <class Composer, int FMT, bool NT>
 __global__ __launch_bounds__(256, 7) void raster_kernel(const typename Composer::Desc* __restrict__ descs, RasterAtlas A,
                                                      void* __restrict__ obs, int n, const uint8_t* __restrict__ only) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    RasterCtx R;
-    R.frame = smem;
-    R.mask = reinterpret_cast<uint32_t*>(smem + FRAME_BYTES);
-    R.A = A;
-    R.T = as_const(A.tables);
-    R.tid = threadIdx.x;
+    const RasterCtx R = make_ctx(smem, A);
     const int tid = threadIdx.x, stride = gridDim.x;
     const cptr<typename Composer::Desc> cdescs = as_const(descs);
     Composer::recycle(R);  // scratch state compose() expects (e.g. a zeroed hole mask); published by the barriers below
@@ -337,12 +338,7 @@ template <class Composer, int FMT>
 __global__ __launch_bounds__(256) void raster_sparse_kernel(const typename Composer::Desc* __restrict__ descs, RasterAtlas A,
                                                           void* __restrict__ obs, int n, const uint8_t* __restrict__ only) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    RasterCtx R;
-    R.frame = smem;
-    R.mask = reinterpret_cast<uint32_t*>(smem + FRAME_BYTES);
-    R.A = A;
-    R.T = as_const(A.tables);
-    R.tid = threadIdx.x;
+    const RasterCtx R = make_ctx(smem, A);
     const int tid = threadIdx.x;
     const cptr<typename Composer::Desc> cdescs = as_const(descs);
     Composer::recycle(R);  // scratch state compose() expects (e.g. a zeroed hole mask); published by the barriers below

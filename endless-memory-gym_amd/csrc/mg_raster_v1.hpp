@@ -68,6 +68,12 @@ struct RasterCtx {
     RasterAtlas A;
     int tid;
 };
+__device__ __forceinline__ RasterCtx make_ctx(uint8_t* smem, const RasterAtlas& A) {  // smem: the workgroup's RASTER_LDS bytes
+    RasterCtx R;
+    R.frame = smem; R.mask = reinterpret_cast<uint32_t*>(smem + FRAME_BYTES);
+    R.A = A; R.T = A.tables; R.tid = threadIdx.x;
+    return R;
+}
 
 // all six 16-byte loads are issued before the first LDS write (one L2 round trip, not six)
 __device__ __forceinline__ void fill_template(const RasterCtx& R, int t) {
@@ -153,12 +159,7 @@ template <class Composer, int FMT>
 __global__ __launch_bounds__(256, 7) void raster_kernel(const typename Composer::Desc* __restrict__ descs, RasterAtlas A,
                                                      void* __restrict__ obs, int n, const uint8_t* __restrict__ only) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    RasterCtx R;
-    R.frame = smem;
-    R.mask = reinterpret_cast<uint32_t*>(smem + FRAME_BYTES);
-    R.A = A;
-    R.T = A.tables;
-    R.tid = threadIdx.x;
+    const RasterCtx R = make_ctx(smem, A);
     const int tid = threadIdx.x;
     for (int v = blockIdx.x; v < n; v += gridDim.x) {
         const int env = xcd_grouped_frame(v, n);
@@ -183,12 +184,7 @@ template <class Composer, int FMT>
 __global__ __launch_bounds__(256) void raster_sparse_kernel(const typename Composer::Desc* __restrict__ descs, RasterAtlas A,
                                                           void* __restrict__ obs, int n, const uint8_t* __restrict__ only) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    RasterCtx R;
-    R.frame = smem;
-    R.mask = reinterpret_cast<uint32_t*>(smem + FRAME_BYTES);
-    R.A = A;
-    R.T = A.tables;
-    R.tid = threadIdx.x;
+    const RasterCtx R = make_ctx(smem, A);
     const int tid = threadIdx.x;
     for (int base = blockIdx.x * SPARSE_CHUNK; base < n; base += gridDim.x * SPARSE_CHUNK) {
         const int e = base + (tid & (SPARSE_CHUNK - 1));  // (every wave looks at the same SPARSE_CHUNK instances: the same list in all four)

@@ -1407,12 +1407,7 @@ template <bool EN, bool BORDER, bool NT, bool FINAL = false>
 __global__ __launch_bounds__(256, MG_SPOT_SERVE_OCC) void spot_raster_serve_kernel(SpotServeArgs a) {
     typedef SpotComposerT<BORDER> Composer;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    RasterCtx R;
-    R.frame = smem;
-    R.mask = reinterpret_cast<uint32_t*>(smem + FRAME_BYTES);
-    R.A = a.A;
-    R.T = as_const(a.A.tables);
-    R.tid = threadIdx.x;
+    const RasterCtx R = make_ctx(smem, a.A);
     const int tid = threadIdx.x;
     const int n = a.n;
     void* const obs = a.obs;

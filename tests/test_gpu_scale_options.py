@@ -3,7 +3,7 @@
 
 Stamps larger than what a composer keeps in registers per layer (256 padded pixels for the spotlight family's agent / coin /
 exit, 1,024 for the Mystery Path agent) used to be refused; the spotlight composers now read the excess from the atlas while
-they compose and a Mystery Path handle switches to MysteryBigComposer (csrc/mg_mystery.hip)."""
+they compose and a Mystery Path handle switches to MysteryBigComposer (csrc/mg_mystery_compose.hpp)."""
 import numpy as np
 import pytest
 

@@ -1,4 +1,4 @@
-"""The lane-per-job path generator (csrc/mg_mystery.hip: lane_path) compares A* f-costs through integer keys
+"""The lane-per-job path generator (csrc/mg_mystery_path.hpp: lane_path) compares A* f-costs through integer keys
 (g_cost << 17) + round(sqrt(d2) * 2^17) instead of the reference's doubles g_cost + sqrt(d2)
 (/root/reference/memory_gym/pygame_assets.py:701-724, heuristic :726-736).  This checks, over every reachable
 (g_cost, d2), that the keys order exactly like the doubles and tie exactly where the doubles tie."""
