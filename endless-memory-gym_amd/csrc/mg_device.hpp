@@ -163,6 +163,17 @@ __device__ __forceinline__ void free_move(int a0, int a1, int v_axis, int v_diag
     }
 }
 
+// A kernel's arguments read AGAIN, where they are used, from the kernel-argument segment through a pointer the compiler cannot see through (T = the struct at the head
+// of the segment): as loop invariants they are hoisted out of a persistent kernel's loop and held in scalar registers for its whole length (mortar_step_raster_kernel,
+// spot_raster_serve_kernel say what that cost them).
+#define MG_KERNARG_AS __attribute__((address_space(4)))
+template <class T>
+__device__ __forceinline__ const T MG_KERNARG_AS* kernarg_reread() {
+    const T MG_KERNARG_AS* ka = (const T MG_KERNARG_AS*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(ka));
+    return ka;
+}
+
 // Index of the option set an instance runs under (include/memgym.h: mg_bind_option_sets), from the caller's int32 array: masked
 // to the MG_MAX_OPTION_SETS = 8 parameter blocks every handle uploads, so that a stray entry reads SOME block of the handle
 // (never-written sets hold the reference's defaults) instead of memory beyond them.

@@ -19,7 +19,6 @@ namespace mg {
 void set_error(const std::string& msg);
 static_assert(MG_MAX_OPTION_SETS == 8, "set_index() (mg_device.hpp) masks an instance's set index with 7");
 
-// RAII device array
 // One error word in pinned, coherent host memory mapped into the device's address space: kernels raise bits with a
 // system-scope atomic OR (rare path), the host reads them without touching the stream (mg_peek_errors).
 struct ErrorWord {
@@ -66,6 +65,7 @@ __device__ __forceinline__ void queue_leave(int* left, int participants, int* co
 }
 #endif
 
+// RAII device array
 template <typename T>
 struct DevArray {
     T* p = nullptr;

@@ -1,0 +1,143 @@
+// mg_mortar_one_launch.hpp -- Mortar Mayhem family (included by mg_mortar.hip only): mortar_step_raster_kernel, the step as ONE launch -- step workgroups and frame
+// workgroups in one grid, the claim / epoch hand-over between them, RESCUE_AFTER_TICKS, and the MG_LABV measurement forms (tools/build_variant.sh).
+#pragma once
+#include "mg_mortar_compose.hpp"
+#include "mg_mortar_step.hpp"
+
+namespace mg {
+using namespace v1;  // raster generation 1 (see mg_raster_v1.hpp)
+// ONE launch per step (uint8 observations).  `logic_wgs` workgroups of the grid run the step (one lane per instance), all others
+// are the raster's persistent workgroups; a frame's workgroup waits for ITS descriptor -- the epoch in the descriptor's last
+// word, read at agent scope past the caches -- instead of for the slowest wave of a separate logic launch plus that launch's
+// fixed cost: the first frames leave ~8 us earlier (MortarMayhem-Grid 65,536: 233 -> 224 us per step, 281 -> 292 M env-steps/s;
+// 16,384: 69 -> 65 us; profiles/r03_one_launch.md).
+//
+// Liveness does NOT rest on the order in which the hardware dispatches workgroups (round 4).  The instances are stepped in
+// slots of 64 (one wave); a slot belongs to whichever wave first exchanges this step's ticket into its claim word.  Normally
+// that is the step workgroup's wave (the step workgroups come first in the grid and are resident before the frame workgroups
+// fill the chip).  A frame wave whose descriptor has not shown the epoch after RESCUE_AFTER_TICKS (200 us) tries the claim of the
+// slot its frame belongs to ITSELF: if it wins, the step wave has not started yet (e.g. no free slot on the chip because frame
+// workgroups were dispatched first) and the frame wave steps those 64 instances with its own lanes, then draws; if it loses,
+// the slot's owner is a resident wave that never waits for anything, so the descriptor is on its way.  Every wait therefore
+// ends, no frame is ever drawn from a stale descriptor, and there is no time-out to report (error bit 128 of rounds <= 3 is
+// gone).  tests/test_gpu_one_launch.py runs the launch with the step workgroups LAST in the grid (lab build) -- every frame
+// workgroup resident before any step workgroup -- and under a concurrent stream.
+//
+// Hand-over of the 16-byte descriptor: the publisher writes words 0..2 with agent-scope (write-through) stores, waits until they
+// have reached the coherence point (s_waitcnt vmcnt(0)) and only then writes word 3, which carries the epoch; the reader polls
+// word 3 with agent-scope loads and, once it shows the epoch, reads words 0..2 with agent-scope loads issued AFTER that
+// observation.  Release / acquire atomics would be the textbook form; at agent scope on gfx950 they write back / invalidate
+// the whole L2 of the XCD around every hand-over (buffer_wbl2 / buffer_inv sc1), with the observation stream in that L2.
+// The two-launch form is used while a stream is being captured into a HIP graph (epoch and ticket are launch arguments: a
+// replay would find them satisfied already) and for handles with instance groups (their stagger needs the logic launch's end).
+
+// A frame wave tries the claim after it has waited this long (real-time clock, 100 MHz).  The step workgroups normally publish
+// within 15-20 us; the first version counted 32 polls (~15 us as it turned out): every early frame wave then sent its one
+// exchange at the few cache lines of claim words, and those ~7,000 serialised atomics cost the 16,384-instance launch 6 of
+// its 66 us (profiles/r04_one_launch.md).
+constexpr unsigned long long RESCUE_AFTER_TICKS = 20000;  // 200 us
+// DONE_FLAG (the single-instance fast path, mg_single_step: ONE frame workgroup): when the frame is out, the workgroup stores `done_ticket`
+// to `done_flag` -- a word in the caller's pinned block that the host polls -- at system scope: 2.7 us less per step than a stream memory
+// operation behind the launch, 4.5 us less than hipStreamSynchronize (tools/microbench/launch_wait.hip).  Everything else the host reads
+// (reward, done, the episode record) was stored by the step's wave BEFORE it published the descriptor this workgroup waited for.
+// FINAL: the call keeps terminal observations (see mortar_step_body) -- a kernel of its own, the measured one (FINAL = false) is as it was.
+template <bool DONE_FLAG, bool FINAL = false>
+__global__ __launch_bounds__(256, 7) void mortar_step_raster_kernel(MortarStepArgs a, int logic_wgs, int logic_base, uint32_t epoch,
+                                                                    uint32_t ticket, uint32_t* claims, uint32_t* rescues,
+                                                                    RasterAtlas A, void* __restrict__ obs, uint32_t* done_flag, uint32_t done_ticket) {
+    const int n = a.n;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int rel = (int)blockIdx.x - logic_base;
+    const bool is_logic = rel >= 0 && rel < logic_wgs;
+    // true: this wave owns slot `q` (instances 64 q .. 64 q + 63) for this step
+    auto claim = [&](int q) -> bool {
+        uint32_t old = 0;
+        if (lane == 0) old = __hip_atomic_exchange(claims + q, ticket, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return (uint32_t)__builtin_amdgcn_readfirstlane((int)old) != ticket;
+    };
+    if (is_logic) {  // a step workgroup: wave w steps slot 4 rel + w unless a frame wave got there first
+        const int q = rel * 4 + (tid >> 6), i = q * 64 + lane;
+#if defined(MG_LABV) && MG_LABV >= 1
+        if (i < n) mortar_step_body<true, false, false, FINAL>(i, a, epoch);
+#else
+        if (i < n) mortar_step_body<true, true, false, FINAL>(i, a, epoch, claims + q, ticket);
+#endif
+        return;
+    }
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    RasterCtx R = make_ctx(smem, A);
+    const int stride = (int)gridDim.x - logic_wgs;
+    for (int v = (int)blockIdx.x < logic_base ? (int)blockIdx.x : (int)blockIdx.x - logic_wgs; v < n; v += stride) {
+        const int env = xcd_grouped_frame(v, n);
+        // every lane reads the same words (one transaction per wave); no barrier: the waves of a workgroup wait separately
+        const uint32_t* src = reinterpret_cast<const uint32_t*>(a.io.desc + env);
+        uint32_t w[4];
+        bool tried = false;
+        unsigned long long t0 = 0;
+        for (int polls = 0;; ++polls) {
+            // (all lanes read the same word; readfirstlane tells the compiler so: the wait loop's control stays scalar)
+            w[3] = (uint32_t)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(src + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+            if ((w[3] >> 24) == epoch) break;
+#if defined(MG_LABV) && MG_LABV >= 2
+            if (false) {
+#else
+            if (polls == 0) t0 = wall_clock64();
+            if (!tried && (polls & 15) == 15 && wall_clock64() - t0 >= RESCUE_AFTER_TICKS) {  // (the clock is read every 16th poll)
+#endif
+                tried = true;  // (a lost claim is not retried: its owner is running)
+                if (claim(env >> 6)) {  // rare: step the 64 instances around this frame here; the next poll finds the epoch
+                    // The step's arguments are read AGAIN, from the kernel-argument segment, through a pointer the compiler
+                    // cannot see through: as loop invariants they were hoisted out of the frame loop and kept in ~80 scalar
+                    // registers for its whole length (spilled to vector lanes, those to scratch: 232 B per lane).
+                    const MortarStepArgs MG_KERNARG_AS* ka = kernarg_reread<MortarStepArgs>();
+                    int i = (env >> 6) * 64 + lane;
+                    asm volatile("" : "+v"(i));  // (nor may what the step derives from `i` be computed at the head of every frame)
+                    if (i < n) mortar_step_body<true, false, false, FINAL>(i, *(const MortarStepArgs*)ka, epoch);
+                    if (lane == 0) atomicAdd(rescues, 1u);
+                    continue;
+                }
+            }
+            __builtin_amdgcn_s_sleep(4);
+        }
+        asm volatile("" ::: "memory");  // the loads below stay behind the observation of the epoch
+        w[0] = __hip_atomic_load(src + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        w[1] = __hip_atomic_load(src + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        w[2] = __hip_atomic_load(src + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        MortarDesc d;
+        memcpy(&d, w, sizeof(d));
+        if constexpr (FINAL) {
+            if (d.ring_on) {  // the instance finished in this step: its terminal frame first, into the caller's final-observation buffer
+                // (a.tdesc[env] was published in front of the descriptor whose epoch has just been observed)
+                const uint32_t* tsrc = reinterpret_cast<const uint32_t*>(a.tdesc + env);
+                uint32_t tw[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) tw[k] = __hip_atomic_load(tsrc + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                MortarDesc td;
+                memcpy(&td, tw, sizeof(td));
+                int tt = tid;
+                asm volatile("" : "+v"(tt));
+                R.tid = tt;
+                MortarComposer::compose(&td, R);
+                __syncthreads();
+                store_frame<MG_OBS_U8_XYC, false>(smem, a.info.final_obs_dev, env, tt);
+                __syncthreads();
+            }
+        }
+        if (MortarComposer::skip(&d)) continue;
+        // the lane's frame offsets are derived from an opaque copy of its index, i.e. inside the iteration: as loop invariants
+        // they were live across the (rare) step code above, which needs every register the kernel has
+        int t = tid;
+        asm volatile("" : "+v"(t));
+        R.tid = t;
+        MortarComposer::compose(&d, R);
+        __syncthreads();
+        store_frame<MG_OBS_U8_XYC, false>(smem, obs, env, t);  // (plain stores: non-temporal ones 281 -> 226-241 M at 65,536, round 4)
+        __syncthreads();
+    }
+    if constexpr (DONE_FLAG) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");  // this wave's stores (the frame; after a rescue also the step's results) are performed system-wide
+        __syncthreads();
+        if (tid == 0) __hip_atomic_store(done_flag, done_ticket, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+}  // namespace mg

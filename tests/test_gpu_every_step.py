@@ -6,7 +6,7 @@ arrangement bench.py measures (pinned to the oracle by tests/test_gpu_full_batch
 
 Round 6: this is how a race of the round-4 fused spotlight launch was found (tools/vector_soak.py) -- a reset frame drawn from the old or a
 half-written descriptor, one frame in ~10^7, which frames compared every 20th step of a 200-step run meet with a probability of a few
-per cent per run (csrc/mg_spot.hip spot_raster_serve_kernel: scalar loads behind vector stores of the same workgroup)."""
+per cent per run (csrc/mg_spot_serve.hpp spot_raster_serve_kernel: scalar loads behind vector stores of the same workgroup)."""
 import pytest
 
 pytestmark = pytest.mark.gpu

@@ -1,4 +1,4 @@
-"""GPU (-m gpu): the mortar family's one-launch step (csrc/mg_mortar.hip mortar_step_raster_kernel) never shows a stale frame.
+"""GPU (-m gpu): the mortar family's one-launch step (csrc/mg_mortar_one_launch.hpp mortar_step_raster_kernel) never shows a stale frame.
 
 The reference's step() returns the frame of THIS step, always (mortar_mayhem_grid.py:280-375).  In the one launch a frame's
 workgroup waits for the descriptor the step's workgroups of the same launch publish; since round 4 a frame wave that waits

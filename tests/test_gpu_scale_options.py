@@ -101,7 +101,7 @@ def test_debug_view_with_large_sprites(env_id, opts):
 def test_stale_exits_keep_the_size_they_were_made_with():
     """use_exit = False keeps the instance's EARLIER exit on screen (searing_spotlights.py:431-435) -- an object of its own in the
     reference, so it keeps its size when exit_scale changes meanwhile.  The handle holds one pair of exit stamps per size still on
-    some screen (csrc/mg_spot.hip: exit generations); a checkpoint carries them."""
+    some screen (csrc/mg_spot_types.hpp: exit generations); a checkpoint carries them."""
     import memory_gym_amd
     import oracle_lib
     from memory_gym_amd.reset_params import process_reset_params

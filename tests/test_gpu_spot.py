@@ -171,7 +171,7 @@ def test_scale_options(env_id, opts):
 @pytest.mark.parametrize("n", [700, 3000])
 def test_every_instance_truncated_in_the_same_step(n):
     """The fused raster / reset launch takes as few resets per serving workgroup as serve the queue in one round (1 .. 8, chosen in
-    the kernel from the queue's length: csrc/mg_spot.hip SpotServeArgs): with max_steps = 9 every instance is truncated in steps 9,
+    the kernel from the queue's length: csrc/mg_spot_types.hpp SpotServeArgs): with max_steps = 9 every instance is truncated in steps 9,
     18 and 27 -- n resets at once, two and eight per workgroup, several rounds for the larger batch."""
     run_parity("SearingSpotlights-v0", dict(max_steps=9), n=n, steps=30, check_every=3)
 
@@ -179,7 +179,7 @@ def test_every_instance_truncated_in_the_same_step(n):
 @pytest.mark.parametrize("env_id", ["SearingSpotlights-v0", "Endless-SearingSpotlights-v0"])
 @pytest.mark.parametrize("count", [1, 2, 3, 4, 5])
 def test_reset_spotlights_from_one_batch_of_outputs(env_id, count):
-    """new_spots_at_reset (csrc/mg_spot.hip): a reset's `initial_spawns` spotlights come from the generator's next 16 outputs at once
+    """new_spots_at_reset (csrc/mg_spot_logic.hpp): a reset's `initial_spawns` spotlights come from the generator's next 16 outputs at once
     (PCG64 jump-ahead across the instance's 16 lanes), and which half of which output feeds which draw depends on whether the stream
     arrives with a buffered 32-bit half.  Both layouts, every count the batch form takes (1..5): with `sample_agent_position` on, the
     seeded reset draws one more 32-bit number in front of the spotlights than with it off, so the two settings reach the spotlights in
