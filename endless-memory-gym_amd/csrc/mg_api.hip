@@ -119,7 +119,7 @@ void destroy_family(mg_env* e) {
     e->fam = nullptr;
 }
 size_t obs_bytes_of(int f) {
-    const size_t elem = f == MG_OBS_F32_CYX ? 4 : ((f == MG_OBS_F16_CYX || f == MG_OBS_BF16_CYX) ? 2 : 1);
+    const size_t elem = f == MG_OBS_F32_CYX ? 4 : ((f == MG_OBS_F16_CYX || f == MG_OBS_BF16_CYX) ? 2 : 1);  // (MG_OBS_U8_XYC, MG_OBS_U8_CYX: one byte)
     return elem * 84 * 84 * 3;
 }
 }  // namespace
@@ -234,7 +234,7 @@ int64_t mg_capacity(mg_env* env, const char* what) {
 
 int mg_set_obs_format(mg_env* env, int format) {
     return guarded(env, [&] {
-        if (format != MG_OBS_U8_XYC && format != MG_OBS_F32_CYX && format != MG_OBS_F16_CYX && format != MG_OBS_BF16_CYX)
+        if (format != MG_OBS_U8_XYC && format != MG_OBS_F32_CYX && format != MG_OBS_F16_CYX && format != MG_OBS_BF16_CYX && format != MG_OBS_U8_CYX)
             throw mg::OptionError{-3, "mg_set_obs_format: unknown format"};
         env->obs_format = env->fam->obs_format = format;
     });

@@ -28,12 +28,20 @@ inline void with_bool(bool flag, F&& f) {
     else f(std::false_type{});
 }
 
-// the four stream-out formats of include/memgym.h (anything else: the uint8 frame, as the kernels' own default)
+// the five stream-out formats of include/memgym.h (anything else: the uint8 frame, as the kernels' own default)
 template <typename F>
 inline void with_obs_format(int fmt, F&& f) {
     if (fmt == MG_OBS_F32_CYX) f(std::integral_constant<int, MG_OBS_F32_CYX>{});
     else if (fmt == MG_OBS_BF16_CYX) f(std::integral_constant<int, MG_OBS_BF16_CYX>{});
     else if (fmt == MG_OBS_F16_CYX) f(std::integral_constant<int, MG_OBS_F16_CYX>{});
+    else if (fmt == MG_OBS_U8_CYX) f(std::integral_constant<int, MG_OBS_U8_CYX>{});
+    else f(std::integral_constant<int, MG_OBS_U8_XYC>{});
+}
+
+// the one-byte formats alone (what the mortar family's one-launch step is instantiated for); the caller has checked that fmt is one
+template <typename F>
+inline void with_one_byte_format(int fmt, F&& f) {
+    if (fmt == MG_OBS_U8_CYX) f(std::integral_constant<int, MG_OBS_U8_CYX>{});
     else f(std::integral_constant<int, MG_OBS_U8_XYC>{});
 }
 

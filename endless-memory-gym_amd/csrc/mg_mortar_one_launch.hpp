@@ -6,7 +6,7 @@
 
 namespace mg {
 using namespace v1;  // raster generation 1 (see mg_raster_v1.hpp)
-// ONE launch per step (uint8 observations).  `logic_wgs` workgroups of the grid run the step (one lane per instance), all others
+// ONE launch per step (the one-byte observation formats: FMT = MG_OBS_U8_XYC or MG_OBS_U8_CYX, mg_stream_out.hpp).  `logic_wgs` workgroups of the grid run the step (one lane per instance), all others
 // are the raster's persistent workgroups; a frame's workgroup waits for ITS descriptor -- the epoch in the descriptor's last
 // word, read at agent scope past the caches -- instead of for the slowest wave of a separate logic launch plus that launch's
 // fixed cost: the first frames leave ~8 us earlier (MortarMayhem-Grid 65,536: 233 -> 224 us per step, 281 -> 292 M env-steps/s;
@@ -41,7 +41,8 @@ constexpr unsigned long long RESCUE_AFTER_TICKS = 20000;  // 200 us
 // operation behind the launch, 4.5 us less than hipStreamSynchronize (tools/microbench/launch_wait.hip).  Everything else the host reads
 // (reward, done, the episode record) was stored by the step's wave BEFORE it published the descriptor this workgroup waited for.
 // FINAL: the call keeps terminal observations (see mortar_step_body) -- a kernel of its own, the measured one (FINAL = false) is as it was.
-template <bool DONE_FLAG, bool FINAL = false>
+// FMT: the stream-out format of both frames.  MG_OBS_U8_CYX has the plain and the FINAL form (no DONE_FLAG one: mg_single_step waits for the stream).
+template <bool DONE_FLAG, bool FINAL = false, int FMT = MG_OBS_U8_XYC>
 __global__ __launch_bounds__(256, 7) void mortar_step_raster_kernel(MortarStepArgs a, int logic_wgs, int logic_base, uint32_t epoch,
                                                                     uint32_t ticket, uint32_t* claims, uint32_t* rescues,
                                                                     RasterAtlas A, void* __restrict__ obs, uint32_t* done_flag, uint32_t done_ticket) {
@@ -119,7 +120,7 @@ __global__ __launch_bounds__(256, 7) void mortar_step_raster_kernel(MortarStepAr
                 R.tid = tt;
                 MortarComposer::compose(&td, R);
                 __syncthreads();
-                store_frame<MG_OBS_U8_XYC, false>(smem, a.info.final_obs_dev, env, tt);
+                store_frame<FMT, false>(smem, a.info.final_obs_dev, env, tt);
                 __syncthreads();
             }
         }
@@ -131,7 +132,7 @@ __global__ __launch_bounds__(256, 7) void mortar_step_raster_kernel(MortarStepAr
         R.tid = t;
         MortarComposer::compose(&d, R);
         __syncthreads();
-        store_frame<MG_OBS_U8_XYC, false>(smem, obs, env, t);  // (plain stores: non-temporal ones 281 -> 226-241 M at 65,536, round 4)
+        store_frame<FMT, false>(smem, obs, env, t);  // (plain stores: non-temporal ones 281 -> 226-241 M at 65,536, round 4)
         __syncthreads();
     }
     if constexpr (DONE_FLAG) {

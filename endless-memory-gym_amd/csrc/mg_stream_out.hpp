@@ -6,6 +6,9 @@
 //   MG_OBS_U8_XYC    1,323 x 16-byte stores, lane-contiguous (1 KiB per wave instruction), the headline format;
 //   MG_OBS_F32_CYX / MG_OBS_F16_CYX / MG_OBS_BF16_CYX   value / 255 in image order [c][y][x]: the
 //                    transpose is done LDS-side (byte gathers, stride 252 B), the global stores stay 16-byte vectors.
+//   MG_OBS_U8_CYX    the same bytes in image order [c][y][x]: the frame is transposed IN PLACE in LDS (frame_to_cyx below: dword
+//                    reads, v_perm_b32, dword writes; no second frame buffer), then leaves through the uint8 format's own 1,323 x 16-byte
+//                    stores.  The LDS frame is no longer [x][y][c] afterwards: every composer redraws the whole frame, none reads the last one.
 // NT (uint8 format only): non-temporal stores.  A measured choice, not a taste: a non-temporal stream does not displace the
 // logic kernel's state from the caches (spotlight family at 65,536 instances: logic kernel 38 vs 48 us) but is itself slower
 // than a plain one (16,384 frames: 63 vs 60 us); the mortar frames (generation 1) lose 40 % with it
@@ -54,9 +57,68 @@ __device__ __forceinline__ float byte_to_unit(uint8_t b) {
     return __fmaf_rn(__fmaf_rn(-q0, 255.0f, v), r, q0);
 }
 
+// MG_OBS_U8_CYX: the LDS frame [x][y][c] -> [c][y][x], in place.  Each output dword is four bytes of four neighbouring columns at one
+// in-column offset 3 y + c, so a lane takes a 4-column x 12-byte block (x = 4 xg .. 4 xg + 3, y = 4 k .. 4 k + 3, all three channels): twelve
+// dword reads, three 4x4 byte transposes of eight v_perm_b32 each, twelve dword writes -- a byte is read once, and the vector unit spends two
+// instructions per output dword where a byte gather spends four reads and three packs.  21 x 21 = 441 blocks; all 256 lanes hold theirs in
+// registers (two rounds, 24 dwords) across a barrier, because a block's twelve dwords land all over the frame.
+// Banks (32 of them for ds_read_b32 / ds_write_b32, conflicts within a 32-lane half): a read's dword address is 63 (4 xg + i) + 3 k + m, i.e.
+// bank 3 k - 4 xg + const; a write's is 21 (84 c + 4 k + j) + xg, i.e. bank 20 k + xg + const.  Lanes are dealt 8 k x 4 xg per half
+// (slot u = 168 (k / 8) + 8 xg + k % 8; 504 slots, k < 21 in use): 20 k + xg then takes 32 different values -- the writes are
+// conflict-free but for a few 2-way halves where a half-wave straddles two k tiles -- and 3 k - 4 xg repeats only for
+// (k, xg) ~ (k + 4, xg + 3): four 2-way pairs per half.  Counted over a frame with the rule above (tools/lds_bank_count.py; derived from
+// the addresses, no counter run stands behind it): 192 half-wave reads + 192 extra cycles, 192 half-wave writes + 36 (none beyond 2-way).
+// With k or xg alone along the lanes one side is 3-way throughout (20 k and 4 xg take 8 values each): 168 + 324 extra cycles.  The byte
+// gather of the float formats, asked for 16-byte chunks of this format, would be 672 half-wave reads + 1,440 extra cycles
+// (profiles/u8_chw.md).
+// Why no lane is masked (below): with idle lanes in the second round the compiler kept more scalar state across the barrier and the FINAL
+// form of the mortar one-launch step reported a private segment; giving every lane a block, duplicates included, keeps it at 0 bytes.
+__device__ __forceinline__ void frame_to_cyx(uint8_t* frame, int tid) {
+    uint32_t* const w = reinterpret_cast<uint32_t*>(frame);
+    constexpr int COL_DW = COL_BYTES / 4, ROW_DW = SCREEN / 4;  // 63 dwords per [x] column before, 21 per (c, y) row after
+    constexpr int K_BLOCKS = SCREEN / 4, SLOTS = ((K_BLOCKS + 7) / 8) * 8 * ROW_DW;  // 21 blocks of four y; 504 lane slots
+    static_assert(COL_BYTES % 12 == 0 && SCREEN % 4 == 0 && SLOTS <= 2 * 256, "4-column x 12-byte blocks, two rounds of 256 lanes");
+    uint32_t t[2][12];
+    int at[2];  // dword of the block's (c = 0, j = 0) output
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        // No lane is ever masked: a slot with k = 21 .. 23 takes block k - 5 of its own half-wave (the same addresses: a broadcast read, the
+        // same dwords stored twice), the eight lanes past the last slot take their first block again.
+        const int u1 = tid + 256 * r, u = u1 < SLOTS ? u1 : tid;
+        const int kt = u / (8 * ROW_DW), rem = u - kt * (8 * ROW_DW), k1 = kt * 8 + (rem & 7);
+        const int xg = rem >> 3, k = k1 < K_BLOCKS ? k1 : k1 - 5;
+        at[r] = 4 * k * ROW_DW + xg;
+        const uint32_t* src = w + 4 * xg * COL_DW + 3 * k;
+#pragma unroll
+        for (int m = 0; m < 3; ++m) {
+            const uint32_t c0 = src[m], c1 = src[COL_DW + m], c2 = src[2 * COL_DW + m], c3 = src[3 * COL_DW + m];
+            // v_perm_b32 D, S0, S1, sel: selector bytes 0-3 pick from S1, 4-7 from S0
+            const uint32_t lo01 = __builtin_amdgcn_perm(c1, c0, 0x05010400u), hi01 = __builtin_amdgcn_perm(c1, c0, 0x07030602u);
+            const uint32_t lo23 = __builtin_amdgcn_perm(c3, c2, 0x05010400u), hi23 = __builtin_amdgcn_perm(c3, c2, 0x07030602u);
+            t[r][4 * m + 0] = __builtin_amdgcn_perm(lo23, lo01, 0x05040100u);  // in-column byte 4 m + b of columns 0..3
+            t[r][4 * m + 1] = __builtin_amdgcn_perm(lo23, lo01, 0x07060302u);
+            t[r][4 * m + 2] = __builtin_amdgcn_perm(hi23, hi01, 0x05040100u);
+            t[r][4 * m + 3] = __builtin_amdgcn_perm(hi23, hi01, 0x07060302u);
+        }
+    }
+    __syncthreads();  // every block is in registers: the frame may be overwritten
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+#pragma unroll
+        for (int o = 0; o < 12; ++o) w[at[r] + ((o % 3) * SCREEN + o / 3) * ROW_DW] = t[r][o];  // in-column byte o = 3 j + c -> row 84 c + 4 k + j
+    }
+    __syncthreads();
+}
+
+// Every format reads the frame only and may be called by any lane on its own, EXCEPT MG_OBS_U8_CYX: that one is a collective call of a
+// workgroup of exactly 256 threads (tid = 0 .. 255) from workgroup-uniform flow -- it holds two barriers -- and it DESTROYS the frame
+// (hence the non-const pointer): the caller composes the whole frame again before it reads a byte of it.
 template <int FMT, bool NT, bool BUF = false>
-__device__ __forceinline__ void store_frame(const uint8_t* __restrict__ frame, void* __restrict__ obs, int env, int tid) {
-    if constexpr (FMT == MG_OBS_U8_XYC && BUF) {
+__device__ __forceinline__ void store_frame(uint8_t* __restrict__ frame, void* __restrict__ obs, int env, int tid) {
+    if constexpr (FMT == MG_OBS_U8_CYX) {  // then out like the uint8 frame, which it is: one byte per element, 1,323 vectors
+        frame_to_cyx(frame, tid);
+        store_frame<MG_OBS_U8_XYC, NT, BUF>(frame, obs, env, tid);
+    } else if constexpr (FMT == MG_OBS_U8_XYC && BUF) {
         const u32x4* lds16 = reinterpret_cast<const u32x4*>(frame);
         // raw buffer over this frame only: stride 0, FRAME_BYTES records, dword 3 = 32-bit untyped data (gfx9 encoding)
         __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(static_cast<uint8_t*>(obs) + (size_t)env * OBS_STRIDE_U8, 0, FRAME_BYTES, 0x00020000);

@@ -126,7 +126,8 @@ class VecMemoryGym:
     metadata = {"render_modes": ["rgb_array", "debug_rgb_array"], "render_fps": 25}
 
     OBS_FORMATS = {"u8_xyc": (0, torch.uint8, (84, 84, 3)), "f32_chw": (1, torch.float32, (3, 84, 84)),
-                   "f16_chw": (2, torch.float16, (3, 84, 84)), "bf16_chw": (3, torch.bfloat16, (3, 84, 84))}
+                   "f16_chw": (2, torch.float16, (3, 84, 84)), "bf16_chw": (3, torch.bfloat16, (3, 84, 84)),
+                   "u8_chw": (4, torch.uint8, (3, 84, 84))}
 
     def __init__(self, env_id, num_envs=1, device=None, render_mode=None, obs_format="u8_xyc", final_observation=False,
                  obs_buffer=None, obs_placement=None, ground_truth64=False, on_capacity="raise", capacity=None):
@@ -160,7 +161,8 @@ class VecMemoryGym:
         self.action_space, self.observation_space, self.ground_truth_space = _spaces(self.action_dim, self.gt_dim, self.vec_dim)
         N, dev = self.num_envs, self.device
         # "u8_xyc" is the reference's observation; "f32_chw"/"f16_chw" are obs/255 in [c][y][x] order, converted inside
-        # the raster kernel's stream-out (what a trainer would otherwise compute from the uint8 frame every step)
+        # the raster kernel's stream-out (what a trainer would otherwise compute from the uint8 frame every step); "u8_chw" is the
+        # reference's bytes in [c][y][x] order: obs[i, c, y, x] == u8_xyc obs[i, x, y, c] -- a uint8 rollout buffer in image order
         self.obs_format = obs_format
         code, dt, shape = self.OBS_FORMATS[obs_format]
         _native.check(_native.LIB.mg_set_obs_format(h, code), "mg_set_obs_format")
@@ -475,6 +477,8 @@ class VecMemoryGym:
         mg_render_debug)."""
         if self.render_mode == "debug_rgb_array":
             return self.render_debug()
+        if self.obs_format == "u8_chw":
+            return self.obs.permute(0, 2, 3, 1)
         if self.obs_format != "u8_xyc":
             return (self.obs.permute(0, 2, 3, 1).float() * 255.0).round().to(torch.uint8)
         return self.obs.permute(0, 2, 1, 3)

@@ -43,10 +43,11 @@ typedef struct mg_info_buffers {
     /* Optional (gymnasium 0.29 VectorEnv convention, info["final_observation"]): with autoreset != 0 and this pointer
      * set, mg_step also writes the TERMINAL observation of every instance that finished in this call to row i of this
      * buffer (same format and shape as obs_dev; rows of other instances are left untouched) while obs_dev row i holds
-     * the first observation of the new episode.  uint8 observations, one option set: the step's own launches draw both frames (round 6;
+     * the first observation of the new episode.  MG_OBS_U8_XYC observations, one option set: the step's own launches draw both frames (round 6;
      * Endless-MysteryPath: the terminal frames by one sparse raster launch behind them) -- 0-4 % of a step for eight env ids, 11-12 % for
-     * SearingSpotlights-v0 and Endless-MysteryPath-v0.  Otherwise (float formats, per-instance option sets, the mortar family under graph
-     * capture): a step without auto-reset, the terminal rows copied, a masked reset whose frames a sparse raster launch draws. */
+     * SearingSpotlights-v0 and Endless-MysteryPath-v0; the mortar family does the same for MG_OBS_U8_CYX (ONE launch per step).  Otherwise
+     * (float formats, MG_OBS_U8_CYX on the other two families, per-instance option sets, the mortar family under graph capture): a step
+     * without auto-reset, the terminal rows copied, a masked reset whose frames a sparse raster launch draws. */
     void* final_obs_dev;
     /* Optional: the step reward of every instance as the reference computes it -- a Python float, i.e. a double
      * (e.g. mortar_mayhem_grid.py:288-352) -- next to reward_dev's float32 rounding of it; [num_envs]. */
@@ -140,12 +141,20 @@ int64_t mg_capacity(mg_env* env, const char* what);
  *                                                         from the observation before its CNN; 84,672 B per instance
  *   MG_OBS_F16_CYX  float16 [num_envs][3][84 y][84 x]  -- the float32 quotient rounded to nearest-even half
  *   MG_OBS_BF16_CYX bfloat16 [num_envs][3][84 y][84 x] -- the float32 quotient rounded to nearest-even bfloat16
+ *   MG_OBS_U8_CYX   uint8   [num_envs][3][84 y][84 x]  -- the reference's bytes in image (CHW) order:
+ *                                                         out[i][c][y][x] == xyc[i][x][y][c]; 21,168 B per instance, the uint8
+ *                                                         rollout buffer a CNN trainer keeps (/ 255 goes into its first layer)
  * The conversion is fused into the raster kernel's stream-out (no second pass over HBM).  mg_obs_bytes returns the
- * bytes per instance of the current format. */
+ * bytes per instance of the current format.
+ * Which arrangements a format takes: the mortar family's one-launch step (and its form that keeps terminal observations) runs for
+ * both one-byte formats, MG_OBS_U8_XYC and MG_OBS_U8_CYX.  The fused launches of the spotlight and Mystery Path families (deferred
+ * resets, served queues, terminal frames drawn by the step's own launches) exist for MG_OBS_U8_XYC alone: there MG_OBS_U8_CYX takes
+ * the paths of the float formats. */
 #define MG_OBS_U8_XYC 0
 #define MG_OBS_F32_CYX 1
 #define MG_OBS_F16_CYX 2
 #define MG_OBS_BF16_CYX 3
+#define MG_OBS_U8_CYX 4
 int mg_set_obs_format(mg_env* env, int format);
 size_t mg_obs_bytes(const mg_env* env);
 
@@ -295,7 +304,7 @@ typedef struct mg_obs_alloc_info {
 } mg_obs_alloc_info;
 #define MG_OBS_SEARCH_DEFAULT ((size_t)-1)
 int mg_obs_alloc(int device, size_t bytes, size_t search_budget_bytes, void** out_dev, mg_obs_alloc_info* info);
-/* The same for a buffer whose observations are `frame_bytes` each (= mg_obs_bytes of the handle: 21,168 for MG_OBS_U8_XYC -- what
+/* The same for a buffer whose observations are `frame_bytes` each (= mg_obs_bytes of the handle: 21,168 for MG_OBS_U8_XYC and MG_OBS_U8_CYX -- what
  * mg_obs_alloc assumes --, 42,336 for the 16-bit formats, 84,672 for MG_OBS_F32_CYX).  A raster launch writes at fronts that are one
  * WINDOW = 14,336 observations apart, and the split that is fast is the one of the concurrently written fronts: pieces are dealt to the
  * zones window by window (neighbouring windows start in different zones, a window's pieces alternate).  For windows of about one
@@ -334,7 +343,8 @@ int mg_enable_peer_access(int device, int peer_device);
  * (finite Mystery Path: wave-ticks and paths of the A* generation inside the step's launches).  "emp_ahead_records"
  * (Endless-MysteryPath: first segments of NEXT episodes generated ahead of time, which a finishing instance's own step turns into its
  * reset -- EndlessMysteryPathEnv.reset, endless_mystery_path.py:195-280, without a queue entry); "emp_own_resets" (such resets; counted
- * by the lab build only).  Unknown name: -1.  Synchronous. */
+ * by the lab build only).  "one_launch_steps" (mortar family): mg_step calls of this handle that went out as the one-launch kernel, counted
+ * on the host.  Unknown name: -1.  Synchronous. */
 int mg_debug_counter(mg_env* env, const char* name, int64_t* value);
 
 /* Test hook: copy the numpy-compatible PCG64 words of instance i to host:

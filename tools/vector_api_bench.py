@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""tools/vector_api_bench.py [ENV_ID N STEPS] -- what the gymnasium-0.29 vector convention costs: env-steps/s through
+"""tools/vector_api_bench.py [ENV_ID N STEPS [OBS_FORMAT]] -- what the gymnasium-0.29 vector convention costs: env-steps/s through
 memory_gym_amd.vector.GymnasiumVectorEnv (terminal observations kept in infos["final_observation"], sub-environments reset in the same call)
-against VecMemoryGym.step with auto-reset (what bench.py measures), same instances, same uniform random actions, torch tensors throughout."""
+against VecMemoryGym.step with auto-reset (what bench.py measures), same instances, same uniform random actions, torch tensors throughout.
+OBS_FORMAT (default u8_xyc): the observation format of both legs (VecMemoryGym.OBS_FORMATS)."""
 import os
 import sys
 import time
@@ -16,6 +17,7 @@ from memory_gym_amd.vector import GymnasiumVectorEnv  # noqa: E402
 env_id = sys.argv[1] if len(sys.argv) > 1 else "MortarMayhem-Grid-v0"
 n = int(sys.argv[2]) if len(sys.argv) > 2 else 65536
 steps = int(sys.argv[3]) if len(sys.argv) > 3 else 300
+fmt = sys.argv[4] if len(sys.argv) > 4 else "u8_xyc"
 
 
 FOLLOW = os.environ.get("SOAK_POLICY") == "follower"  # ids whose ground truth names the way: the agent follows it (eps 0.02), episodes get long
@@ -49,5 +51,5 @@ def run(label, make, step):
     env.close()
 
 
-run("%s x %d, VecMemoryGym.step (auto-reset)" % (env_id, n), lambda: memory_gym_amd.make(env_id, num_envs=n, device=0), lambda e, a: e.step(a))
-run("... GymnasiumVectorEnv.step (final_observation)", lambda: GymnasiumVectorEnv(env_id, n, device=0), lambda e, a: e.step(a))
+run("%s x %d %s, VecMemoryGym.step (auto-reset)" % (env_id, n, fmt), lambda: memory_gym_amd.make(env_id, num_envs=n, device=0, obs_format=fmt), lambda e, a: e.step(a))
+run("... GymnasiumVectorEnv.step (final_observation)", lambda: GymnasiumVectorEnv(env_id, n, device=0, obs_format=fmt), lambda e, a: e.step(a))
