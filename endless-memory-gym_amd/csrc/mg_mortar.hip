@@ -8,10 +8,11 @@
 //   memory_gym/character_controller.py   free :89-146  grid :177-210  screen-wrap :226-283
 //   memory_gym/pygame_assets.py          Command :241-304  MortarTile/MortarArena :306-418
 //
+//   mg_mortar_handover.hpp    the 64-bit word that carries a frame descriptor from a step lane to a frame workgroup of the same launch (host-includable)
 //   mg_mortar_types.hpp       the variant constants; MortarParams, MortarState, MortarDesc, MortarIO, MortarStepArgs
 //   mg_mortar_compose.hpp     MortarComposer (the observation) and MortarDebugComposer, with the measurement hooks MG_LAB_NO_TEMPLATE / MG_LAB_NO_STAMPS
 //   mg_mortar_step.hpp        reset and step of one instance (mortar_reset, mortar_step_body); mortar_reset_kernel, mortar_step_kernel
-//   mg_mortar_one_launch.hpp  mortar_step_raster_kernel: the step as one launch, its claim / epoch hand-over, RESCUE_AFTER_TICKS
+//   mg_mortar_one_launch.hpp  mortar_step_raster_kernel: the step as one launch, its claim / hand-over word, RESCUE_AFTER_TICKS
 //
 // The launches of a step as shipped:
 //   ONE launch for one-byte observations (MG_OBS_U8_XYC, MG_OBS_U8_CYX) and one option set (mortar_step_raster_kernel: the step's workgroups lead the raster's grid and a frame waits for its own
@@ -128,10 +129,11 @@ class MortarFamily : public Family {
         state_.alloc(n);
         cmds_.alloc((size_t)n * P_.cmd_cap);
         desc_.alloc(n);
-        tdesc_.alloc(n);  // (terminal-frame descriptors of the FINAL one-launch step: 16 B per instance; allocated here so that no step allocates)
+        tdesc_.alloc(n);  // (terminal-frame words of the FINAL one-launch step: 8 B per instance; allocated here so that no step allocates)
         rng_.alloc(n);
         err_.alloc();
         claims_.alloc((size_t)((n + 255) / 256) * 4);
+        handover_.alloc(n);  // (zeroed: epoch 0 is never a one-launch epoch; transient within a launch, so no part of state_blobs())
         rescues_.alloc(1);
         sets_.alloc();
         launch(mortar_init_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, n, state_.p);
@@ -207,7 +209,7 @@ class MortarFamily : public Family {
         else if (endless && key == "reward_new_command_success") P.r_new = v[0];
         else if (!endless && key == "arena_size") {
             int a = A.integer();
-            if (a < 2 || a > 6) throw OptionError{-4, "assert 2 <= arena_size <= 6"};
+            if (a < 2 || a > MORTAR_MAX_N) throw OptionError{-4, "assert 2 <= arena_size <= 6"};  // (MORTAR_MAX_N: what the hand-over word's template field is checked against)
             if (a != P_.N) A.geometry(P_.N, a);  // (the one geometry key that asks for a rebuild only when its value changes)
         }
         else if (!endless && key == "command_count") O.st_command_count.set(P.command_count, A.int_list(1, P_.taskb ? VEC_DIM / 9 : P_.cmd_cap));
@@ -244,10 +246,10 @@ class MortarFamily : public Family {
         flag_stored_ = false;
         const mg_info_buffers ib = begin_step(info);
         sets_.upload(s);
-        const MortarStepArgs sa{P_, n_, io(), actions, reward, done, gt_dim() ? gt : nullptr, ib, autoreset, nullptr};
+        const MortarStepArgs sa{P_, n_, io(), actions, reward, done, gt_dim() ? gt : nullptr, ib, autoreset, handover_.p, nullptr};
         // one launch: mortar_step_raster_kernel (handles with ONE option set: the per-set step code reads its parameters from memory)
         if (one_byte_format() && fuse_step() && !sets_.per_set() && !capturing(s)) {
-            epoch_ = epoch_ % 255u + 1u;  // 1 .. 255: never the 0 a reset's (or the two-launch step's) descriptors carry
+            epoch_ = epoch_ % 255u + 1u;  // 1 .. 255: never the 0 of a fresh hand-over array (resets and two-launch steps do not write the words)
             ++ticket_;                    // claim words hold the ticket of the last one-launch step: never this one
             const int logic_wgs = (n_ + 255) / 256;
             const int frames = frames_grid(n_);
@@ -333,8 +335,8 @@ class MortarFamily : public Family {
     bool flag_stored_ = false;      // done_flag_stored
     int64_t one_launch_steps_ = 0;  // debug_counter("one_launch_steps")
     uint32_t ticket_ = 0;  // one-launch step: number of the step, the value a slot's claim word takes when a wave claims it
-    uint32_t epoch_ = 0;  // the one-launch step's descriptor epoch, 1 .. 255 (every step rewrites every descriptor, so the only stale
-                          // values a frame workgroup can meet are the previous step's and the 0 of a reset / two-launch step)
+    uint32_t epoch_ = 0;  // the one-launch step's hand-over epoch, 1 .. 255 (every one-launch step rewrites every word, so the only stale
+                          // values a frame workgroup can meet are the previous one-launch step's and the 0 of the fresh array)
     bool one_byte_format() const { return obs_format == MG_OBS_U8_XYC || obs_format == MG_OBS_U8_CYX; }  // what the one-launch step is instantiated for
     static bool fuse_step() {  // lab build: MEMGYM_MORTAR_FUSE=0 selects the two-launch form for A/B measurements
         static const bool on = lab_flag("MEMGYM_MORTAR_FUSE", true);
@@ -423,8 +425,9 @@ class MortarFamily : public Family {
     float* vec_ = nullptr;
     DevArray<MortarState> state_;
     DevArray<uint8_t> cmds_;
-    DevArray<MortarDesc> desc_, tdesc_;  // tdesc_: terminal-frame descriptors (FINAL form of the one-launch step)
+    DevArray<MortarDesc> desc_;
     DevArray<uint32_t> claims_, rescues_;  // one-launch step: one claim word per 64 instances; slots stepped by frame waves
+    DevArray<uint64_t> handover_, tdesc_;  // one-launch step: the hand-over word per instance (mg_mortar_handover.hpp); tdesc_: the terminal frames' (FINAL form)
 };
 
 Family* make_mortar(int variant, int num_envs) { return new MortarFamily(variant, num_envs); }

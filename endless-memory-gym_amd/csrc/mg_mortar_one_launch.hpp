@@ -7,7 +7,7 @@
 namespace mg {
 using namespace v1;  // raster generation 1 (see mg_raster_v1.hpp)
 // ONE launch per step (the one-byte observation formats: FMT = MG_OBS_U8_XYC or MG_OBS_U8_CYX, mg_stream_out.hpp).  `logic_wgs` workgroups of the grid run the step (one lane per instance), all others
-// are the raster's persistent workgroups; a frame's workgroup waits for ITS descriptor -- the epoch in the descriptor's last
+// are the raster's persistent workgroups; a frame's workgroup waits for ITS descriptor -- the epoch in the instance's hand-over
 // word, read at agent scope past the caches -- instead of for the slowest wave of a separate logic launch plus that launch's
 // fixed cost: the first frames leave ~8 us earlier (MortarMayhem-Grid 65,536: 233 -> 224 us per step, 281 -> 292 M env-steps/s;
 // 16,384: 69 -> 65 us; profiles/r03_one_launch.md).
@@ -23,10 +23,15 @@ using namespace v1;  // raster generation 1 (see mg_raster_v1.hpp)
 // gone).  tests/test_gpu_one_launch.py runs the launch with the step workgroups LAST in the grid (lab build) -- every frame
 // workgroup resident before any step workgroup -- and under a concurrent stream.
 //
-// Hand-over of the 16-byte descriptor: the publisher writes words 0..2 with agent-scope (write-through) stores, waits until they
-// have reached the coherence point (s_waitcnt vmcnt(0)) and only then writes word 3, which carries the epoch; the reader polls
-// word 3 with agent-scope loads and, once it shows the epoch, reads words 0..2 with agent-scope loads issued AFTER that
-// observation.  Release / acquire atomics would be the textbook form; at agent scope on gfx950 they write back / invalidate
+// Hand-over of the descriptor: ONE 64-bit word per instance (a.handover[i], layout in mg_mortar_handover.hpp: the fields the frame loop draws
+// from, and the epoch in the top byte).  Writer: the instance's step lane, one relaxed agent-scope (write-through) 64-bit store as soon as the
+// descriptor is known.  Reader: every wave of the frame's workgroup, relaxed agent-scope 64-bit loads until the epoch is this launch's; the
+// descriptor is built in scalar registers from that SAME value.  A naturally aligned 64-bit access is single-copy atomic, so the value that
+// shows the epoch is whole: no wait between words, no second load (until this form the descriptor went over as 3 + 1 words with an
+// s_waitcnt vmcnt(0) between them and was read in two round trips; profiles/handover_word.md).  The word orders nothing else, and in the
+// plain launch nothing else is handed over; the FINAL and <DONE_FLAG> forms keep one wait in front of it (mortar_step_body says for what).
+// io.desc[i] is still written, as one plain 16-byte store behind the word: LATER launches read it (two-launch raster, sparse raster, debug view).
+// Release / acquire atomics would be the textbook form; at agent scope on gfx950 they write back / invalidate
 // the whole L2 of the XCD around every hand-over (buffer_wbl2 / buffer_inv sc1), with the observation stream in that L2.
 // The two-launch form is used while a stream is being captured into a HIP graph (epoch and ticket are launch arguments: a
 // replay would find them satisfied already) and for handles with instance groups (their stagger needs the logic launch's end).
@@ -36,10 +41,19 @@ using namespace v1;  // raster generation 1 (see mg_raster_v1.hpp)
 // exchange at the few cache lines of claim words, and those ~7,000 serialised atomics cost the 16,384-instance launch 6 of
 // its 66 us (profiles/r04_one_launch.md).
 constexpr unsigned long long RESCUE_AFTER_TICKS = 20000;  // 200 us
+// What a frame workgroup draws from, rebuilt from the two dwords of a hand-over word (glyph_x0 is not in the word: the launch runs under ONE option set)
+__device__ __forceinline__ MortarDesc desc_from_handover(uint32_t lo, uint32_t hi, int glyph_x0) {
+    const Handover f = unpack_handover(lo, hi);
+    MortarDesc d;
+    d.sx = (int16_t)f.sx, d.sy = (int16_t)f.sy, d.tmpl = (uint16_t)f.tmpl, d.sprite = (uint8_t)f.sprite, d.glyph = (uint8_t)f.glyph;
+    d.glyph_x0 = (int16_t)glyph_x0;
+    d.ring_x = d.ring_y = 0, d.ring_on = (uint8_t)f.ring_on, d.reserved = 0;
+    return d;
+}
 // DONE_FLAG (the single-instance fast path, mg_single_step: ONE frame workgroup): when the frame is out, the workgroup stores `done_ticket`
 // to `done_flag` -- a word in the caller's pinned block that the host polls -- at system scope: 2.7 us less per step than a stream memory
 // operation behind the launch, 4.5 us less than hipStreamSynchronize (tools/microbench/launch_wait.hip).  Everything else the host reads
-// (reward, done, the episode record) was stored by the step's wave BEFORE it published the descriptor this workgroup waited for.
+// (reward, done, the episode record) was stored by the step's wave, and waited for (mortar_step_body<ORDERED>), BEFORE it published the word this workgroup waited for.
 // FINAL: the call keeps terminal observations (see mortar_step_body) -- a kernel of its own, the measured one (FINAL = false) is as it was.
 // FMT: the stream-out format of both frames.  MG_OBS_U8_CYX has the plain and the FINAL form (no DONE_FLAG one: mg_single_step waits for the stream).
 template <bool DONE_FLAG, bool FINAL = false, int FMT = MG_OBS_U8_XYC>
@@ -59,9 +73,9 @@ __global__ __launch_bounds__(256, 7) void mortar_step_raster_kernel(MortarStepAr
     if (is_logic) {  // a step workgroup: wave w steps slot 4 rel + w unless a frame wave got there first
         const int q = rel * 4 + (tid >> 6), i = q * 64 + lane;
 #if defined(MG_LABV) && MG_LABV >= 1
-        if (i < n) mortar_step_body<true, false, false, FINAL>(i, a, epoch);
+        if (i < n) mortar_step_body<true, false, false, FINAL, DONE_FLAG>(i, a, epoch);
 #else
-        if (i < n) mortar_step_body<true, true, false, FINAL>(i, a, epoch, claims + q, ticket);
+        if (i < n) mortar_step_body<true, true, false, FINAL, DONE_FLAG>(i, a, epoch, claims + q, ticket);
 #endif
         return;
     }
@@ -70,15 +84,17 @@ __global__ __launch_bounds__(256, 7) void mortar_step_raster_kernel(MortarStepAr
     const int stride = (int)gridDim.x - logic_wgs;
     for (int v = (int)blockIdx.x < logic_base ? (int)blockIdx.x : (int)blockIdx.x - logic_wgs; v < n; v += stride) {
         const int env = xcd_grouped_frame(v, n);
-        // every lane reads the same words (one transaction per wave); no barrier: the waves of a workgroup wait separately
-        const uint32_t* src = reinterpret_cast<const uint32_t*>(a.io.desc + env);
-        uint32_t w[4];
+        // every lane reads the same word (one transaction per wave); no barrier: the waves of a workgroup wait separately
+        const uint64_t* src = a.handover + env;
+        uint32_t lo, hi;
         bool tried = false;
         unsigned long long t0 = 0;
         for (int polls = 0;; ++polls) {
-            // (all lanes read the same word; readfirstlane tells the compiler so: the wait loop's control stays scalar)
-            w[3] = (uint32_t)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(src + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-            if ((w[3] >> 24) == epoch) break;
+            // (all lanes read the same word; readfirstlane tells the compiler so: the wait loop's control and the descriptor stay scalar)
+            const uint64_t w = __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)w);
+            hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(w >> 32));
+            if ((hi >> (HANDOVER_EPOCH_SHIFT - 32)) == epoch) break;
 #if defined(MG_LABV) && MG_LABV >= 2
             if (false) {
 #else
@@ -93,34 +109,28 @@ __global__ __launch_bounds__(256, 7) void mortar_step_raster_kernel(MortarStepAr
                     const MortarStepArgs MG_KERNARG_AS* ka = kernarg_reread<MortarStepArgs>();
                     int i = (env >> 6) * 64 + lane;
                     asm volatile("" : "+v"(i));  // (nor may what the step derives from `i` be computed at the head of every frame)
-                    if (i < n) mortar_step_body<true, false, false, FINAL>(i, *(const MortarStepArgs*)ka, epoch);
+                    if (i < n) mortar_step_body<true, false, false, FINAL, DONE_FLAG>(i, *(const MortarStepArgs*)ka, epoch);
                     if (lane == 0) atomicAdd(rescues, 1u);
                     continue;
                 }
             }
-            __builtin_amdgcn_s_sleep(4);
+            __builtin_amdgcn_s_sleep(4);  // (1 and 2 measured no better: profiles/handover_word.md)
         }
-        asm volatile("" ::: "memory");  // the loads below stay behind the observation of the epoch
-        w[0] = __hip_atomic_load(src + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        w[1] = __hip_atomic_load(src + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        w[2] = __hip_atomic_load(src + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        MortarDesc d;
-        memcpy(&d, w, sizeof(d));
+        // the descriptor, from the SAME 64-bit value that showed the epoch: no second load, nothing to order
+        const MortarDesc d = desc_from_handover(lo, hi, a.P.glyph_x0);
         if constexpr (FINAL) {
             if (d.ring_on) {  // the instance finished in this step: its terminal frame first, into the caller's final-observation buffer
-                // (a.tdesc[env] was published in front of the descriptor whose epoch has just been observed)
-                const uint32_t* tsrc = reinterpret_cast<const uint32_t*>(a.tdesc + env);
-                uint32_t tw[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) tw[k] = __hip_atomic_load(tsrc + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                MortarDesc td;
-                memcpy(&td, tw, sizeof(td));
+                // (a.tdesc[env] had reached the coherence point before the word that has just been observed left its lane)
+                // (both pointers re-read from the kernel-argument segment, like the rescue's arguments: held across the frame loop they cost it scratch)
+                const MortarStepArgs MG_KERNARG_AS* ka = kernarg_reread<MortarStepArgs>();
+                const uint64_t tw = __hip_atomic_load(ka->tdesc + env, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                const MortarDesc td = desc_from_handover((uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)tw), (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(tw >> 32)), a.P.glyph_x0);
                 int tt = tid;
                 asm volatile("" : "+v"(tt));
                 R.tid = tt;
                 MortarComposer::compose(&td, R);
                 __syncthreads();
-                store_frame<FMT, false>(smem, a.info.final_obs_dev, env, tt);
+                store_frame<FMT, false>(smem, ka->info.final_obs_dev, env, tt);
                 __syncthreads();
             }
         }

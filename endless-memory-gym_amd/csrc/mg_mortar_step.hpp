@@ -148,16 +148,17 @@ __global__ __launch_bounds__(256) void mortar_reset_kernel(MortarParams P0, int 
 }
 
 // The step of instance i.  FUSED (the one-launch step, mortar_step_raster_kernel): the RNG stream is read where it is drawn
-// (ten registers less: that kernel must fit the raster's 72 VGPRs without scratch) and the descriptor is published for the
-// frame workgroups of the SAME launch: agent-scope (write-through) stores, the word that carries the epoch last.
+// (ten registers less: that kernel must fit the raster's 72 VGPRs without scratch) and the descriptor is handed to the
+// frame workgroups of the SAME launch in a.handover[i]: one agent-scope (write-through) 64-bit store that carries the epoch.
 // CLAIM (the step workgroups of the one-launch step): the wave steps its 64 instances only if it is the first to exchange this
 // step's ticket into `claim_word` (see mortar_step_raster_kernel).  The exchange is ISSUED first and its answer awaited together
 // with the state record: as a round trip of its own in front of the loads it delayed every descriptor, i.e. the whole launch,
 // by 5-8 us (16,384 instances: 65 -> 73 us).
 // FINAL (the one-launch step of a call that keeps terminal observations, mg_info_buffers.final_obs_dev): an instance that finishes
-// publishes the descriptor of its TERMINAL frame in a.tdesc[i] before it resets, and says so in the reset frame's descriptor (ring_on, a
-// field only the debug view uses otherwise): the frame workgroup draws the terminal frame into final_obs_dev first.
-template <bool FUSED, bool CLAIM = false, bool PS = false, bool FINAL = false>
+// publishes the descriptor of its TERMINAL frame in a.tdesc[i] (a word of the same layout) before it resets, and says so in the reset frame's
+// hand-over word (ring_on, a field only the debug view uses otherwise): the frame workgroup draws the terminal frame into final_obs_dev first.
+// ORDERED: every store of the lane in front of the hand-over word is complete before the word leaves (see there).
+template <bool FUSED, bool CLAIM = false, bool PS = false, bool FINAL = false, bool ORDERED = false>
 __device__ __forceinline__ void mortar_step_body(int i, const MortarStepArgs& a, uint32_t epoch, uint32_t* claim_word = nullptr,
                                                  uint32_t ticket = 0u) {
     uint32_t claimed_by = 0u;
@@ -375,23 +376,11 @@ __device__ __forceinline__ void mortar_step_body(int i, const MortarStepArgs& a,
     memset(&d, 0, sizeof(d));
     d.glyph_x0 = (int16_t)P.glyph_x0;
     if (done && autoreset) {
-        if constexpr (FINAL) {  // the terminal frame's descriptor (the else branch below), published like the frame descriptor's first words
-            MortarDesc td;
-            memset(&td, 0, sizeof(td));
-            td.glyph_x0 = (int16_t)P.glyph_x0;
+        if constexpr (FINAL) {  // the terminal frame (the else branch below) as a hand-over word of its own, epoch 0: read only behind ring_on
             const int tcx = s.disp_is_agent ? s.ax : s.disp_x, tcy = s.disp_is_agent ? s.ay : s.disp_y;
-            td.sx = (int16_t)(tcx - P.sprite_dim / 2);
-            td.sy = (int16_t)(tcy - P.sprite_dim / 2);
-            td.sprite = s.disp_sprite;
-            td.glyph = glyph;
-            td.tmpl = (uint16_t)((s.tiles_on && P.visual_feedback) ? 1 + s.tx * P.N + s.ty : 0);
-            uint32_t tw[4];
-            memcpy(tw, &td, sizeof(tw));
-            uint32_t* tdst = reinterpret_cast<uint32_t*>(&a.tdesc[i]);
-            __hip_atomic_store(tdst + 0, tw[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(tdst + 1, tw[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(tdst + 2, tw[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(tdst + 3, tw[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // (all four in front of the wait below)
+            const uint64_t tw = pack_handover(tcx - P.sprite_dim / 2, tcy - P.sprite_dim / 2, (s.tiles_on && P.visual_feedback) ? 1 + s.tx * P.N + s.ty : 0,
+                                              0, s.disp_sprite, glyph, 0);
+            __hip_atomic_store(a.tdesc + i, tw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         if (!rng_loaded) g.load(io.rng, i);
         rng_loaded = true;
@@ -410,21 +399,19 @@ __device__ __forceinline__ void mortar_step_body(int i, const MortarStepArgs& a,
             gt[2 * i + 1] = (float)(s.ty / 5.0);
         }
     }
+    if constexpr (FUSED) {
+        // The hand-over: ONE relaxed agent-scope (write-through) 64-bit store, as soon as the descriptor is known -- the frame wave polls this word
+        // and takes every field from the value that showed the epoch (a 64-bit access is single-copy atomic), so nothing has to precede it:
+        //   plain form      no wait.  In that launch the frame wave reads nothing else this lane wrote (templates and stamps are the handle's).
+        //   FINAL           a.tdesc[i] has reached the coherence point before the word whose ring_on announces it: s_waitcnt vmcnt(0) between the two.
+        //   ORDERED         (the <DONE_FLAG> launch) the host reads reward, done and the episode record once the frame workgroup has stored the flag,
+        //                   and that workgroup's release fence covers its OWN stores only: this lane's stores above are complete before the word leaves.
+        if constexpr (FINAL || ORDERED) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __hip_atomic_store(a.handover + i, pack_handover(d.sx, d.sy, d.tmpl, d.ring_on, d.sprite, d.glyph, epoch), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
     if (rng_used) g.store(io.rng, i);
     io.state[i] = s;
-    if constexpr (FUSED) {
-        d.epoch = (uint8_t)epoch;
-        uint32_t w[4];
-        memcpy(w, &d, sizeof(w));
-        uint32_t* dst = reinterpret_cast<uint32_t*>(&io.desc[i]);
-        __hip_atomic_store(dst + 0, w[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(dst + 1, w[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(dst + 2, w[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the three words have reached the coherence point before the fourth leaves
-        __hip_atomic_store(dst + 3, w[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    } else {
-        io.desc[i] = d;
-    }
+    io.desc[i] = d;  // (one plain 16-byte store: the two-launch raster, the sparse raster, mg_render and the debug view of LATER launches read it)
 }
 
 template <bool PS>

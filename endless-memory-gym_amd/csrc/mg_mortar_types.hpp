@@ -2,6 +2,7 @@
 // launches share -- MortarParams, the 64-byte MortarState, the 16-byte frame descriptor MortarDesc, MortarIO and MortarStepArgs.  Every other mg_mortar_*.hpp includes this one.
 #pragma once
 #include "mg_family.hpp"
+#include "mg_mortar_handover.hpp"
 #include "mg_raster_v1.hpp"
 
 namespace mg {
@@ -56,8 +57,7 @@ struct __attribute__((aligned(16))) MortarDesc {
     int16_t glyph_x0;  // blit position of the glyph (x == y)
     int16_t ring_x, ring_y;  // debug view only: top-left of the target ring stamp
     uint8_t ring_on;
-    uint8_t epoch;     // one-launch step (mortar_step_raster_kernel): the step this descriptor belongs to, mod 256; the LAST
-                       // byte of the record, so that the word that carries it can be published last
+    uint8_t reserved;  // (0; the one-launch step's epoch until that step got a hand-over word of its own, mg_mortar_handover.hpp)
 };
 static_assert(sizeof(MortarDesc) == 16, "MortarDesc must be 16 bytes");
 constexpr int STAMP_SPRITE0 = 0, STAMP_GLYPH0 = 8, STAMP_RING = 18;
@@ -88,6 +88,10 @@ struct MortarStepArgs {
     float* gt;
     mg_info_buffers info;
     int autoreset;
-    MortarDesc* tdesc;  // FINAL form of the one-launch step (terminal observations kept): [N] descriptors of the terminal frames
+    uint64_t* handover;  // one-launch step: [N] hand-over words (mg_mortar_handover.hpp), step lane -> frame workgroup of the same launch
+    uint64_t* tdesc;     // FINAL form of the one-launch step (terminal observations kept): [N] words of the terminal frames (same layout, epoch 0)
 };
+// Largest arena the host accepts (arena_size, Endless: 6): template indices are 1 + tx * N + ty <= N * N, far inside the hand-over word's 15 bits
+constexpr int MORTAR_MAX_N = 6;
+static_assert(MORTAR_MAX_N * MORTAR_MAX_N <= (int)HANDOVER_TMPL_MAX, "a template index the host accepts does not fit the hand-over word");
 }  // namespace mg
