@@ -605,4 +605,15 @@ int mg_debug_rng(mg_env* env, int32_t i, uint64_t* out) {
     });
 }
 
+int mg_debug_set_rng(mg_env* env, int32_t i, const uint64_t* in) {
+    return guarded(env, [&] {
+        if (i < 0 || i >= env->num_envs) throw std::runtime_error("mg_debug_set_rng: index out of range");
+        if (!in) throw std::runtime_error("mg_debug_set_rng: NULL");
+        if (!(in[3] & 1)) throw std::runtime_error("mg_debug_set_rng: a PCG64 increment is odd");
+        MG_HIP(hipDeviceSynchronize());
+        env->fam->sync_state();
+        env->fam->debug_set_rng(i, in);
+    });
+}
+
 }  // extern "C"

@@ -111,6 +111,14 @@ struct RngStore {
         out[4] = (b >> 32) & 1;
         out[5] = b & 0xFFFFFFFFull;
     }
+    void debug_set(int i, const uint64_t in[6]) {  // (the packing of Pcg::store, mg_device.hpp)
+        const uint64_t b = (in[5] & 0xFFFFFFFFull) | ((uint64_t)(in[4] ? 1 : 0) << 32);
+        MG_HIP(hipMemcpy(s_hi.p + i, &in[0], 8, hipMemcpyHostToDevice));
+        MG_HIP(hipMemcpy(s_lo.p + i, &in[1], 8, hipMemcpyHostToDevice));
+        MG_HIP(hipMemcpy(i_hi.p + i, &in[2], 8, hipMemcpyHostToDevice));
+        MG_HIP(hipMemcpy(i_lo.p + i, &in[3], 8, hipMemcpyHostToDevice));
+        MG_HIP(hipMemcpy(buf.p + i, &b, 8, hipMemcpyHostToDevice));
+    }
 };
 
 // Host side of an OptList (mg_device.hpp): packs the entries, owns the device copy of lists that do not fit the inline form.
@@ -243,6 +251,9 @@ class Family {
     // put off without changing any result (Endless Mystery Path: owed path segments) is done now.  Synchronous.
     virtual void sync_state() {}
     virtual void debug_rng(int i, uint64_t out[6]) { rng_.debug(i, out); }
+    // mg_debug_set_rng, after sync_state(): the instance's stream is replaced.  A family that holds anything computed ahead of time
+    // from the old stream drops it here (Endless Mystery Path: the record of the next episode's first segment).
+    virtual void debug_set_rng(int i, const uint64_t in[6]) { rng_.debug_set(i, in); }
     // info["ground_truth"] as the reference returns it -- float64 (e.g. endless_mortar_mayhem.py:259,358) -- of every instance,
     // [num_envs][gt_dim], computed from the CURRENT state (the float32 gt_dev of mg_step / mg_reset is its rounding); a small
     // launch of its own, only when a caller asks (mg_info_buffers.gt64_dev, mg_ground_truth64).  No-op for gt_dim() == 0.

@@ -403,6 +403,16 @@ class MysteryFamily : public Family {
             MG_HIP(hipDeviceSynchronize());
         }
     }
+    // (behind sync_state(): nothing is owed, nothing is in flight.)  A record generated ahead of time continued the OLD stream and carries
+    // that stream's state behind the segment: dropped, as the kernels do wherever the stream has moved (EMP_PRE, mg_mystery_endless.hpp)
+    void debug_set_rng(int i, const uint64_t in[6]) override {
+        Family::debug_set_rng(i, in);
+        if (!P_.endless) return;
+        MysteryCore c;
+        MG_HIP(hipMemcpy(&c, core_.p + i, sizeof c, hipMemcpyDeviceToHost));
+        EMP_PRE(c) = 0;
+        MG_HIP(hipMemcpy(core_.p + i, &c, sizeof c, hipMemcpyHostToDevice));
+    }
     void flush_owed(hipStream_t s) {
         launch_checked(emp_flush_owed_kernel, dim3((n_ + 63) / 64), dim3(64), LW_BYTES, s, P_, io());
         owed_possible_ = false;

@@ -67,7 +67,7 @@ __device__ __forceinline__ Pcg bcast(const Pcg& g, int lane) {
 }
 
 // ---- the instance's RNG stream, generated 64 outputs at a time by the whole wave ------------------------------------------
-// A path draws ~130 32-bit numbers; drawn one by one from wave-uniform state, every PCG64 step is a 128 x 128-bit multiply on
+// A path draws 40 - 100 32-bit numbers (at most 111 and what Lemire's loop rejects: fewer than one batch of 128); drawn one by one from wave-uniform state, every PCG64 step is a 128 x 128-bit multiply on
 // the scalar unit (~45 scalar instructions per 64-bit output) inside a kernel that is bound by scalar issue -- a third of a
 // path's instructions.  An LCG can be jumped: s_k = A^k s_0 + S_k inc with S_k = 1 + A + ... + A^(k-1), so lane k computes
 // step k + 1 directly (two 128-bit multiplies on the vector unit, all 64 lanes at once) and a draw is one v_readlane.  The

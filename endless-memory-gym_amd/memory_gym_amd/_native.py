@@ -86,6 +86,7 @@ def _load():
         L.mg_store_probe.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
     L.mg_enable_peer_access.argtypes = [C.c_int, C.c_int]
     L.mg_debug_rng.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+    L.mg_debug_set_rng.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
     if hasattr(L, "mg_set_option_set"):
         L.mg_set_option_set.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.POINTER(C.c_double), C.c_int]
         L.mg_bind_option_sets.argtypes = [C.c_void_p, C.c_void_p]

@@ -573,6 +573,12 @@ class VecMemoryGym:
         _native.check(_native.LIB.mg_debug_rng(self._h, int(i), w.ctypes.data), "mg_debug_rng")
         return w
 
+    def set_rng_words(self, i, words):
+        """Test hook (include/memgym.h: mg_debug_set_rng): instance i continues with the PCG64 stream given in rng_words()' six words."""
+        w = np.ascontiguousarray([int(x) for x in words], dtype=np.uint64)
+        assert w.shape == (6,)
+        _native.check(_native.LIB.mg_debug_set_rng(self._h, int(i), w.ctypes.data), "mg_debug_set_rng")
+
     def debug_counter(self, name):
         """Named test / telemetry counter of the handle (include/memgym.h: mg_debug_counter), e.g. "one_launch_rescues"."""
         v = C.c_int64()

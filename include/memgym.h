@@ -350,6 +350,13 @@ int mg_debug_counter(mg_env* env, const char* name, int64_t* value);
 /* Test hook: copy the numpy-compatible PCG64 words of instance i to host:
  * out[6] = {state_hi, state_lo, inc_hi, inc_lo, has_uint32, uinteger}.  Synchronous. */
 int mg_debug_rng(mg_env* env, int32_t i, uint64_t* out);
+/* Test hook, the reverse: instance i continues with the PCG64 stream given in the same six words -- the reference's
+ * `env.np_random = np.random.Generator(bit_generator with this state)` at this point of the episode.  Nothing else of the instance
+ * changes, except that whatever a family had computed ahead of time from the old stream is dropped (Endless-MysteryPath: the next
+ * episode's first segment).  in[3] (the increment's low word) must be odd.  Synchronous: work
+ * in flight and work put off is finished first, the words are written with host copies -- no kernel of the library reads this hook.
+ * tests/test_gpu_rng_edges.py uses it to put rejected and extreme draws where the device restates numpy's stream. */
+int mg_debug_set_rng(mg_env* env, int32_t i, const uint64_t* in);
 
 #ifdef __cplusplus
 }

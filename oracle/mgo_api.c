@@ -128,18 +128,82 @@ void mgo_rng_words(mgo_env* e, uint64_t* out) {
     out[5] = (uint64_t)e->rng.buf;
 }
 
+/* Test hook, the mirror of mgo_rng_words: env.np_random = Generator(PCG64 with this state) at this point of the episode.  Nothing
+ * else of the instance changes; a reset(seed=None) is legal from now on. */
+static void mgo_rng_assign(mgo_rng* r, const uint64_t* in) {
+    r->state = ((mgo_u128)in[0] << 64) | in[1];
+    r->inc = ((mgo_u128)in[2] << 64) | in[3];
+    r->has_u32 = in[4] != 0;
+    r->buf = (uint32_t)in[5];
+    r->book.outputs = 0;
+    r->book.on = 1;
+}
+void mgo_rng_set_words(mgo_env* e, const uint64_t* in) {
+    mgo_rng_assign(&e->rng, in);
+    e->seeded = 1;
+}
+
+/* Test hook: the bookkeeping of the instance's stream (oracle/mgo_rng.h mgo_rng_book), so that a test knows whether it exercised
+ * what it claims.  counts[4] = {words rejected, 64-bit outputs since the stream was seeded / set, distinct spans that did not fit
+ * the table, entries written to rej_at}; span / draws / span_rejected: up to `cap` table rows (returns how many there are);
+ * rej_at[MGO_RNG_REJ_AT]: origin of the first rejected words, 2 * output index + (1 = high half).  Any pointer may be NULL.
+ * clear != 0: the counters start over (the count of outputs too).  The books of a stream are kept from its first mgo_rng_set_words or
+ * mgo_rng_stats on (the count of outputs always): a test clears them where its observation begins. */
+int mgo_rng_stats(mgo_env* e, uint64_t* counts, uint32_t* span, uint32_t* draws, uint32_t* span_rejected, int cap, uint32_t* rej_at,
+                  int clear) {
+    mgo_rng_book* b = &e->rng.book;
+    const int n = b->n_spans;
+    if (counts) {
+        counts[0] = b->rejected;
+        counts[1] = b->outputs;
+        counts[2] = (uint64_t)b->spans_lost;
+        counts[3] = b->n_rej_at;
+    }
+    for (int k = 0; k < n && k < cap; k++) {
+        if (span) span[k] = b->span[k];
+        if (draws) draws[k] = b->span_draws[k];
+        if (span_rejected) span_rejected[k] = b->span_rejected[k];
+    }
+    if (rej_at)
+        for (uint32_t k = 0; k < b->n_rej_at; k++) rej_at[k] = b->rej_at[k];
+    if (clear) memset(b, 0, sizeof(*b));
+    b->on = 1;
+    return n;
+}
+
 /* ---- raw RNG access for tests/test_oracle_rng.py ------------------------------------------------ */
+static uint64_t mgo_test_rng_run(mgo_rng* r, const int32_t* ops, const int64_t* lo, const int64_t* hi, int n, double* out);
 void mgo_test_rng(uint64_t seed, const int32_t* ops, const int64_t* lo, const int64_t* hi, int n, double* out) {
     mgo_rng r;
+    memset(&r, 0, sizeof(r));
     mgo_rng_seed(&r, seed);
+    mgo_test_rng_run(&r, ops, lo, hi, n, out);
+}
+/* ... starting from given words (mgo_rng_words' order) instead of a seed (tests/test_rng_craft.py).  rejected_ops (may be NULL):
+ * rejected_ops[i] = words op i rejected (0 for an op that is no bounded draw).  Returns the total. */
+uint64_t mgo_test_rng_words(const uint64_t* words, const int32_t* ops, const int64_t* lo, const int64_t* hi, int n, double* out,
+                            uint32_t* rejected_ops) {
+    mgo_rng r;
+    memset(&r, 0, sizeof(r));
+    mgo_rng_assign(&r, words);
+    if (!rejected_ops) return mgo_test_rng_run(&r, ops, lo, hi, n, out);
+    for (int i = 0; i < n; i++) {
+        const uint64_t before = r.book.rejected;
+        mgo_test_rng_run(&r, ops + i, lo + i, hi + i, 1, out + i);
+        rejected_ops[i] = (uint32_t)(r.book.rejected - before);
+    }
+    return r.book.rejected;
+}
+static uint64_t mgo_test_rng_run(mgo_rng* r, const int32_t* ops, const int64_t* lo, const int64_t* hi, int n, double* out) {
     for (int i = 0; i < n; i++) {
         switch (ops[i]) {
-            case 0: out[i] = (double)mgo_integers(&r, lo[i], hi[i]); break;
-            case 1: out[i] = mgo_next_double(&r); break;
-            case 2: out[i] = (double)(mgo_next_u64(&r) >> 11); break;
-            default: out[i] = mgo_uniform(&r, (double)lo[i] / 1e6, (double)hi[i] / 1e6); break;
+            case 0: out[i] = (double)mgo_integers(r, lo[i], hi[i]); break;
+            case 1: out[i] = mgo_next_double(r); break;
+            case 2: out[i] = (double)(mgo_next_u64(r) >> 11); break;
+            default: out[i] = mgo_uniform(r, (double)lo[i] / 1e6, (double)hi[i] / 1e6); break;
         }
     }
+    return r->book.rejected;
 }
 
 /* ---- batched helpers: N independent instances, env i seeded seed0+i ------------------------------ */

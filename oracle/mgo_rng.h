@@ -8,6 +8,10 @@
  * Published algorithms restated: SeedSequence (M.E. O'Neill seed_seq_fe128 variant used by numpy),
  * PCG64 XSL-RR 128/64, Lemire's nearly-divisionless bounded integers (numpy _bounded_integers),
  * next_double = (u64 >> 11) * 2^-53, 32-bit draws buffered LOW half first.
+ *
+ * Bookkeeping (mgo_rng_stats): which spans were drawn, how many 32-bit words Lemire's loop rejected and from which 64-bit
+ * outputs they came.  It is written beside the draws and read by nothing that draws: a test that claims to have exercised a
+ * rejection asks here whether it did (tests/test_rng_craft.py, tests/test_gpu_rng_edges.py).
  */
 #ifndef MGO_RNG_H
 #define MGO_RNG_H
@@ -15,11 +19,49 @@
 
 typedef unsigned __int128 mgo_u128;
 
+#define MGO_RNG_SPANS 32   /* distinct spans remembered per stream (the environments draw fewer than that per option set) */
+#define MGO_RNG_REJ_AT 8   /* rejected words whose origin is remembered */
+
+typedef struct {
+    int on;                               /* books are kept from the first mgo_rng_set_words / mgo_rng_stats of the stream on: every other run of the oracle pays one test per draw */
+    uint64_t rejected;                    /* 32-bit words Lemire's loop threw away */
+    uint64_t outputs;                     /* 64-bit outputs generated since the stream was seeded / set */
+    int n_spans, spans_lost;              /* spans_lost: distinct spans that found the table full */
+    uint32_t span[MGO_RNG_SPANS];         /* distinct spans drawn (hi - lo; span 1 draws nothing and is not listed) */
+    uint32_t span_draws[MGO_RNG_SPANS];   /* integers() calls with that span */
+    uint32_t span_rejected[MGO_RNG_SPANS];/* words rejected under that span */
+    uint32_t n_rej_at;                    /* min(rejected, MGO_RNG_REJ_AT) */
+    uint32_t rej_at[MGO_RNG_REJ_AT];      /* the first rejected words: 2 * (index of the 64-bit output, counted from 0 at the seeding) + (1 = its high half) */
+} mgo_rng_book;
+
 typedef struct {
     mgo_u128 state, inc;
     int has_u32;
     uint32_t buf;
+    mgo_rng_book book;
 } mgo_rng;
+
+static inline int mgo_rng_book_span(mgo_rng* r, uint32_t span) {
+    mgo_rng_book* b = &r->book;
+    for (int k = 0; k < b->n_spans; k++)
+        if (b->span[k] == span) return k;
+    if (b->n_spans == MGO_RNG_SPANS) {
+        b->spans_lost++;
+        return -1;
+    }
+    b->span[b->n_spans] = span;
+    b->span_draws[b->n_spans] = 0;
+    b->span_rejected[b->n_spans] = 0;
+    return b->n_spans++;
+}
+static inline void mgo_rng_book_reject(mgo_rng* r, int k) {
+    mgo_rng_book* b = &r->book;
+    b->rejected++;
+    if (k >= 0) b->span_rejected[k]++;
+    /* the word just drawn: the buffered high half if nothing is buffered now, else the low half of the newest output */
+    if (b->n_rej_at < MGO_RNG_REJ_AT)  /* (0xFFFFFFFF: the half that was buffered already when the stream was set) */
+        b->rej_at[b->n_rej_at++] = b->outputs ? (uint32_t)(2 * (b->outputs - 1) + (r->has_u32 ? 0 : 1)) : 0xFFFFFFFFu;
+}
 
 static inline void mgo_seedseq_state(uint64_t seed, uint64_t out64[4]) {
     const uint32_t INIT_A = 0x43b0d7e5u, MULT_A = 0x931e8875u, INIT_B = 0x8b51f9ddu, MULT_B = 0x58f38dedu;
@@ -69,9 +111,11 @@ static inline void mgo_rng_seed(mgo_rng* r, uint64_t seed) {
     r->state = r->state * MGO_PCG_MULT + r->inc;
     r->has_u32 = 0;
     r->buf = 0;
+    r->book.outputs = 0;  /* (the other counters run on: a test clears them through mgo_rng_stats) */
 }
 
 static inline uint64_t mgo_next_u64(mgo_rng* r) {
+    r->book.outputs++;
     r->state = r->state * MGO_PCG_MULT + r->inc;
     uint64_t hi = (uint64_t)(r->state >> 64), lo = (uint64_t)r->state;
     uint64_t x = hi ^ lo;
@@ -98,11 +142,14 @@ static inline int64_t mgo_integers(mgo_rng* r, int64_t lo, int64_t hi) {
     uint64_t rng = (uint64_t)(hi - 1 - lo);
     if (rng == 0) return lo;
     uint32_t rng_excl = (uint32_t)rng + 1u;
+    const int book = r->book.on ? mgo_rng_book_span(r, rng_excl) : -1;
+    if (book >= 0) r->book.span_draws[book]++;
     uint64_t m = (uint64_t)mgo_next_u32(r) * rng_excl;
     uint32_t left = (uint32_t)m;
     if (left < rng_excl) {
         uint32_t thr = (0xFFFFFFFFu - (uint32_t)rng) % rng_excl;
         while (left < thr) {
+            if (r->book.on) mgo_rng_book_reject(r, book);
             m = (uint64_t)mgo_next_u32(r) * rng_excl;
             left = (uint32_t)m;
         }

@@ -36,6 +36,10 @@ def lib():
         L.mgo_get_list.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int]
         L.mgo_get_gt.argtypes = [C.c_void_p, C.c_void_p]
         L.mgo_rng_words.argtypes = [C.c_void_p, C.c_void_p]
+        L.mgo_rng_set_words.argtypes = [C.c_void_p, C.c_void_p]
+        L.mgo_rng_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+        L.mgo_test_rng_words.restype = C.c_uint64
+        L.mgo_test_rng_words.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.mgo_render_debug.argtypes = [C.c_void_p, C.c_void_p]
         L.mgo_scene.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.mgo_test_rng.argtypes = [C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
@@ -129,6 +133,25 @@ class OracleEnv:
         w = np.zeros(6, np.uint64)
         self.L.mgo_rng_words(self.h, w.ctypes.data)
         return w
+
+    def set_rng_words(self, words):
+        """Test hook (oracle/mgo_api.c mgo_rng_set_words): env.np_random = Generator(PCG64 with this state), rng_words()' order."""
+        w = np.ascontiguousarray([int(x) for x in words], dtype=np.uint64)
+        assert w.shape == (6,) and int(w[3]) & 1, "six words, an odd increment"
+        self.L.mgo_rng_set_words(self.h, w.ctypes.data)
+
+    def rng_stats(self, clear=False):
+        """The stream's bookkeeping (oracle/mgo_rng.h mgo_rng_book): dict(rejected, outputs, spans_lost (distinct spans
+        that found the table of 32 full: their draws are in no row), spans {span: (draws, words rejected)},
+        rej_at [(index of the 64-bit output since the stream was seeded / set, or -1 for a half buffered before that; 1 = high half)])."""
+        cap = 32
+        counts, span, draws, rej = np.zeros(4, np.uint64), np.zeros(cap, np.uint32), np.zeros(cap, np.uint32), np.zeros(cap, np.uint32)
+        at = np.zeros(8, np.uint32)
+        n = self.L.mgo_rng_stats(self.h, counts.ctypes.data, span.ctypes.data, draws.ctypes.data, rej.ctypes.data, cap, at.ctypes.data, int(clear))
+        assert n <= cap
+        return {"rejected": int(counts[0]), "outputs": int(counts[1]), "spans_lost": int(counts[2]),
+                "spans": {int(span[k]): (int(draws[k]), int(rej[k])) for k in range(n)},
+                "rej_at": [(-1, 1) if a == 0xFFFFFFFF else (int(a) >> 1, int(a) & 1) for a in at[:int(counts[3])]]}
 
     def scene(self, values):
         """Test hook (oracle/mgo_env.h mgo_vtbl.scene): put the instance into the scene described by the family-specific
