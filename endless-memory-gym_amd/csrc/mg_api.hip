@@ -22,6 +22,7 @@ struct mg_env {
     int num_envs = 0;
     int variant = 0, family = 0;  // what make_* was called with
     bool started = false;         // a reset has happened
+    int64_t final_obs_generic_steps = 0;  // mg_debug_counter: mg_step calls that kept terminal observations on the generic path (see mg_step)
     std::string id;
     int obs_format = MG_OBS_U8_XYC;
     float* vec_dev = nullptr;     // the caller's vector-observation binding (mg_bind_vector_obs), or the single-instance block's
@@ -342,6 +343,7 @@ int mg_step(mg_env* env, const int32_t* actions_dev, void* obs_dev, float* rewar
             // terminal frames wanted: step without auto-reset (obs rows of finished instances = terminal frames), keep
             // a copy of exactly those rows, then reset the finished instances with seed=None -- the same RNG
             // consumption and frames as the fused path (tests/test_gpu_vector_api.py)
+            ++env->final_obs_generic_steps;
             f->step(actions_dev, obs_dev, reward_dev, done_dev, gt_dev, &ib, 0, st);
             if (mg::sparse_masked_raster()) {  // the rows are there: copied, not drawn again (round 6)
                 const int n = env->num_envs, vec_per_row = (int)(mg_obs_bytes(env) / 16);
@@ -592,6 +594,10 @@ int mg_debug_counter(mg_env* env, const char* name, int64_t* value) {
     return guarded(env, [&] {
         if (!name || !value) throw std::runtime_error("mg_debug_counter: NULL");
         MG_HIP(hipDeviceSynchronize());
+        if (std::string(name) == "final_obs_generic_steps") {  // every id: which way mg_step kept the terminal observations is decided in this file
+            *value = env->final_obs_generic_steps;
+            return;
+        }
         if (!env->fam->debug_counter(name, value)) throw std::runtime_error(std::string("mg_debug_counter: no counter named ") + name + " for " + env->id);
     });
 }

@@ -38,13 +38,6 @@ inline void with_obs_format(int fmt, F&& f) {
     else f(std::integral_constant<int, MG_OBS_U8_XYC>{});
 }
 
-// the one-byte formats alone (what the mortar family's one-launch step is instantiated for); the caller has checked that fmt is one
-template <typename F>
-inline void with_one_byte_format(int fmt, F&& f) {
-    if (fmt == MG_OBS_U8_CYX) f(std::integral_constant<int, MG_OBS_U8_CYX>{});
-    else f(std::integral_constant<int, MG_OBS_U8_XYC>{});
-}
-
 // A launch, and a launch whose error is looked at right away.  Which launches are checked is history, not design (the checked
 // ones are those that were followed by a hipGetLastError() when this header was written); the rule lives in check_launch().
 #ifdef __HIPCC__

@@ -15,9 +15,9 @@
 //   mg_mortar_one_launch.hpp  mortar_step_raster_kernel: the step as one launch, its claim / hand-over word, RESCUE_AFTER_TICKS
 //
 // The launches of a step as shipped:
-//   ONE launch for one-byte observations (MG_OBS_U8_XYC, MG_OBS_U8_CYX) and one option set (mortar_step_raster_kernel: the step's workgroups lead the raster's grid and a frame waits for its own
-//   descriptor; terminal observations kept, mg_info_buffers.final_obs_dev: its <FINAL> form; mg_single_step, MG_OBS_U8_XYC: its <DONE_FLAG> form), two launches otherwise (float
-//   formats, per-instance option sets, HIP-graph capture):
+//   ONE launch for handles with one option set, in every observation format (mortar_step_raster_kernel: the step's workgroups lead the raster's grid and a frame waits for its own
+//   descriptor; terminal observations kept, mg_info_buffers.final_obs_dev: its <FINAL> form; mg_single_step, MG_OBS_U8_XYC: its <DONE_FLAG> form), two launches otherwise
+//   (per-instance option sets, HIP-graph capture):
 //   mortar_step_kernel : one LANE per environment instance.  Episode state machine, RNG, reward/done/info; emits a
 //                   16-byte frame descriptor per instance.  State is small fixed-size records in HBM, read and
 //                   written fully coalesced (lane i <-> record i).
@@ -248,7 +248,7 @@ class MortarFamily : public Family {
         sets_.upload(s);
         const MortarStepArgs sa{P_, n_, io(), actions, reward, done, gt_dim() ? gt : nullptr, ib, autoreset, handover_.p, nullptr};
         // one launch: mortar_step_raster_kernel (handles with ONE option set: the per-set step code reads its parameters from memory)
-        if (one_byte_format() && fuse_step() && !sets_.per_set() && !capturing(s)) {
+        if (one_launch(s)) {
             epoch_ = epoch_ % 255u + 1u;  // 1 .. 255: never the 0 of a fresh hand-over array (resets and two-launch steps do not write the words)
             ++ticket_;                    // claim words hold the ticket of the last one-launch step: never this one
             const int logic_wgs = (n_ + 255) / 256;
@@ -258,21 +258,21 @@ class MortarFamily : public Family {
             // The done flag (want_done_flag) is granted here: this launch is the step's last kernel, and with ONE instance and no ground
             // truth (mg_single_step puts a ground_truth64 launch behind the step) nothing follows it.  (Three of the four <FLAG, FINAL>
             // forms exist: the flag is asked for by single steps, which pass autoreset = 0, so it never meets kept terminal observations.)
-            // (MG_OBS_U8_CYX has no <DONE_FLAG> form: its single steps are the plain launch, and mg_single_step waits for the stream)
+            // (MG_OBS_U8_XYC alone has a <DONE_FLAG> form: single steps in the other formats are the plain launch, and mg_single_step waits for the stream)
             const bool store_flag = flag_dev_ && n_ == 1 && gt_dim() == 0 && obs_format == MG_OBS_U8_XYC;
-            auto one_launch = [&](auto kernel, const MortarStepArgs& a, uint32_t* flag, uint32_t flag_ticket) {
+            auto launch_step = [&](auto kernel, const MortarStepArgs& a, uint32_t* flag, uint32_t flag_ticket) {
                 launch(kernel, dim3(logic_wgs + frames), dim3(256), RASTER_LDS, s, a, logic_wgs, logic_last ? frames : 0, epoch_, ticket_,
                                claims_.p, rescues_.p, atlas_->dev(), obs, flag, flag_ticket);
             };
             prof.begin(1, s);
             if (store_flag) {
-                one_launch(mortar_step_raster_kernel<true>, sa, flag_dev_, flag_ticket_);
+                launch_step(mortar_step_raster_kernel<true>, sa, flag_dev_, flag_ticket_);
             } else if (ib.final_obs_dev && autoreset) {  // terminal observations kept by the launch itself (keeps_final_obs)
                 MortarStepArgs fa = sa;
                 fa.tdesc = tdesc_.p;
-                with_one_byte_format(obs_format, [&](auto F) { one_launch(mortar_step_raster_kernel<false, true, decltype(F)::value>, fa, nullptr, 0u); });
+                with_obs_format(obs_format, [&](auto F) { launch_step(mortar_step_raster_kernel<false, true, decltype(F)::value>, fa, nullptr, 0u); });
             } else {
-                with_one_byte_format(obs_format, [&](auto F) { one_launch(mortar_step_raster_kernel<false, false, decltype(F)::value>, sa, nullptr, 0u); });
+                with_obs_format(obs_format, [&](auto F) { launch_step(mortar_step_raster_kernel<false, false, decltype(F)::value>, sa, nullptr, 0u); });
             }
             check_launch();
             ++one_launch_steps_;
@@ -337,7 +337,8 @@ class MortarFamily : public Family {
     uint32_t ticket_ = 0;  // one-launch step: number of the step, the value a slot's claim word takes when a wave claims it
     uint32_t epoch_ = 0;  // the one-launch step's hand-over epoch, 1 .. 255 (every one-launch step rewrites every word, so the only stale
                           // values a frame workgroup can meet are the previous one-launch step's and the 0 of the fresh array)
-    bool one_byte_format() const { return obs_format == MG_OBS_U8_XYC || obs_format == MG_OBS_U8_CYX; }  // what the one-launch step is instantiated for
+    // step() goes out as mortar_step_raster_kernel (instantiated for every observation format: profiles/chw_final.md has each one against the two launches)
+    bool one_launch(hipStream_t s) { return fuse_step() && !sets_.per_set() && !capturing(s); }
     static bool fuse_step() {  // lab build: MEMGYM_MORTAR_FUSE=0 selects the two-launch form for A/B measurements
         static const bool on = lab_flag("MEMGYM_MORTAR_FUSE", true);
         return on;
@@ -413,7 +414,7 @@ class MortarFamily : public Family {
     // MEMGYM_MORTAR_FINAL_FUSED=0: the generic path of mg_step)
     bool keeps_final_obs(hipStream_t s) override {
         static const bool wanted = lab_flag("MEMGYM_MORTAR_FINAL_FUSED", true);
-        return wanted && one_byte_format() && fuse_step() && !sets_.per_set() && !capturing(s);
+        return wanted && one_launch(s);
     }
 
     void raster(void* obs, hipStream_t s) { raster_only(obs, nullptr, s); }

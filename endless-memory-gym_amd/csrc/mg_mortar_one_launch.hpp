@@ -6,7 +6,7 @@
 
 namespace mg {
 using namespace v1;  // raster generation 1 (see mg_raster_v1.hpp)
-// ONE launch per step (the one-byte observation formats: FMT = MG_OBS_U8_XYC or MG_OBS_U8_CYX, mg_stream_out.hpp).  `logic_wgs` workgroups of the grid run the step (one lane per instance), all others
+// ONE launch per step (every observation format, FMT: mg_stream_out.hpp).  `logic_wgs` workgroups of the grid run the step (one lane per instance), all others
 // are the raster's persistent workgroups; a frame's workgroup waits for ITS descriptor -- the epoch in the instance's hand-over
 // word, read at agent scope past the caches -- instead of for the slowest wave of a separate logic launch plus that launch's
 // fixed cost: the first frames leave ~8 us earlier (MortarMayhem-Grid 65,536: 233 -> 224 us per step, 281 -> 292 M env-steps/s;
@@ -55,11 +55,23 @@ __device__ __forceinline__ MortarDesc desc_from_handover(uint32_t lo, uint32_t h
 // operation behind the launch, 4.5 us less than hipStreamSynchronize (tools/microbench/launch_wait.hip).  Everything else the host reads
 // (reward, done, the episode record) was stored by the step's wave, and waited for (mortar_step_body<ORDERED>), BEFORE it published the word this workgroup waited for.
 // FINAL: the call keeps terminal observations (see mortar_step_body) -- a kernel of its own, the measured one (FINAL = false) is as it was.
-// FMT: the stream-out format of both frames.  MG_OBS_U8_CYX has the plain and the FINAL form (no DONE_FLAG one: mg_single_step waits for the stream).
+// FMT: the stream-out format of both frames.  Every format but MG_OBS_U8_XYC has the plain and the FINAL form (no DONE_FLAG one: mg_single_step waits for the stream).
+// Workgroups per CU the kernel is compiled for: 7 (72 VGPRs) for the one-byte formats, 6 (80 VGPRs) for the float ones -- their stream-out holds a
+// lane's gather offsets and eight converted values next to the frame loop's own state, and under the bound of 7 the 16-bit forms spilled 13-14
+// VGPRs (24 / 68 B of scratch per lane); with 6 no float form spills one (profiles/chw_final.md).
+constexpr int one_launch_wgs_per_cu(int fmt) { return fmt == MG_OBS_U8_XYC || fmt == MG_OBS_U8_CYX ? 7 : 6; }
 template <bool DONE_FLAG, bool FINAL = false, int FMT = MG_OBS_U8_XYC>
-__global__ __launch_bounds__(256, 7) void mortar_step_raster_kernel(MortarStepArgs a, int logic_wgs, int logic_base, uint32_t epoch,
+__global__ __launch_bounds__(256, one_launch_wgs_per_cu(FMT)) void mortar_step_raster_kernel(MortarStepArgs a, int logic_wgs, int logic_base, uint32_t epoch,
                                                                     uint32_t ticket, uint32_t* claims, uint32_t* rescues,
                                                                     RasterAtlas A, void* __restrict__ obs, uint32_t* done_flag, uint32_t done_ticket) {
+    // The float stream-outs get this kernel's own instantiation of store_frame (SITE, mg_stream_out.hpp) and the lane index with its range
+    // restored: the frame loop's index is opaque (below), and the raster kernels that share the float instantiations would be compiled for a
+    // lane index of any sign with it (signed divisions in the lane's gather offsets).  The one-byte forms call what they always called.
+    constexpr bool ONE_BYTE = one_launch_wgs_per_cu(FMT) == 7;
+    auto store = [](uint8_t* frame, void* dst, int env, int t) {
+        if constexpr (ONE_BYTE) store_frame<FMT, false>(frame, dst, env, t);
+        else store_frame<FMT, false, false, 1>(frame, dst, env, t & 255);
+    };
     const int n = a.n;
     const int tid = threadIdx.x, lane = tid & 63;
     const int rel = (int)blockIdx.x - logic_base;
@@ -130,7 +142,7 @@ __global__ __launch_bounds__(256, 7) void mortar_step_raster_kernel(MortarStepAr
                 R.tid = tt;
                 MortarComposer::compose(&td, R);
                 __syncthreads();
-                store_frame<FMT, false>(smem, ka->info.final_obs_dev, env, tt);
+                store(smem, ka->info.final_obs_dev, env, tt);
                 __syncthreads();
             }
         }
@@ -142,7 +154,7 @@ __global__ __launch_bounds__(256, 7) void mortar_step_raster_kernel(MortarStepAr
         R.tid = t;
         MortarComposer::compose(&d, R);
         __syncthreads();
-        store_frame<FMT, false>(smem, obs, env, t);  // (plain stores: non-temporal ones 281 -> 226-241 M at 65,536, round 4)
+        store(smem, obs, env, t);  // (plain stores: non-temporal ones 281 -> 226-241 M at 65,536, round 4)
         __syncthreads();
     }
     if constexpr (DONE_FLAG) {

@@ -465,16 +465,18 @@ class MysteryFamily : public Family {
     void raster_with_paths(void* obs, hipStream_t s, void* final_obs = nullptr) {
         const dim3 grid(frames_grid(n_) + PATH_WGS);
         auto paths_launch = [&](auto kernel) { launch_checked(kernel, grid, dim3(256), RASTER_LDS, s, desc_.p, atlas_->dev(), obs, n_, P_, io(), final_obs); };
-        if (final_obs) paths_launch(mystery_raster_paths_kernel<MG_OBS_U8_XYC, true>);  // (the FINAL form exists for the uint8 format only: keeps_final_obs)
-        else with_obs_format(obs_format, [&](auto F) { paths_launch(mystery_raster_paths_kernel<decltype(F)::value>); });
+        with_obs_format(obs_format, [&](auto F) {
+            if (final_obs) paths_launch(mystery_raster_paths_kernel<decltype(F)::value, true>);
+            else paths_launch(mystery_raster_paths_kernel<decltype(F)::value>);
+        });
     }
-    // (the finite variants' step + raster / path-service launches keep terminal observations themselves; lab MEMGYM_MYSTERY_FINAL_FUSED=0: the
+    // (the finite variants' step + raster / path-service launches keep terminal observations themselves, in every observation format; lab MEMGYM_MYSTERY_FINAL_FUSED=0: the
     // generic path of mg_step.  Endless Mystery Path: its step kernel and the service waves of its fused launch leave the terminal frame
     // DESCRIPTORS behind, one sparse raster launch draws them -- lab MEMGYM_EMP_FINAL_FUSED=0: the generic path.)
     bool keeps_final_obs(hipStream_t) override {
         static const bool wanted = lab_flag("MEMGYM_MYSTERY_FINAL_FUSED", true), emp_wanted = lab_flag("MEMGYM_EMP_FINAL_FUSED", true);
         if (P_.endless) return emp_wanted && fuse_serve() && obs_format == MG_OBS_U8_XYC && !big_sprites_ && !sets_.per_set();
-        return wanted && obs_format == MG_OBS_U8_XYC && !big_sprites_ && !sets_.per_set() && defer_mode() != 0;
+        return wanted && !big_sprites_ && !sets_.per_set() && defer_mode() != 0;
     }
     MysteryIO io() {
         MysteryIO o;

@@ -113,7 +113,10 @@ __device__ __forceinline__ void frame_to_cyx(uint8_t* frame, int tid) {
 // Every format reads the frame only and may be called by any lane on its own, EXCEPT MG_OBS_U8_CYX: that one is a collective call of a
 // workgroup of exactly 256 threads (tid = 0 .. 255) from workgroup-uniform flow -- it holds two barriers -- and it DESTROYS the frame
 // (hence the non-const pointer): the caller composes the whole frame again before it reads a byte of it.
-template <int FMT, bool NT, bool BUF = false>
+// SITE: a number that gives a caller an instantiation of its own.  Before anything is inlined the compiler's interprocedural passes merge
+// what every caller of ONE instantiation knows about its arguments (the range of `tid`, say); a caller that passes a lane index the compiler
+// cannot see through would change the code of all the others (the mortar one-launch step's float forms, mg_mortar_one_launch.hpp: SITE = 1).
+template <int FMT, bool NT, bool BUF = false, int SITE = 0>
 __device__ __forceinline__ void store_frame(uint8_t* __restrict__ frame, void* __restrict__ obs, int env, int tid) {
     if constexpr (FMT == MG_OBS_U8_CYX) {  // then out like the uint8 frame, which it is: one byte per element, 1,323 vectors
         frame_to_cyx(frame, tid);
