@@ -27,9 +27,10 @@
 //                  spot_step_kernel with defer = 1: an instance that finishes is queued and its descriptor tagged DESC_QUEUED -> spot_raster_serve_kernel: the first
 //                  SPOT_SVC_WGS workgroups take the queue entries, reset those instances and draw their frames, all others draw the frames that were not queued.
 //   Which one: fuse_resets().  Endless-SearingSpotlights-v0: two launches up to RASTER_PLAIN_MAX = 16,384 instances, fused beyond; SearingSpotlights-v0: fused up to
-//   FUSE_MAX = 65,536 instances, two launches beyond.  Float observation formats, per-instance option sets and autoreset = 0: always two launches.
+//   FUSE_MAX = 65,536 instances, two launches beyond; MG_OBS_U8_CYX like the uint8 frame, the float formats fused up to FUSE_MAX on both ids (fuse_resets()).
+//   Per-instance option sets, autoreset = 0 and the image-order formats on a stream that is being captured: always two launches.
 //   Terminal observations kept (mg_info_buffers.final_obs_dev, keeps_final_obs()): always the fused pair, in its <FINAL> form -- the service workgroup draws the terminal
-//   frame from the descriptor the step left, then resets.
+//   frame from the descriptor the step left, then resets.  Every observation format: spot_raster_serve_kernel<EN, BORDER, NT, FINAL, FMT>.
 #include <memory>
 
 #include "mg_atlas.hpp"
@@ -290,7 +291,7 @@ class SpotFamily : public Family {
         // (a call that keeps terminal observations: always deferred -- the service workgroup draws the terminal frame from the descriptor this
         // launch leaves, then resets: keeps_final_obs)
         const bool keep_final = autoreset && ib.final_obs_dev && keeps_final_obs(s);
-        const int defer = (autoreset && obs_format == MG_OBS_U8_XYC && (fuse_resets() || keep_final) && !sets_.per_set()) ? 1 : 0;
+        const int defer = (autoreset && (fuse_resets() || keep_final) && !sets_.per_set() && fused_here(s)) ? 1 : 0;
         const int sb = step_block(256);
         const SpotStepArgs sa{P_, io(), actions, reward, done, gt, ib, autoreset, defer};
         const dim3 sg((n_ * SLOTS + sb - 1) / sb);
@@ -307,17 +308,24 @@ class SpotFamily : public Family {
                                    keep_final ? ib.final_obs_dev : nullptr};
             const bool nt = fused_nt();                // non-temporal: with plain stores the fused launch loses 5-15 us at every occupancy
             const int serve_lds = RASTER_LDS_REQUEST;  // 25 KiB: six per CU
-            // (endless x border x non-temporal x kept terminal observations: all sixteen forms are launched)
+            // (endless x border x non-temporal x kept terminal observations: all sixteen forms are launched in each of the two one-byte formats;
+            // the float formats' stream-out has no non-temporal flavour -- eight forms each, NT = false)
             with_bool(P_.endless, [&](auto EN) {
                 with_bool(P_.ordered_holes, [&](auto BO) {
-                    with_bool(nt, [&](auto NT) {
-                        with_bool(keep_final, [&](auto FINAL) {
-                            launch_checked(spot_raster_serve_kernel<decltype(EN)::value, decltype(BO)::value, decltype(NT)::value, decltype(FINAL)::value>,
-                                           dim3(grid), dim3(256), serve_lds, s, va);
+                    with_bool(keep_final, [&](auto FINAL) {
+                        with_obs_format(obs_format, [&](auto F) {
+                            constexpr int FMT = decltype(F)::value;
+                            constexpr bool ONE_BYTE = FMT == MG_OBS_U8_XYC || FMT == MG_OBS_U8_CYX;
+                            with_bool(ONE_BYTE && nt, [&](auto NT) {
+                                if constexpr (ONE_BYTE || !decltype(NT)::value)
+                                    launch_checked(spot_raster_serve_kernel<decltype(EN)::value, decltype(BO)::value, decltype(NT)::value, decltype(FINAL)::value, FMT>,
+                                                   dim3(grid), dim3(256), serve_lds, s, va);
+                            });
                         });
                     });
                 });
             });
+            ++spot_fused_steps_;
         } else {
             raster(obs, s);
         }
@@ -359,8 +367,14 @@ class SpotFamily : public Family {
         sets_.touch();
     }
     void raster_debug(void* frames, hipStream_t s) override;
+    bool debug_counter(const std::string& name, int64_t* out) override {
+        if (name != "spot_fused_steps") return false;  // step() calls that went out as spot_raster_serve_kernel since the handle was created (host-side count)
+        *out = spot_fused_steps_;
+        return true;
+    }
 
    private:
+    int64_t spot_fused_steps_ = 0;  // debug_counter("spot_fused_steps")
     SpotIO io() {
         SpotIO o;
         o.core = core_.p;
@@ -505,9 +519,16 @@ class SpotFamily : public Family {
 
     void raster(void* obs, hipStream_t s) { raster_only(obs, nullptr, s); }
     // (the fused raster / reset launch keeps terminal observations itself; lab MEMGYM_SPOT_FINAL_FUSED=0: the generic path of mg_step)
-    bool keeps_final_obs(hipStream_t) override {
+    bool keeps_final_obs(hipStream_t s) override {
         static const bool wanted = lab_flag("MEMGYM_SPOT_FINAL_FUSED", true);
-        return wanted && obs_format == MG_OBS_U8_XYC && !sets_.per_set();
+        return wanted && !sets_.per_set() && fused_here(s);
+    }
+    // (a stream that is being captured into a graph: the image-order formats keep the two plain launches and mg_step's generic path there -- what
+    // they took everywhere before the fused launch learnt them; the uint8 frame's fused launch is captured as it always was)
+    bool fused_here(hipStream_t s) const {
+        if (obs_format == MG_OBS_U8_XYC) return true;
+        hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+        return !(hipStreamIsCapturing(s, &st) == hipSuccess && st != hipStreamCaptureStatusNone);
     }
 
     // Resets served inside the raster launch: on for the finite variant up to FUSE_MAX instances (more instances finish per step
@@ -517,7 +538,15 @@ class SpotFamily : public Family {
     // tail is amortised over several rounds of waves and the plain raster's seven workgroups per CU win.  The endless variant (its
     // step kernel's reset tail is 4 us) the other way round: off up to 16,384 instances (230 / 230; the plain raster stores with
     // the cached policy there), on beyond, where the plain raster stores non-temporally as well (32,768: 242-244 / 233-234,
-    // 65,536: 245-248 / 239-242, 131,072: 256-257 / 236-252).  MEMGYM_SPOT_FUSE=0 / 1 (lab build) forces it off / on for both.
+    // 65,536: 245-248 / 239-242, 131,072: 256-257 / 236-252).  MEMGYM_SPOT_FUSE=0 / 1 (lab build) forces it off / on for both, in every format.
+    // The other formats (profiles/spot_chw.md; M env-steps/s fused / not, two runs each, the same session):
+    //   MG_OBS_U8_CYX, the uint8 frame's bytes: its thresholds.  Finite 16,384: 200.3-200.9 / 179.9-180.5, 65,536: 224.5-225.0 / 199.7-200.0; endless
+    //   65,536: 242.2-242.3 / 221.2-221.9 (16,384 and below stays on two launches like the uint8 frame, not measured fused).
+    //   Float formats: fused up to FUSE_MAX on BOTH ids.  Finite 16,384: bf16 120.3-120.7 / 110.9-111.1, f32 64.6-65.5 / 62.5-62.8; 65,536: bf16
+    //   141.2-141.4 / 141.5-142.0 (0.3 % below, within the unfused form's own two-run spread of 0.4 %), f32 76.8-77.0 / 76.1-76.4.  Endless 16,384: bf16
+    //   121.0-121.9 / 119.5-120.0, f32 65.4-66.7 / 64.8-66.1; 65,536: bf16 146.4-146.5 / 143.5-143.9, f32 77.3-77.7 / 77.4-77.5.  The stream-out
+    //   bounds these launches, so the reset tail saved shows at 16,384 and hardly at 65,536; no row lost.  f16 follows bf16 (the same kernel but for
+    //   the conversion instruction).  Beyond FUSE_MAX nothing is measured in these formats: two launches, as before.
     static constexpr int FUSE_MAX = 65536;
     // store flavour of the fused launch: it runs five workgroups per CU (the reset code's registers), where only the
     // non-temporal stream keeps up; MEMGYM_RASTER_NT forces (tuning only)
@@ -527,7 +556,9 @@ class SpotFamily : public Family {
     }
     bool fuse_resets() const {
         static const int forced = lab_forced("MEMGYM_SPOT_FUSE");
-        return forced >= 0 ? forced != 0 : (P_.endless ? n_ > RASTER_PLAIN_MAX : n_ <= FUSE_MAX);
+        if (forced >= 0) return forced != 0;
+        if (obs_format == MG_OBS_U8_XYC || obs_format == MG_OBS_U8_CYX) return P_.endless ? n_ > RASTER_PLAIN_MAX : n_ <= FUSE_MAX;
+        return n_ <= FUSE_MAX;
     }
 
     OptionSets<SpotOpt> sets_;

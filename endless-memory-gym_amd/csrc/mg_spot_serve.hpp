@@ -69,9 +69,27 @@ static_assert(SPOT_SVC_BATCH * (DISC_INTS * 4 + (int)sizeof(SpotCore)) <= FRAME_
 // FINAL (round 6): a call in the gymnasium vector convention.  The step kernel has stored a finishing instance's state and frame descriptor
 // "as after any other step" (valid = DESC_QUEUED): that descriptor IS the terminal frame's -- the service workgroup draws it into final_obs
 // before it resets the instance and draws the new episode's first frame into obs.  A kernel of its own; the measured ones are as they were.
-template <bool EN, bool BORDER, bool NT, bool FINAL = false>
+// FMT: the observation format of both targets (obs and final_obs), handed to store_frame at the three store sites: the draw lambda, the FINAL
+// loop and -- through the lambda -- the frame walk.  MG_OBS_U8_XYC is the default: those sixteen forms keep their names and their code.  The float
+// formats ignore NT and BUF in store_frame and are launched with NT = false only (mg_spot.hip).
+// MG_OBS_U8_CYX -- store_frame is then a collective of the 256 lanes with two barriers that transposes the LDS frame in place (frame_to_cyx's
+// caller contract, mg_stream_out.hpp):
+//   * uniform flow.  Every store site sits behind a __syncthreads() of this kernel, which already needs what the collective needs.  `service`,
+//     `count`, `batch` and `base` come from blockIdx, the kernel arguments and one scalar load (queue_count): the same in every lane.  The two k
+//     loops run to min(batch, count - base), uniform; the `tid < 16 * batch` branch between them holds no store site.  The frame walk's `valid != 1u`
+//     is a scalar load through the constant address space: a scalar decision.
+//   * nobody reads the transposed frame.  A store site is always compose -> barrier -> recycle (the hole mask behind the frame, not the frame) ->
+//     store_frame -> barrier, and the next user of the frame area is either another compose, which writes all of the frame before anything reads
+//     it (the Composer concept, mg_raster.hpp), or the service workgroup's reset: that one WRITES its disc lists and SpotCore records into the
+//     frame area (disc_slot, `s = io.core[i]`) before it reads them and never looks at what a frame left there -- in this format as in the others,
+//     where the area holds the last [x][y][c] frame at that point.  What the reset leaves in the area is in turn overwritten by the next compose.
+//   * 256 lanes: dim3(256) is the only block size this kernel is launched with (__launch_bounds__(256, ...)).
+template <bool EN, bool BORDER, bool NT, bool FINAL = false, int FMT = MG_OBS_U8_XYC>
 __global__ __launch_bounds__(256, MG_SPOT_SERVE_OCC) void spot_raster_serve_kernel(SpotServeArgs a) {
     typedef SpotComposerT<BORDER> Composer;
+    // the float forms call a store_frame instantiation of their own (SITE, mg_stream_out.hpp): sharing the raster kernels' moved THEIR code
+    // (profiles/spot_chw.md); the one-byte forms share it as the uint8 form always has
+    constexpr int SITE = (FMT == MG_OBS_U8_XYC || FMT == MG_OBS_U8_CYX) ? 0 : 2;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const RasterCtx R = make_ctx(smem, a.A);
     const int tid = threadIdx.x;
@@ -91,7 +109,7 @@ __global__ __launch_bounds__(256, MG_SPOT_SERVE_OCC) void spot_raster_serve_kern
         Composer::compose(from + env, Pq, R);
         __syncthreads();
         Composer::recycle(R);
-        store_frame<MG_OBS_U8_XYC, NT, true>(smem, obs, env, tid);
+        store_frame<FMT, NT, true, SITE>(smem, obs, env, tid);
         __syncthreads();
     };
     if (service) {
@@ -111,7 +129,7 @@ __global__ __launch_bounds__(256, MG_SPOT_SERVE_OCC) void spot_raster_serve_kern
                     Composer::compose(cdescs + env, Pq, R);
                     __syncthreads();
                     Composer::recycle(R);
-                    store_frame<MG_OBS_U8_XYC, NT, true>(smem, fin, env, tid);
+                    store_frame<FMT, NT, true, SITE>(smem, fin, env, tid);
                     __syncthreads();
                 }
             }

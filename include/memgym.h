@@ -45,9 +45,10 @@ typedef struct mg_info_buffers {
      * buffer (same format and shape as obs_dev; rows of other instances are left untouched) while obs_dev row i holds
      * the first observation of the new episode.  MG_OBS_U8_XYC observations, one option set: the step's own launches draw both frames (round 6;
      * Endless-MysteryPath: the terminal frames by one sparse raster launch behind them) -- 0-4 % of a step for eight env ids, 11-12 % for
-     * SearingSpotlights-v0 and Endless-MysteryPath-v0; the mortar family (ONE launch per step) and the finite Mystery Path ids do the same in
-     * every observation format.  Otherwise (the other formats on the spotlight family and Endless-MysteryPath-v0, per-instance option sets, the
-     * mortar family under graph capture): a step without auto-reset, the terminal rows copied, a masked reset whose frames a sparse raster
+     * SearingSpotlights-v0 and Endless-MysteryPath-v0; the mortar family (ONE launch per step), the finite Mystery Path ids and the
+     * spotlight family (its fused raster / reset launch) do the same in every observation format.  Otherwise (the other formats on
+     * Endless-MysteryPath-v0, per-instance option sets, under graph capture the mortar family and the spotlight family's image-order
+     * formats): a step without auto-reset, the terminal rows copied, a masked reset whose frames a sparse raster
      * launch draws; mg_debug_counter "final_obs_generic_steps" counts those calls. */
     void* final_obs_dev;
     /* Optional: the step reward of every instance as the reference computes it -- a Python float, i.e. a double
@@ -148,10 +149,11 @@ int64_t mg_capacity(mg_env* env, const char* what);
  * The conversion is fused into the raster kernel's stream-out (no second pass over HBM).  mg_obs_bytes returns the
  * bytes per instance of the current format.
  * Which arrangements a format takes: the mortar family's one-launch step and the finite Mystery Path ids' step + raster / path-service
- * launches (and the forms of both that keep terminal observations) run for all five formats.  The fused launches of the spotlight
- * family and of Endless-MysteryPath-v0 (deferred resets, served queues, terminal frames drawn by the step's own launches) exist for
- * MG_OBS_U8_XYC alone: there the other four formats step in separate logic and raster launches and keep terminal observations on
- * mg_step's generic path. */
+ * launches (and the forms of both that keep terminal observations) run for all five formats, and so does the spotlight family's
+ * fused raster / reset launch (deferred resets served inside the raster launch, terminal frames drawn there; which sizes take it
+ * without kept terminal observations is a measured choice per format, csrc/mg_spot.hip fuse_resets()).  The fused launches of
+ * Endless-MysteryPath-v0 (served queues, records ahead of time) exist for MG_OBS_U8_XYC alone: there the other four formats step in
+ * separate logic and raster launches and keep terminal observations on mg_step's generic path. */
 #define MG_OBS_U8_XYC 0
 #define MG_OBS_F32_CYX 1
 #define MG_OBS_F16_CYX 2
@@ -346,7 +348,8 @@ int mg_enable_peer_access(int device, int peer_device);
  * (Endless-MysteryPath: first segments of NEXT episodes generated ahead of time, which a finishing instance's own step turns into its
  * reset -- EndlessMysteryPathEnv.reset, endless_mystery_path.py:195-280, without a queue entry); "emp_own_resets" (such resets; counted
  * by the lab build only).  "one_launch_steps" (mortar family): mg_step calls of this handle that went out as the one-launch kernel, counted
- * on the host.  "final_obs_generic_steps" (every id): mg_step calls of this handle that kept terminal observations
+ * on the host.  "spot_fused_steps" (spotlight family): mg_step calls of this handle that went out as the fused raster / reset launch
+ * (spot_raster_serve_kernel), counted on the host.  "final_obs_generic_steps" (every id): mg_step calls of this handle that kept terminal observations
  * (mg_info_buffers.final_obs_dev, autoreset) on the generic path -- a step without auto-reset, a copy of the finished rows, a masked reset --
  * instead of inside the step's own launches, counted on the host.  Unknown name: -1.  Synchronous. */
 int mg_debug_counter(mg_env* env, const char* name, int64_t* value);

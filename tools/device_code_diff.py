@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""tools/device_code_diff.py PARENT_TREE NEW_TREE  -- did a host-side change move any device code?
+"""tools/device_code_diff.py PARENT_TREE NEW_TREE [--rename REGEX=REPLACEMENT ...]  -- did a host-side change move any device code?
 
 Compiles every csrc/*.hip of both trees to device-only gfx950 assembly (hipcc --cuda-device-only -S), once with the product
 flags and once with -DMG_LAB, each file with the EXTRA_FLAGS of its own tree's __graft_entry__.py, and compares per symbol:
@@ -8,6 +8,9 @@ flags and once with -DMG_LAB, each file with the EXTRA_FLAGS of its own tree's _
   * each function body is equal once the function ordinal in local labels (.LBB<k>_, .Lfunc_end<k>, ... -- it only encodes the
     order of emission) is normalised,
   * each device global (size, alignment, initialiser) is equal.
+--rename: applied to the PARENT's assembly before it is parsed, for a kernel template that gained a defaulted parameter -- the Itanium mangling
+spells defaulted template arguments out, so every old instantiation has a new symbol and would be listed as "only in PARENT" / "only in NEW"
+with nothing said about its code.  --all: every report line, not the first 40 per file.
 Prints one summary line per file and build, exits 1 if anything differs.  A tool, not a test: it compiles twenty times."""
 import concurrent.futures
 import glob
@@ -93,9 +96,19 @@ def compare(what, a, b, report):
 
 
 def main():
-    if len(sys.argv) != 3:
+    args, renames, show_all = [], [], False
+    it = iter(sys.argv[1:])
+    for a in it:
+        if a == "--rename":
+            rx, _, repl = next(it, "").partition("=")
+            renames.append((re.compile(rx), repl))
+        elif a == "--all":
+            show_all = True
+        else:
+            args.append(a)
+    if len(args) != 2:
         sys.exit(__doc__)
-    parent, new = (os.path.abspath(p) for p in sys.argv[1:3])
+    parent, new = (os.path.abspath(p) for p in args)
     names = lambda t: sorted(os.path.basename(f) for f in glob.glob(os.path.join(t, "endless-memory-gym_amd", "csrc", "*.hip"))
                              if not os.path.basename(f).startswith("_"))
     if names(parent) != names(new):
@@ -111,13 +124,19 @@ def main():
         total_bad = 0
         for src in names(new):
             for lab in (False, True):
-                fa, da, ga = parse(jobs[(src, lab, "parent")].result())
+                parent_asm = jobs[(src, lab, "parent")].result()
+                if renames:
+                    text = open(parent_asm).read()
+                    for rx, repl in renames:
+                        text = rx.sub(repl, text)
+                    open(parent_asm, "w").write(text)
+                fa, da, ga = parse(parent_asm)
                 fb, db, gb = parse(jobs[(src, lab, "new")].result())
                 report = []
                 bad = compare("kernel descriptor", da, db, report) + compare("function", fa, fb, report) + compare("global", ga, gb, report)
                 total_bad += bad
                 print("%-18s %-7s %3d kernels, %3d functions, %2d globals: %d differ" % (src, "lab" if lab else "product", len(db), len(fb), len(gb), bad))
-                print("\n".join(report[:40]), end="\n" if report else "")
+                print("\n".join(report if show_all else report[:40]), end="\n" if report else "")
     print("device code: %s (assembly kept in %s)" % ("IDENTICAL" if not total_bad else "%d DIFFERENCES" % total_bad, tmp))
     sys.exit(1 if total_bad else 0)
 

@@ -3,7 +3,9 @@
 resets drawn by the mask, Endless-MysteryPath's masked resets from records ahead of time) in lock-step with a handle of the same id that
 steps with the same-step auto-reset the parity suite pins to the oracle: observations, rewards and dones must be equal after EVERY step,
 the generator's words of sample instances at the end; terminal observations must differ from the new episode's first frame only where an
-episode really ended.  Sizes choose the large-launch arrangements."""
+episode really ended.  Sizes choose the large-launch arrangements.
+VECTOR_SOAK_ONLY=ID[,ID]: these ids only; VECTOR_SOAK_FORMAT: the observation format of both handles (default u8_xyc); VECTOR_SOAK_N: the
+number of instances of every chosen id instead of the table's."""
 import os
 import sys
 
@@ -21,10 +23,13 @@ CASES = [("MortarMayhem-Grid-v0", 65536), ("MortarMayhem-v0", 20001), ("Endless-
          ("MortarMayhemB-Grid-v0", 12289), ("MortarMayhemB-v0", 8193)]
 if os.environ.get("VECTOR_SOAK_ONLY"):
     CASES = [c for c in CASES if c[0] in os.environ["VECTOR_SOAK_ONLY"].split(",")]
+fmt = os.environ.get("VECTOR_SOAK_FORMAT", "u8_xyc")
+if os.environ.get("VECTOR_SOAK_N"):
+    CASES = [(c[0], int(os.environ["VECTOR_SOAK_N"])) for c in CASES]
 vis = (lambda o: o["visual_observation"] if isinstance(o, dict) else o)
 for env_id, n in CASES:
-    venv = GymnasiumVectorEnv(env_id, n, device=0)
-    fused = memory_gym_amd.make(env_id, num_envs=n, device=0)
+    venv = GymnasiumVectorEnv(env_id, n, device=0, obs_format=fmt)
+    fused = memory_gym_amd.make(env_id, num_envs=n, device=0, obs_format=fmt)
     adim = fused.action_dim
     n_act = 4 if adim == 1 else 3
     o1, _ = venv.reset(seed=5)
@@ -81,6 +86,6 @@ for env_id, n in CASES:
         assert np.array_equal(venv.env.rng_words(i), fused.rng_words(i)), (env_id, i)
     venv.env.check_errors()
     fused.check_errors()
-    print("ok %-30s %6d instances x %d steps, %d episodes finished: vector convention == auto-reset step" % (env_id, n, steps, finished), flush=True)
+    print("ok %-30s %6d instances x %d steps in %s, %d episodes finished: vector convention == auto-reset step" % (env_id, n, steps, fmt, finished), flush=True)
     venv.close()
     fused.close()
