@@ -21,8 +21,10 @@
 //   MysteryPath-v0          the same two launches, defer 2: a wave serves up to HYBRID_INLINE resets itself and queues them all once it has more
 //   Endless-MysteryPath-v0  emp_step_kernel: a lane per instance, due segments and most resets become queue entries -> emp_raster_serve_kernel: service workgroups take
 //                           the entries and draw those instances' frames, background workgroups generate owed segments and the next episode's first (up to 20,480
-//                           instances: entries of the service waves instead), the others draw the frames
-//   Terminal observations kept (mg_info_buffers.final_obs_dev): the <FINAL> forms of the same launches; endless: plus one raster_sparse_kernel for the terminal frames.
+//                           instances: entries of the service waves instead), the others draw the frames -- in all five observation formats
+//                           (emp_raster_serve_kernel<FMT, EMP_NT, FINAL>; steps_fused(): not with per-instance option sets or BIG sprites)
+//   Terminal observations kept (mg_info_buffers.final_obs_dev): the <FINAL> forms of the same launches; endless: plus one raster_sparse_kernel for the terminal frames,
+//   in the handle's format.
 #include <memory>
 
 #include "mg_atlas_v1.hpp"
@@ -240,7 +242,7 @@ class MysteryFamily : public Family {
             // a masked reset(seed=None) of a handle whose steps run the fused arrangement: reset like the auto-reset step resets (lazy
             // segments, records ahead of time: emp_masked_reset_kernel); lab MEMGYM_EMP_MASKED_FAST=0: through the queue server like any other
             static const bool fast_wanted = lab_flag("MEMGYM_EMP_MASKED_FAST", true);
-            const bool fast = fast_wanted && mask && !seeds && !ps && lazy_wanted_ && fuse_serve() && obs_format == MG_OBS_U8_XYC && !big_sprites_;
+            const bool fast = fast_wanted && mask && !seeds && lazy_wanted_ && steps_fused();
             P_.lazy = fast ? 1 : 0;  // (otherwise an explicit reset generates all three segments; whatever an old episode is owed comes first)
             P_.pre = (fast && pre_wanted_) ? 1 : 0;
             P_.lazy_append = 0;
@@ -278,7 +280,7 @@ class MysteryFamily : public Family {
             // lazy initial segments need the fused launch (its frame workgroups carry the background jobs); any other path
             // first generates what earlier fused steps left owed
             // (per-instance option sets: the plain arrangement -- step kernel, queue server, raster -- whose kernels have a <PS> form)
-            const bool fused = fuse_serve() && obs_format == MG_OBS_U8_XYC && !ps && !big_sprites_;
+            const bool fused = steps_fused();
             P_.lazy = (fused && lazy_wanted_) ? 1 : 0;
             P_.pre = (P_.lazy && pre_wanted_) ? 1 : 0;
             static const int lazy_append = lab_int("MEMGYM_EMP_LAZY_APPEND", 1);
@@ -312,17 +314,28 @@ class MysteryFamily : public Family {
                 auto raster_serve = [&](auto kernel, int wgs, int bg) {
                     launch(kernel, dim3(wgs), dim3(256), RASTER_LDS, s, desc_.p, atlas_->dev(), obs, n_, P_, io(), reward, done, gt, ib, autoreset, svc, bg, turn_);
                 };
-                with_bool(nt, [&](auto NT) {
-                    with_bool(keep_final, [&](auto FINAL) {
-                        raster_serve(emp_raster_serve_kernel<MG_OBS_U8_XYC, decltype(NT)::value, decltype(FINAL)::value>, grid, bgw);
+                // (format x non-temporal x kept terminal observations: four forms in each of the two one-byte formats; the float formats' stream-out
+                // has no non-temporal flavour -- two forms each, EMP_NT = false, whatever `nt` says)
+                auto in_format = [&](bool want_nt, bool final, int wgs, int bg) {
+                    with_obs_format(obs_format, [&](auto F) {
+                        constexpr int FMT = decltype(F)::value;
+                        constexpr bool ONE_BYTE = FMT == MG_OBS_U8_XYC || FMT == MG_OBS_U8_CYX;
+                        with_bool(ONE_BYTE && want_nt, [&](auto NT) {
+                            with_bool(final, [&](auto FINAL) {
+                                if constexpr (ONE_BYTE || !decltype(NT)::value)
+                                    raster_serve(emp_raster_serve_kernel<FMT, decltype(NT)::value, decltype(FINAL)::value>, wgs, bg);
+                            });
+                        });
                     });
-                });
+                };
+                in_format(nt, keep_final, grid, bgw);
                 check_launch();
+                ++emp_fused_steps_;
                 if (keep_final)  // every finished instance's flag is in `done` by now (the service workgroups wrote the last of them)
-                    launch_raster_sparse<MysteryComposer>(tdesc_.p, atlas_->dev(), ib.final_obs_dev, MG_OBS_U8_XYC, n_, s, done);
+                    launch_raster_sparse<MysteryComposer>(tdesc_.p, atlas_->dev(), ib.final_obs_dev, obs_format, n_, s, done);
                 prof.end(1, s);
                 if (bgw_later)  // (grid = service + background workgroups only: no frames; the queue is empty by now)
-                    raster_serve(emp_raster_serve_kernel<MG_OBS_U8_XYC, false>, svc + bgw_later, bgw_later);
+                    in_format(false, false, svc + bgw_later, bgw_later);
 #ifdef MG_LAB_EMP_CLOCK  // diagnosis: is the next logic kernel slow because the L2 is full of dirty observation lines?
                 static const int wb = lab_int("MEMGYM_LAB_WBL2", 0);
                 if (wb) launch(lab_wbl2_kernel, dim3(wb), dim3(64), 0, s);
@@ -372,6 +385,10 @@ class MysteryFamily : public Family {
         launch_checked(mystery_gt64_kernel, dim3((n_ + 255) / 256), dim3(256), 0, s, n_, core_.p, out);
     }
     bool debug_counter(const std::string& name, int64_t* out) override {
+        if (name == "emp_fused_steps") {  // step() calls that went out as emp_raster_serve_kernel since the handle was created (host-side count)
+            *out = emp_fused_steps_;
+            return true;
+        }
         if (name == "emp_segments_sum" || name == "emp_segments_max" || name == "emp_falloff_max") {  // a scan of the state records as they stand
             std::vector<MysteryCore> h(n_);
             MG_HIP(hipDeviceSynchronize());
@@ -420,6 +437,7 @@ class MysteryFamily : public Family {
     void raster_debug(void* frames, hipStream_t s) override;
 
    private:
+    int64_t emp_fused_steps_ = 0;  // debug_counter("emp_fused_steps")
     // instance-carrying lanes per wave (see instance_of_lane); MEMGYM_MYSTERY_LPW overrides for tuning
     int lpw() const {
         static const int forced = lab_int("MEMGYM_MYSTERY_LPW", 0);
@@ -443,6 +461,17 @@ class MysteryFamily : public Family {
         static const bool on = lab_flag("MEMGYM_EMP_FUSE", true);
         return on;
     }
+    // This handle steps in the fused arrangement: emp_step_kernel + emp_raster_serve_kernel in the handle's format.  What comes with it comes
+    // together or not at all: lazy initial segments, records ahead of time (EMP_PRE), the fast masked reset (emp_masked_reset_kernel), terminal
+    // observations kept by the step's own launches (keeps_final_obs).  Per-instance option sets and BIG agent sprites keep the plain
+    // arrangement (step kernel, queue server, raster), whose kernels have the <PS> forms and the BIG composer.
+    // No observation format is excluded, and that is a measured choice (profiles/emp_chw.md; the parent's plain arrangement against the fused
+    // one, A/B/A/B on one box, us per step at 32,768 / 16,384 instances under random actions, auto-reset leg): u8_chw 232-233 -> 153-155 /
+    // 158-159 -> 102-103, bf16_chw 322-323 -> 237-239 / 218-223 -> 174-175, f16_chw like bf16_chw, f32_chw 531 -> 444 / 328-329 -> 289-296; with
+    // terminal observations kept and under a path-following policy the gain is larger still.  The image-order forms need 16-48 B more scratch per
+    // lane than their u8_xyc siblings (736-784 B against 736-752 B) at the same 80 VGPRs and six workgroups per CU.  The lab build's
+    // MEMGYM_EMP_FUSE=0 puts a handle of any format on the plain arrangement.
+    bool steps_fused() const { return fuse_serve() && !sets_.per_set() && !big_sprites_; }
     // MEMGYM_EMP_RESET_LANES=0: a full reset through the queue server, one wave per instance (round 1)
     bool reset_by_lanes() const {
         static const bool on = lab_flag("MEMGYM_EMP_RESET_LANES", true);
@@ -475,7 +504,7 @@ class MysteryFamily : public Family {
     // DESCRIPTORS behind, one sparse raster launch draws them -- lab MEMGYM_EMP_FINAL_FUSED=0: the generic path.)
     bool keeps_final_obs(hipStream_t) override {
         static const bool wanted = lab_flag("MEMGYM_MYSTERY_FINAL_FUSED", true), emp_wanted = lab_flag("MEMGYM_EMP_FINAL_FUSED", true);
-        if (P_.endless) return emp_wanted && fuse_serve() && obs_format == MG_OBS_U8_XYC && !big_sprites_ && !sets_.per_set();
+        if (P_.endless) return emp_wanted && steps_fused();
         return wanted && !big_sprites_ && !sets_.per_set() && defer_mode() != 0;
     }
     MysteryIO io() {

@@ -43,12 +43,13 @@ typedef struct mg_info_buffers {
     /* Optional (gymnasium 0.29 VectorEnv convention, info["final_observation"]): with autoreset != 0 and this pointer
      * set, mg_step also writes the TERMINAL observation of every instance that finished in this call to row i of this
      * buffer (same format and shape as obs_dev; rows of other instances are left untouched) while obs_dev row i holds
-     * the first observation of the new episode.  MG_OBS_U8_XYC observations, one option set: the step's own launches draw both frames (round 6;
-     * Endless-MysteryPath: the terminal frames by one sparse raster launch behind them) -- 0-4 % of a step for eight env ids, 11-12 % for
-     * SearingSpotlights-v0 and Endless-MysteryPath-v0; the mortar family (ONE launch per step), the finite Mystery Path ids and the
-     * spotlight family (its fused raster / reset launch) do the same in every observation format.  Otherwise (the other formats on
-     * Endless-MysteryPath-v0, per-instance option sets, under graph capture the mortar family and the spotlight family's image-order
-     * formats): a step without auto-reset, the terminal rows copied, a masked reset whose frames a sparse raster
+     * the first observation of the new episode.  One option set: the step's own launches draw both frames, for every env id in every
+     * observation format (round 6 for MG_OBS_U8_XYC: 0-4 % of a step for eight env ids, 11-12 % for SearingSpotlights-v0 and
+     * Endless-MysteryPath-v0) -- the mortar family's ONE launch per step, the finite Mystery Path ids' step + raster / path-service launches, the
+     * spotlight family's fused raster / reset launch, and Endless-MysteryPath-v0's step + raster / service launches with one sparse raster
+     * launch behind them that draws the terminal frames from the descriptors they leave.  Otherwise (per-instance option sets; agent sprites
+     * too big for registers, the agent_scale option, on the Mystery Path family; under graph capture the mortar family and the spotlight
+     * family's image-order formats): a step without auto-reset, the terminal rows copied, a masked reset whose frames a sparse raster
      * launch draws; mg_debug_counter "final_obs_generic_steps" counts those calls. */
     void* final_obs_dev;
     /* Optional: the step reward of every instance as the reference computes it -- a Python float, i.e. a double
@@ -151,9 +152,10 @@ int64_t mg_capacity(mg_env* env, const char* what);
  * Which arrangements a format takes: the mortar family's one-launch step and the finite Mystery Path ids' step + raster / path-service
  * launches (and the forms of both that keep terminal observations) run for all five formats, and so does the spotlight family's
  * fused raster / reset launch (deferred resets served inside the raster launch, terminal frames drawn there; which sizes take it
- * without kept terminal observations is a measured choice per format, csrc/mg_spot.hip fuse_resets()).  The fused launches of
- * Endless-MysteryPath-v0 (served queues, records ahead of time) exist for MG_OBS_U8_XYC alone: there the other four formats step in
- * separate logic and raster launches and keep terminal observations on mg_step's generic path. */
+ * without kept terminal observations is a measured choice per format, csrc/mg_spot.hip fuse_resets()).  Endless-MysteryPath-v0's fused
+ * raster / service launch (served queues, lazy initial segments, records ahead of time, the fast masked reset) runs for all five formats
+ * as well: no format is excluded, a measured choice (csrc/mg_mystery.hip steps_fused(), profiles/emp_chw.md).  No id steps unfused because of its
+ * format; what keeps the plain launches is per-instance option sets and, on the Mystery Path family, agent sprites too big for registers. */
 #define MG_OBS_U8_XYC 0
 #define MG_OBS_F32_CYX 1
 #define MG_OBS_F16_CYX 2
@@ -349,7 +351,8 @@ int mg_enable_peer_access(int device, int peer_device);
  * reset -- EndlessMysteryPathEnv.reset, endless_mystery_path.py:195-280, without a queue entry); "emp_own_resets" (such resets; counted
  * by the lab build only).  "one_launch_steps" (mortar family): mg_step calls of this handle that went out as the one-launch kernel, counted
  * on the host.  "spot_fused_steps" (spotlight family): mg_step calls of this handle that went out as the fused raster / reset launch
- * (spot_raster_serve_kernel), counted on the host.  "final_obs_generic_steps" (every id): mg_step calls of this handle that kept terminal observations
+ * (spot_raster_serve_kernel), counted on the host.  "emp_fused_steps" (Endless-MysteryPath): mg_step calls of this handle that went out as the
+ * fused raster / service launch (emp_raster_serve_kernel), counted on the host.  "final_obs_generic_steps" (every id): mg_step calls of this handle that kept terminal observations
  * (mg_info_buffers.final_obs_dev, autoreset) on the generic path -- a step without auto-reset, a copy of the finished rows, a masked reset --
  * instead of inside the step's own launches, counted on the host.  Unknown name: -1.  Synchronous. */
 int mg_debug_counter(mg_env* env, const char* name, int64_t* value);
