@@ -3,10 +3,9 @@ oracle alone says about them (no GPU): that the runs reach what the GPU tests ar
 step with more finished instances than one service round of the small launch takes (EMP_SVC_WGS_SMALL x 4 waves = 3,072), and, in the lane
 regime (more than 20,480 instances), a step with more than EMP_SVC_WGS_PRE x 4 = 256 of them.
 
-The oracle's runs are computed once per case and shared by the formats (oracle_run); nothing changes them afterwards."""
-import functools
-
-import numpy as np
+The oracle's runs are computed once per case and shared by the formats (tests/chw_referee.py oracle_run: seeds arange(n) + 31, actions from
+PCG64(6)); nothing changes them afterwards."""
+from chw_referee import frozen, oracle_run
 
 ENV_ID = "Endless-MysteryPath-v0"
 # Episodes that end within nine steps: max_steps truncates, three points of stamina let an agent off the path end them earlier (both kinds of ending in one run).
@@ -25,52 +24,13 @@ ONE_ROUND_PRE = 64 * 4                 # EMP_SVC_WGS_PRE x 4
 FORCED = dict(n=96, steps=40)          # case 4
 
 
-def seeds_of(n):
-    return np.arange(n, dtype=np.int64) + 31
-
-
-def actions_of(prng, n):
-    return prng.integers(0, 4, (n,)).astype(np.int32)
-
-
-@functools.lru_cache(maxsize=1)
-def oracle_run(n, steps, short, frames):
-    """`steps` auto-reset steps of n instances under SHORT (short=True) or IN_STEP, seeds arange(n) + 31, actions from PCG64(6).
-    -> (seeds, first, run): first = the reset frames (frames=True: two batches in lock step, one returns the frames, one the digests) or their
-    digests; run = per step (actions, frames or None, digest, final_digest, reward, done, ground_truth float32)."""
-    import oracle_lib
-
-    opts = SHORT if short else IN_STEP
-    dig = oracle_lib.OracleBatch(ENV_ID, n, options=opts)
-    pix = oracle_lib.OracleBatch(ENV_ID, n, options=opts) if frames else None
-    seeds = seeds_of(n)
-    first = dig.reset_digest(seeds)
-    if pix:
-        first = pix.reset(seeds)
-    prng = np.random.Generator(np.random.PCG64(6))
-    run = []
-    for _ in range(steps):
-        a = actions_of(prng, n)
-        dg, fdg, rew, done = dig.step_digest(a, autoreset=True)
-        fr = None
-        if pix:
-            fr, rew2, done2 = pix.step(a, autoreset=True)
-            assert np.array_equal(rew, rew2) and np.array_equal(done, done2)
-        gt = np.stack([e.gt() for e in dig.envs]).astype(np.float32)
-        run.append((a, fr, dg, fdg, rew, done, gt))
-    dig.close()
-    if pix:
-        pix.close()
-    return seeds, first, run
-
-
 def most_in_one_step(run):
     return max(int(s[5].sum()) for s in run)
 
 
 def test_case_1_sees_terminal_and_running_rows():
     n, steps = TERMINAL["n"], TERMINAL["steps"]
-    run = oracle_run(n, steps, True, False)[2]
+    run = oracle_run(ENV_ID, n, steps, frozen(SHORT), False)[2]
     n_done = sum(int(s[5].sum()) for s in run)
     n_running = sum(int((s[5] == 0).sum()) for s in run)
     assert n_done >= 6 * n, n_done  # max_steps = 9 over 60 steps: six endings per instance at the least
@@ -79,16 +39,16 @@ def test_case_1_sees_terminal_and_running_rows():
 
 def test_case_2_fills_more_than_one_service_round():
     assert ROUNDS["n"] % 64 != 0
-    run = oracle_run(ROUNDS["n"], ROUNDS["steps"], False, False)[2]
+    run = oracle_run(ENV_ID, ROUNDS["n"], ROUNDS["steps"], frozen(IN_STEP), False)[2]
     assert most_in_one_step(run) > ONE_ROUND, most_in_one_step(run)
 
 
 def test_case_3_fills_more_than_one_service_round_of_the_lane_regime():
     assert LANES["n"] > 20480 and LANES["n"] % 64 != 0 and LANES["n"] % 256 != 0
-    run = oracle_run(LANES["n"], LANES["steps"], False, False)[2]
+    run = oracle_run(ENV_ID, LANES["n"], LANES["steps"], frozen(IN_STEP), False)[2]
     assert most_in_one_step(run) > ONE_ROUND_PRE, most_in_one_step(run)
 
 
 def test_case_4_resets_instances():
-    run = oracle_run(FORCED["n"], FORCED["steps"], True, False)[2]
+    run = oracle_run(ENV_ID, FORCED["n"], FORCED["steps"], frozen(SHORT), False)[2]
     assert sum(int(s[5].sum()) for s in run) > FORCED["n"]

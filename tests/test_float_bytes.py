@@ -1,28 +1,15 @@
 """CPU: a float observation names its byte.  The float stream-out formats hold byte / 255 as float32, or that quotient rounded to float16 /
 bfloat16 (include/memgym.h MG_OBS_F32_CYX / F16_CYX / BF16_CYX); round(x * 255) recovers the byte from every one of the 3 x 256 values, so
-a test may turn float rows back into the uint8 [x][y][c] frame the oracle digests (float_rows_to_bytes; tests/test_gpu_chw_final.py).
+a test may turn float rows back into the uint8 [x][y][c] frame the oracle digests (tests/chw_referee.py: unit_values, float_rows_to_bytes).
 
 Why it holds: neighbouring bytes are 1 / 255 = 3.9e-3 apart; bfloat16 keeps 8 significant bits, so below 1 its rounding error is at most
 2^-9 = 1.95e-3 relative to a value < 1, i.e. less than half that spacing, and x * 255 lies within 0.5 of the byte."""
 import numpy as np
 import pytest
 
+from chw_referee import float_rows_to_bytes, unit_values
+
 FORMATS = ("f32_chw", "f16_chw", "bf16_chw")
-
-
-def unit_values(fmt):
-    """torch tensor [256]: what the format stores for the bytes 0 .. 255"""
-    import torch
-
-    q = torch.from_numpy(np.arange(256, dtype=np.float32) / np.float32(255))
-    return q.to({"f32_chw": torch.float32, "f16_chw": torch.float16, "bf16_chw": torch.bfloat16}[fmt])
-
-
-def float_rows_to_bytes(rows):
-    """float tensor [k][3][84 y][84 x] (any of the three formats, any device) -> uint8 tensor [k][84 x][84 y][3], the oracle's frame order"""
-    import torch
-
-    return torch.round(rows.to(torch.float32) * 255.0).to(torch.uint8).permute(0, 3, 2, 1).contiguous()
 
 
 @pytest.mark.parametrize("fmt", FORMATS)

@@ -2,68 +2,24 @@
 csrc/mg_mystery_endless_launch.hpp) in the image-order formats (bf16_chw, f16_chw, f32_chw, u8_chw), with and without kept terminal observations,
 and what comes with the fused arrangement: lazy initial segments, records ahead of time, the fast masked reset.
 
-Comparisons are exact, as in tests/test_gpu_chw_final.py: a float frame is the oracle's uint8 frame through the 256-entry table of
-tests/test_float_bytes.py.  Which launches ran is asserted from the host-side counters of mg_debug_counter: "final_obs_generic_steps" (mg_step's
-generic terminal-observation branch) and "emp_fused_steps" (step() calls that went out as emp_raster_serve_kernel).  The inputs, and what the
-oracle alone says about them, are in tests/test_emp_chw_inputs.py."""
+Comparisons are exact and made by tests/chw_referee.py: a float frame is the oracle's uint8 frame through its 256-entry table.  Which launches
+ran is asserted from the host-side counters of mg_debug_counter: "final_obs_generic_steps" (mg_step's generic terminal-observation branch) and
+"emp_fused_steps" (step() calls that went out as emp_raster_serve_kernel).  The inputs, and what the oracle alone says about them, are in
+tests/test_emp_chw_inputs.py."""
 import numpy as np
 import pytest
 
-from test_emp_chw_inputs import ENV_ID, FORCED, IN_STEP, LANES, ONE_ROUND, ONE_ROUND_PRE, ROUNDS, SHORT, TERMINAL, oracle_run
-from test_gpu_chw_final import SENTINEL, converted, rows_to_bytes
+from chw_referee import (CHW, SENTINEL, clones, converted, lock_step_with_a_twin, lock_step_with_the_oracle, replay_captured, rows_to_bytes,
+                         same_steps, two_option_sets_keep_the_generic_path)
+from test_emp_chw_inputs import ENV_ID, FORCED, IN_STEP, LANES, ONE_ROUND, ONE_ROUND_PRE, ROUNDS, SHORT, TERMINAL
 
 pytestmark = pytest.mark.gpu
-
-CHW = ("bf16_chw", "f16_chw", "f32_chw", "u8_chw")
-
-
-def lock_step_with_the_oracle(fmt, n, steps, short, frames, final=True):
-    """Every step against the oracle: frames (frames=True: byte for byte, else by digest), rewards, dones, ground truth and, final=True, terminal
-    rows by digest and sentinel rows.  -> (finished rows seen, running rows seen, most finished in one step, the handle, still open)"""
-    import frame_digest as fd
-    import memory_gym_amd
-    import torch
-
-    opts = SHORT if short else IN_STEP
-    seeds, first, run = oracle_run(n, steps, short, frames)
-    env = memory_gym_amd.make(ENV_ID, num_envs=n, device=0, obs_format=fmt, final_observation=final)
-
-    def same_frames(obs, want_frames, want_digest):
-        if frames:
-            return torch.equal(obs.cpu(), converted(fmt, want_frames))
-        b = rows_to_bytes(fmt, obs)
-        return torch.equal(converted(fmt, b), obs) and len(fd.differing(fd.digest_torch(b), want_digest)) == 0
-
-    obs = env.reset(seed=seeds, options=opts)[0]
-    assert same_frames(obs, first, first), "%s: reset frames differ from the oracle's" % fmt
-    n_done = n_running = most = 0
-    for t, (a, fr, dg, fdg, rew, done, gt) in enumerate(run):
-        if final:
-            env.final_obs.fill_(SENTINEL[fmt])
-        obs, r, d, _, info = env.step(a)
-        d_host = d.cpu().numpy()
-        assert np.array_equal(d_host, done.astype(bool)), "%s: dones differ at step %d" % (fmt, t)
-        assert np.array_equal(r.cpu().numpy(), rew.astype(np.float32)), "%s: rewards differ at step %d" % (fmt, t)
-        assert same_frames(obs, fr, dg), "%s: frames differ from the oracle's at step %d" % (fmt, t)
-        assert np.array_equal(info["ground_truth"].cpu().numpy(), gt), "%s: ground truth differs at step %d" % (fmt, t)
-        if final:
-            rows = info["final_observation"]
-            if d_host.any():
-                b = rows_to_bytes(fmt, rows[d])
-                assert len(fd.differing(fd.digest_torch(b), fdg[d_host])) == 0, "%s: terminal frames differ from the oracle's at step %d" % (fmt, t)
-                assert torch.equal(converted(fmt, b), rows[d]), "%s: a terminal row holds a value no byte maps to (step %d)" % (fmt, t)
-            assert bool((rows[~d] == SENTINEL[fmt]).all()), "%s: a row of a running instance was written at step %d" % (fmt, t)
-        n_done += int(d_host.sum())
-        n_running += int((~d_host).sum())
-        most = max(most, int(d_host.sum()))
-    env.check_errors()
-    return n_done, n_running, most, env
 
 
 @pytest.mark.parametrize("fmt", CHW)
 def test_terminal_frames_against_the_oracle(fmt):
     n, steps = TERMINAL["n"], TERMINAL["steps"]
-    n_done, n_running, _, env = lock_step_with_the_oracle(fmt, n, steps, short=True, frames=True)
+    n_done, n_running, _, env = lock_step_with_the_oracle(ENV_ID, fmt, n, steps, SHORT)
     assert n_done >= 6 * n and n_running >= n, (n_done, n_running)
     assert env.debug_counter("final_obs_generic_steps") == 0  # the step's own launches kept the terminal observations
     assert env.debug_counter("emp_fused_steps") == steps
@@ -114,7 +70,7 @@ def test_more_than_one_service_round(fmt):
     """4,163 instances, nearly all truncated in the same step (9 and 18): more than 768 x 4 queue entries, so service waves fetch a second
     entry through QC_HEAD; and a count that is no multiple of 64."""
     n, steps = ROUNDS["n"], ROUNDS["steps"]
-    _, _, most, env = lock_step_with_the_oracle(fmt, n, steps, short=False, frames=False)
+    _, _, most, env = lock_step_with_the_oracle(ENV_ID, fmt, n, steps, IN_STEP, frames=False)
     assert most > ONE_ROUND, most  # otherwise the run did not reach the second round
     assert env.debug_counter("final_obs_generic_steps") == 0
     assert env.debug_counter("emp_fused_steps") == steps
@@ -126,7 +82,7 @@ def test_the_lane_regime(fmt):
     """20,481 instances: the handle leaves bg_coop -- the lane generator in background workgroups, records ahead of time (EMP_PRE), 64 service
     workgroups, plain stores -- and more than 64 x 4 instances finish in one step."""
     n, steps = LANES["n"], LANES["steps"]
-    _, _, most, env = lock_step_with_the_oracle(fmt, n, steps, short=False, frames=False)
+    _, _, most, env = lock_step_with_the_oracle(ENV_ID, fmt, n, steps, IN_STEP, frames=False)
     assert most > ONE_ROUND_PRE, most
     assert env.debug_counter("final_obs_generic_steps") == 0
     assert env.debug_counter("emp_fused_steps") == steps
@@ -139,7 +95,7 @@ def test_plain_autoreset_steps_against_the_oracle(fmt):
     """final_observation=False: the fused launch in its plain form.  No format is excluded from the fused arrangement (profiles/emp_chw.md,
     csrc/mg_mystery.hip steps_fused()), so the product library runs it for all four."""
     n, steps = FORCED["n"], FORCED["steps"]
-    n_done, _, _, env = lock_step_with_the_oracle(fmt, n, steps, short=True, frames=True, final=False)
+    n_done, _, _, env = lock_step_with_the_oracle(ENV_ID, fmt, n, steps, SHORT, final=False)
     assert n_done > n
     assert env.debug_counter("emp_fused_steps") == steps
     env.close()
@@ -149,34 +105,19 @@ def test_plain_autoreset_steps_against_the_oracle(fmt):
 def test_masked_reset_in_mid_run(fmt):
     """reset(seed=None, mask=...) between steps: the fast path (emp_masked_reset_kernel: lazy segments, records ahead of time where there are any).
     Against a u8_xyc twin given the same actions and masks: the frames right after each reset and over 20 further steps, rewards, dones."""
-    import memory_gym_amd
     import torch
 
     n = 160
-    twin = memory_gym_amd.make(ENV_ID, num_envs=n, device=0, obs_format="u8_xyc")
-    env = memory_gym_amd.make(ENV_ID, num_envs=n, device=0, obs_format=fmt)
-    g = torch.Generator(device="cuda").manual_seed(11)
-    o_x, o_c = twin.reset(seed=3, options=SHORT)[0], env.reset(seed=3, options=SHORT)[0]
-    assert torch.equal(o_c, converted(fmt, o_x))
 
-    def steps(k, what):
-        n_done = 0
-        for t in range(k):
-            a = torch.randint(0, 4, (n,), device="cuda", generator=g, dtype=torch.int32)
-            (o_x, r_x, d_x, _, _), (o_c, r_c, d_c, _, _) = twin.step(a), env.step(a)
-            assert torch.equal(r_x, r_c) and torch.equal(d_x, d_c), "%s: rewards / dones differ, %s step %d" % (fmt, what, t)
-            assert torch.equal(o_c, converted(fmt, o_x)), "%s: frames differ, %s step %d" % (fmt, what, t)
-            n_done += int(d_c.sum())
-        return n_done
+    def masked_resets(t, twin, env, g):
+        if t in (7, 12):  # two masked resets five steps apart: the second meets instances the first one left with owed segments
+            mask = torch.rand(n, device="cuda", generator=g) < 0.4
+            assert 0 < int(mask.sum()) < n
+            o_x, o_c = twin.reset(mask=mask)[0], env.reset(mask=mask)[0]
+            assert torch.equal(o_c, converted(fmt, o_x)), "%s: frames differ right after the masked reset before step %d" % (fmt, t)
 
-    steps(7, "before the resets")
-    for k in range(2):  # two masked resets five steps apart: the second meets instances the first one left with owed segments
-        mask = torch.rand(n, device="cuda", generator=g) < 0.4
-        assert 0 < int(mask.sum()) < n
-        o_x, o_c = twin.reset(mask=mask)[0], env.reset(mask=mask)[0]
-        assert torch.equal(o_c, converted(fmt, o_x)), "%s: frames differ right after masked reset %d" % (fmt, k)
-        steps(5, "after masked reset %d," % k)
-    assert steps(15, "late") > 0
+    finished, twin, env = lock_step_with_a_twin(ENV_ID, fmt, n, 7 + 5 + 5 + 15, SHORT, final=False, seed=3, action_seed=11, between=masked_resets)
+    assert sum(finished[-15:]) > 0
     for e in (twin, env):
         e.check_errors()
         e.close()
@@ -185,30 +126,7 @@ def test_masked_reset_in_mid_run(fmt):
 def test_two_option_sets_keep_the_generic_path():
     """Per-instance option sets: the plain arrangement and mg_step's generic path for terminal observations, and the counters say so.
     (A guard: this holds before and after the fused launch learnt the image-order formats.)"""
-    import memory_gym_amd
-    import torch
-
-    n, steps = 64, 12
-    envs = [memory_gym_amd.make(ENV_ID, num_envs=n, device=0, obs_format=f, final_observation=True) for f in ("u8_xyc", "bf16_chw")]
-    mask = torch.zeros(n, dtype=torch.uint8, device="cuda")
-    mask[n // 2:] = 1
-    for e in envs:
-        e.reset(seed=5, options=SHORT)
-        e.reset(options=dict(SHORT, max_steps=5), mask=mask)  # the second half runs under a second option set
-    g = torch.Generator(device="cuda").manual_seed(7)
-    n_done = 0
-    for t in range(steps):
-        a = torch.randint(0, 4, (n,), device="cuda", generator=g, dtype=torch.int32)
-        (o_x, r_x, d_x, _, i_x), (o_c, r_c, d_c, _, i_c) = envs[0].step(a), envs[1].step(a)
-        assert torch.equal(r_x, r_c) and torch.equal(d_x, d_c) and torch.equal(o_c, converted("bf16_chw", o_x)), "step %d" % t
-        assert torch.equal(i_c["final_observation"][d_c], converted("bf16_chw", i_x["final_observation"][d_x])), "terminal frames, step %d" % t
-        n_done += int(d_c.sum())
-    assert n_done > 0
-    for e in envs:
-        assert e.debug_counter("final_obs_generic_steps") == steps
-        assert e.debug_counter("emp_fused_steps") == 0
-        e.check_errors()
-        e.close()
+    two_option_sets_keep_the_generic_path(ENV_ID, SHORT, dict(SHORT, max_steps=5), 12, "emp_fused_steps")
 
 
 def test_graph_replay_of_a_bf16_handle_equals_a_u8_xyc_twin():
@@ -230,28 +148,12 @@ def test_graph_replay_of_a_bf16_handle_equals_a_u8_xyc_twin():
     assert finished > n
     env = memory_gym_amd.make(ENV_ID, num_envs=n, device=0, obs_format=fmt, final_observation=True)
     env.reset(seed=9, options=IN_STEP)
-    snap = env.state_dict()
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):  # warm-up on a side stream, as torch's graph recipe asks
-        env.step(acts[0])
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    env.load_state_dict(snap)
-    before = env.debug_counter("emp_fused_steps")
-    outs = []
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        for a in acts:
-            o, r, d, _, info = env.step(a)
-            outs.append((o.clone(), r.clone(), d.clone(), info["final_observation"].clone()))
-    env.load_state_dict(snap)
-    graph.replay()
-    torch.cuda.synchronize()
-    for k, ((o1, r1, d1, f1), (o2, r2, d2, f2)) in enumerate(zip(want, outs)):
-        assert torch.equal(o1, o2) and torch.equal(r1, r2) and torch.equal(d1, d2), "step %d of the replay differs" % k
+    before = []
+    outs = replay_captured(env, acts, lambda out: clones(out, final=True), lambda: before.append(env.debug_counter("emp_fused_steps")))
+    same_steps(want, outs)
+    for k, ((_, _, d1, f1), (_, _, _, f2)) in enumerate(zip(want, outs)):
         assert torch.equal(f1, f2[d1]), "terminal observations of step %d differ in the replay" % k
-    assert env.debug_counter("emp_fused_steps") == before + K  # the captured steps were the fused launch
+    assert env.debug_counter("emp_fused_steps") == before[0] + K  # the captured steps were the fused launch
     assert env.debug_counter("final_obs_generic_steps") == 0
     env.check_errors()
     twin.close()

@@ -2,6 +2,8 @@
 capture it in a HIP graph; the replay must reproduce the eager results exactly."""
 import pytest
 
+from chw_referee import clones, replay_captured, same_steps
+
 pytestmark = pytest.mark.gpu
 
 
@@ -16,32 +18,10 @@ def test_step_is_graph_capturable(env_id, adim, n_act):
     acts = [torch.randint(0, n_act, (n,) if adim == 1 else (n, adim), device="cuda", generator=g, dtype=torch.int32) for _ in range(K)]
     eager = memory_gym_amd.make(env_id, num_envs=n, device=0)
     eager.reset(seed=9)
-    want = []
-    for a in acts:
-        o, r, d, _, _ = eager.step(a)
-        want.append((o.clone(), r.clone(), d.clone()))
-
+    want = [clones(eager.step(a)) for a in acts]
     env = memory_gym_amd.make(env_id, num_envs=n, device=0)
     env.reset(seed=9)
-    snap = env.state_dict()
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):  # warm-up on a side stream, as torch's graph recipe asks
-        env.step(acts[0])
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    env.load_state_dict(snap)
-    outs = []
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        for a in acts:
-            o, r, d, _, _ = env.step(a)
-            outs.append((o.clone(), r.clone(), d.clone()))
-    env.load_state_dict(snap)  # capture does not execute: state is still the snapshot; make that explicit
-    graph.replay()
-    torch.cuda.synchronize()
-    for k, ((o1, r1, d1), (o2, r2, d2)) in enumerate(zip(want, outs)):
-        assert torch.equal(o1, o2) and torch.equal(r1, r2) and torch.equal(d1, d2), "step %d of the replay differs" % k
+    same_steps(want, replay_captured(env, acts, clones))
     env.check_errors()
     eager.close()
     env.close()
@@ -65,34 +45,14 @@ def test_step_with_terminal_observations_is_graph_capturable(env_id, adim, n_act
     acts = [torch.randint(0, n_act, (n,) if adim == 1 else (n, adim), device="cuda", generator=g, dtype=torch.int32) for _ in range(K)]
     eager = memory_gym_amd.VecMemoryGym(env_id, num_envs=n, device=0, final_observation=True)
     eager.reset(seed=9, options=options)
-    want, finished = [], 0
-    for a in acts:
-        o, r, d, _, info = eager.step(a)
-        want.append((o.clone(), r.clone(), d.clone(), info["final_observation"].clone()))
-        finished += int(d.sum())
-    assert finished > 0
+    want = [clones(eager.step(a), final=True) for a in acts]
+    assert sum(int(d.sum()) for _, _, d, _ in want) > 0
 
     env = memory_gym_amd.VecMemoryGym(env_id, num_envs=n, device=0, final_observation=True)
     env.reset(seed=9, options=options)
-    snap = env.state_dict()
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        env.step(acts[0])
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    env.load_state_dict(snap)
-    outs = []
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        for a in acts:
-            o, r, d, _, info = env.step(a)
-            outs.append((o.clone(), r.clone(), d.clone(), info["final_observation"].clone()))
-    env.load_state_dict(snap)
-    graph.replay()
-    torch.cuda.synchronize()
-    for k, ((o1, r1, d1, f1), (o2, r2, d2, f2)) in enumerate(zip(want, outs)):
-        assert torch.equal(o1, o2) and torch.equal(r1, r2) and torch.equal(d1, d2), "step %d of the replay differs" % k
+    outs = replay_captured(env, acts, lambda out: clones(out, final=True))
+    same_steps(want, outs)
+    for k, ((_, _, d1, f1), (_, _, _, f2)) in enumerate(zip(want, outs)):
         assert torch.equal(f1[d1.bool()], f2[d1.bool()]), "terminal observations of step %d differ in the replay" % k
     env.check_errors()
     eager.close()

@@ -9,50 +9,33 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from chw_referee import SHORT, clones, lock_step_with_a_twin, replay_captured, same_steps
+
 pytestmark = pytest.mark.gpu
 
 CASES = [("MortarMayhem-Grid-v0", 4), ("MortarMayhem-v0", 3), ("Endless-MortarMayhem-v0", 3), ("MysteryPath-v0", 3),
          ("Endless-MysteryPath-v0", 4), ("MysteryPath-Grid-v0", 4), ("SearingSpotlights-v0", 3),
          ("Endless-SearingSpotlights-v0", 3), ("MortarMayhemB-Grid-v0", 4), ("MortarMayhemB-v0", 3)]
 
-# reset options under which episodes end within a few steps (terminal observations, resets inside the run)
-SHORT = {"MortarMayhem-Grid-v0": {"command_count": [2], "command_show_duration": [1], "command_show_delay": [0], "explosion_delay": [2],
-                                  "explosion_duration": [1]},
-         "Endless-MortarMayhem-v0": {"command_show_duration": [1], "command_show_delay": [0], "explosion_delay": [2], "explosion_duration": [1],
-                                     "max_steps": 14},
-         "MysteryPath-Grid-v0": {"max_steps": 7},
-         "SearingSpotlights-v0": {"max_steps": 9, "agent_health": 1}}
-
 
 def _actions(torch, g, env, n, n_act):
     return torch.randint(0, n_act, (n,) if env.action_dim == 1 else (n, 2), device="cuda", generator=g, dtype=torch.int32)
 
 
-def _vis(o):
-    return o["visual_observation"] if isinstance(o, dict) else o
-
-
 @pytest.mark.parametrize("env_id,n_act", CASES)
 def test_u8_chw_is_the_permuted_u8_xyc(env_id, n_act):
-    import memory_gym_amd
     import torch
 
     n, steps = 96, 50
-    xyc = memory_gym_amd.make(env_id, num_envs=n, device=0, obs_format="u8_xyc")
-    chw = memory_gym_amd.make(env_id, num_envs=n, device=0, obs_format="u8_chw")
-    assert chw.obs.shape == (n, 3, 84, 84) and chw.obs.dtype == torch.uint8
-    g = torch.Generator(device="cuda").manual_seed(3)
-    o_x, o_c = xyc.reset(seed=11)[0], chw.reset(seed=11)[0]
-    for t in range(steps + 1):
-        assert torch.equal(_vis(o_c), _vis(o_x).permute(0, 3, 2, 1)), "%s: frames differ at step %d" % (env_id, t)
+
+    def same_render(t, xyc, chw, g):
         assert torch.equal(chw.render(), xyc.render()), "%s: render() differs at step %d" % (env_id, t)
-        if isinstance(o_x, dict):
-            assert torch.equal(o_c["vector_observation"], o_x["vector_observation"]), "%s: vector observation differs at step %d" % (env_id, t)
-        a = _actions(torch, g, xyc, n, n_act)
-        (o_x, r_x, d_x, _, _), (o_c, r_c, d_c, _, _) = xyc.step(a), chw.step(a)
-        assert torch.equal(r_x, r_c) and torch.equal(d_x, d_c), "%s: rewards / dones differ at step %d" % (env_id, t)
+
+    _, xyc, chw = lock_step_with_a_twin(env_id, "u8_chw", n, steps + 1, final=False, seed=11, action_seed=3, between=same_render)
+    assert chw.obs.shape == (n, 3, 84, 84) and chw.obs.dtype == torch.uint8
+    assert xyc.action_space.n == n_act if xyc.action_dim == 1 else list(xyc.action_space.nvec) == [n_act, n_act]
     if env_id.startswith("MortarMayhemB"):
-        assert isinstance(o_x, dict)
+        assert xyc.vector_obs is not None  # (observations are the reference's Dict: the twin loop compared the vector observation too)
     for e in (xyc, chw):
         e.check_errors()
         e.close()
@@ -88,21 +71,9 @@ def test_u8_chw_matches_the_oracle(env_id, n_act):
 def test_more_than_one_frame_per_workgroup(env_id, n_act):
     """Just above the raster grid (14,336 persistent workgroups, mg_raster_v1.hpp RASTER_GRID) and no multiple of 64: 67 workgroups
     draw two frames, the last 64-instance claim slot of the one-launch step holds 3 instances."""
-    import memory_gym_amd
-    import torch
-
     n, steps = 14336 + 67, 12
     assert n % 64 != 0
-    xyc = memory_gym_amd.make(env_id, num_envs=n, device=0, obs_format="u8_xyc")
-    chw = memory_gym_amd.make(env_id, num_envs=n, device=0, obs_format="u8_chw")
-    g = torch.Generator(device="cuda").manual_seed(4)
-    o_x, o_c = xyc.reset(seed=21)[0], chw.reset(seed=21)[0]
-    assert torch.equal(o_c, o_x.permute(0, 3, 2, 1))
-    for t in range(steps):
-        a = _actions(torch, g, xyc, n, n_act)
-        (o_x, r_x, d_x, _, _), (o_c, r_c, d_c, _, _) = xyc.step(a), chw.step(a)
-        assert torch.equal(o_c, o_x.permute(0, 3, 2, 1)), "%s: frames differ after step %d" % (env_id, t)
-        assert torch.equal(r_x, r_c) and torch.equal(d_x, d_c)
+    _, xyc, chw = lock_step_with_a_twin(env_id, "u8_chw", n, steps, final=False)
     assert chw.debug_counter("one_launch_steps") == steps
     assert xyc.debug_counter("one_launch_steps") == steps
     for e in (xyc, chw):
@@ -115,27 +86,10 @@ def test_more_than_one_frame_per_workgroup(env_id, n_act):
 def test_terminal_observations(env_id, n_act):
     """final_observation=True: rows of finished instances hold the permuted terminal frame, every other row is left alone; on the mortar
     family every such step is ONE launch (the FINAL form of the one-launch step)."""
-    import memory_gym_amd
-    import torch
-
-    n, steps, sentinel = 48, 60, 0x5A
-    xyc = memory_gym_amd.make(env_id, num_envs=n, device=0, obs_format="u8_xyc", final_observation=True)
-    chw = memory_gym_amd.make(env_id, num_envs=n, device=0, obs_format="u8_chw", final_observation=True)
-    g = torch.Generator(device="cuda").manual_seed(6)
-    xyc.reset(seed=31, options=SHORT[env_id])
-    chw.reset(seed=31, options=SHORT[env_id])
-    n_done = n_running = 0
-    for t in range(steps):
-        a = _actions(torch, g, xyc, n, n_act)
-        xyc.final_obs.fill_(sentinel)
-        chw.final_obs.fill_(sentinel)
-        (o_x, _, d_x, _, i_x), (o_c, _, d_c, _, i_c) = xyc.step(a), chw.step(a)
-        assert torch.equal(d_x, d_c) and torch.equal(o_c, o_x.permute(0, 3, 2, 1)), "%s: step %d" % (env_id, t)
-        f_x, f_c = i_x["final_observation"], i_c["final_observation"]
-        assert torch.equal(f_c[d_c], f_x[d_x].permute(0, 3, 2, 1)), "%s: terminal frames differ at step %d" % (env_id, t)
-        assert bool((f_c[~d_c] == sentinel).all()), "%s: a row of a running instance was written at step %d" % (env_id, t)
-        n_done += int(d_c.sum())
-        n_running += int((~d_c).sum())
+    n, steps = 48, 60
+    finished, xyc, chw = lock_step_with_a_twin(env_id, "u8_chw", n, steps, SHORT[env_id], seed=31, action_seed=6)
+    n_done = sum(finished)
+    n_running = n * steps - n_done
     assert n_done > n and n_running > n, (n_done, n_running)  # both kinds of row were seen, many times
     if "MortarMayhem" in env_id:
         assert chw.debug_counter("one_launch_steps") == steps
@@ -195,33 +149,12 @@ def test_graph_replay_equals_eager():
     acts = [torch.randint(0, 4, (n,), device="cuda", generator=g, dtype=torch.int32) for _ in range(K)]
     eager = memory_gym_amd.make(env_id, num_envs=n, device=0, obs_format="u8_chw")
     eager.reset(seed=9)
-    want = []
-    for a in acts:
-        o, r, d, _, _ = eager.step(a)
-        want.append((o.clone(), r.clone(), d.clone()))
+    want = [clones(eager.step(a)) for a in acts]
     env = memory_gym_amd.make(env_id, num_envs=n, device=0, obs_format="u8_chw")
     env.reset(seed=9)
-    snap = env.state_dict()
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):  # warm-up on a side stream, as torch's graph recipe asks
-        env.step(acts[0])
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    env.load_state_dict(snap)
-    before = env.debug_counter("one_launch_steps")
-    outs = []
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        for a in acts:
-            o, r, d, _, _ = env.step(a)
-            outs.append((o.clone(), r.clone(), d.clone()))
-    env.load_state_dict(snap)
-    graph.replay()
-    torch.cuda.synchronize()
-    for k, ((o1, r1, d1), (o2, r2, d2)) in enumerate(zip(want, outs)):
-        assert torch.equal(o1, o2) and torch.equal(r1, r2) and torch.equal(d1, d2), "step %d of the replay differs" % k
-    assert env.debug_counter("one_launch_steps") == before  # captured steps are not the one-launch kernel
+    before = []
+    same_steps(want, replay_captured(env, acts, clones, lambda: before.append(env.debug_counter("one_launch_steps"))))
+    assert env.debug_counter("one_launch_steps") == before[0]  # captured steps are not the one-launch kernel
     env.check_errors()
     eager.close()
     env.close()

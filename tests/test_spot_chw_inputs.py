@@ -2,10 +2,9 @@
 alone says about them (no GPU): that the runs reach what the GPU tests are about -- terminal rows and running rows in the same steps, and a
 step with more finished instances than one service round of the launch takes (512 workgroups x 8 = 4,096).
 
-The oracle's runs are computed once per (id, case) and shared by the formats (oracle_run); nothing changes them afterwards."""
-import functools
-
-import numpy as np
+The oracle's runs are computed once per (id, case) and shared by the formats (tests/chw_referee.py oracle_run: seeds arange(n) + 31, actions
+from PCG64(6)); nothing changes them afterwards."""
+from chw_referee import frozen, oracle_run
 
 IDS = ("SearingSpotlights-v0", "Endless-SearingSpotlights-v0")
 # Episodes that end within nine steps: max_steps truncates, one point of health lets a spotlight end them earlier (both kinds of ending in one run).
@@ -20,49 +19,10 @@ ONE_ROUND = 512 * 8                        # SPOT_SVC_WGS x SPOT_SVC_BATCH (csrc
 FORCED = dict(n=96, steps=40)              # case 4
 
 
-def seeds_of(n):
-    return np.arange(n, dtype=np.int64) + 31
-
-
-def actions_of(prng, n):
-    return prng.integers(0, 3, (n, 2)).astype(np.int32)
-
-
-@functools.lru_cache(maxsize=1)
-def oracle_run(env_id, n, steps, short, frames):
-    """`steps` auto-reset steps of n instances under SHORT (short=True) or IN_STEP, seeds arange(n) + 31, actions from PCG64(6).
-    -> (seeds, first, run): first = the reset frames (frames=True: two batches in lock step, one returns the frames, one the digests) or their
-    digests; run = per step (actions, frames or None, digest, final_digest, reward, done, ground_truth float32 or None)."""
-    import oracle_lib
-
-    opts = (SHORT if short else IN_STEP)[env_id]
-    dig = oracle_lib.OracleBatch(env_id, n, options=opts)
-    pix = oracle_lib.OracleBatch(env_id, n, options=opts) if frames else None
-    seeds = seeds_of(n)
-    first = dig.reset_digest(seeds)
-    if pix:
-        first = pix.reset(seeds)
-    prng = np.random.Generator(np.random.PCG64(6))
-    run = []
-    for _ in range(steps):
-        a = actions_of(prng, n)
-        dg, fdg, rew, done = dig.step_digest(a, autoreset=True)
-        fr = None
-        if pix:
-            fr, rew2, done2 = pix.step(a, autoreset=True)
-            assert np.array_equal(rew, rew2) and np.array_equal(done, done2)
-        gt = np.stack([e.gt() for e in dig.envs]).astype(np.float32) if dig.envs[0].gt_dim else None
-        run.append((a, fr, dg, fdg, rew, done, gt))
-    dig.close()
-    if pix:
-        pix.close()
-    return seeds, first, run
-
-
 def test_case_1_sees_terminal_and_running_rows():
     for env_id in IDS:
         n, steps = TERMINAL["n"], TERMINAL["steps"]
-        run = oracle_run(env_id, n, steps, True, False)[2]
+        run = oracle_run(env_id, n, steps, frozen(SHORT[env_id]), False)[2]
         n_done = sum(int(s[5].sum()) for s in run)
         n_running = sum(int((s[5] == 0).sum()) for s in run)
         assert n_done >= 6 * n, (env_id, n_done)  # max_steps = 9 over 60 steps: six endings per instance at the least
@@ -71,12 +31,12 @@ def test_case_1_sees_terminal_and_running_rows():
 
 def test_case_2_fills_more_than_one_service_round():
     for env_id in IDS:
-        run = oracle_run(env_id, ROUNDS["n"], ROUNDS["steps"], False, False)[2]
+        run = oracle_run(env_id, ROUNDS["n"], ROUNDS["steps"], frozen(IN_STEP[env_id]), False)[2]
         most = max(int(s[5].sum()) for s in run)
         assert most > ONE_ROUND, (env_id, most)
 
 
 def test_case_4_resets_instances():
     for env_id in IDS:
-        run = oracle_run(env_id, FORCED["n"], FORCED["steps"], True, False)[2]
+        run = oracle_run(env_id, FORCED["n"], FORCED["steps"], frozen(SHORT[env_id]), False)[2]
         assert sum(int(s[5].sum()) for s in run) > FORCED["n"]
