@@ -5,6 +5,7 @@
 #include <map>
 #include <mutex>
 
+#include "mg_expert.hpp"
 #include "mg_family.hpp"
 #include "mg_lab.hpp"
 
@@ -356,6 +357,15 @@ int mg_step(mg_env* env, const int32_t* actions_dev, void* obs_dev, float* rewar
             f->step(actions_dev, obs_dev, reward_dev, done_dev, gt_dev, &ib, autoreset, st);
         }
         if (ib.gt64_dev) f->ground_truth64(ib.gt64_dev, st);
+    });
+}
+
+int mg_expert_actions(mg_env* env, double eps, uint64_t seed, uint64_t step, int32_t* actions_dev, void* stream) {
+    return guarded(env, [&] {
+        if (!actions_dev) throw std::runtime_error("mg_expert_actions: actions_dev is NULL");
+        if (!env->started) throw std::runtime_error("mg_expert_actions: before the first mg_reset / mg_set_state");
+        if (!(eps >= 0.0 && eps <= 1.0)) throw std::runtime_error("mg_expert_actions: eps outside [0, 1]");
+        env->fam->expert_actions(mg::ExpertArgs{eps, mg::expert_base(seed, step), actions_dev}, (hipStream_t)stream);
     });
 }
 

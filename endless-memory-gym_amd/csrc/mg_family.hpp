@@ -199,6 +199,8 @@ struct KernelProfile {
     }
 };
 
+struct ExpertArgs;  // mg_expert.hpp
+
 // What the C ABI (mg_api.hip) sees of an environment family, and the host-side plumbing the three families share: the error
 // word, the RNG streams, the "seeded" / "geometry changed" guards and the debug view's scratch frames.
 class Family {
@@ -258,6 +260,9 @@ class Family {
     // [num_envs][gt_dim], computed from the CURRENT state (the float32 gt_dev of mg_step / mg_reset is its rounding); a small
     // launch of its own, only when a caller asks (mg_info_buffers.gt64_dev, mg_ground_truth64).  No-op for gt_dim() == 0.
     virtual void ground_truth64(double* /*gt64_dev*/, hipStream_t /*s*/) {}
+    // mg_expert_actions: the oracle's expert action of every instance from the CURRENT state (or the random one its draw gives it, ExpertArgs /
+    // mg_expert.hpp), into x.actions in the layout step() reads.  One small launch; changes no state, draws from no instance's stream.
+    virtual void expert_actions(const ExpertArgs& x, hipStream_t s) = 0;
     // device-side error bits accumulated since the last call (0 = none); synchronises
     virtual int poll_errors() {
         MG_HIP(hipDeviceSynchronize());

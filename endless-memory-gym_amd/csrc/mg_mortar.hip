@@ -13,6 +13,7 @@
 //   mg_mortar_compose.hpp     MortarComposer (the observation) and MortarDebugComposer, with the measurement hooks MG_LAB_NO_TEMPLATE / MG_LAB_NO_STAMPS
 //   mg_mortar_step.hpp        reset and step of one instance (mortar_reset, mortar_step_body); mortar_reset_kernel, mortar_step_kernel
 //   mg_mortar_one_launch.hpp  mortar_step_raster_kernel: the step as one launch, its claim / hand-over word, RESCUE_AFTER_TICKS
+//   mg_mortar_expert.hpp      mortar_expert_kernel: the scripted teacher of the five ids (mg_expert_actions), a launch of its own
 //
 // The launches of a step as shipped:
 //   ONE launch for handles with one option set, in every observation format (mortar_step_raster_kernel: the step's workgroups lead the raster's grid and a frame waits for its own
@@ -33,6 +34,7 @@
 #include "mg_mortar_compose.hpp"
 #include "mg_mortar_step.hpp"
 #include "mg_mortar_one_launch.hpp"
+#include "mg_mortar_expert.hpp"
 
 namespace mg {
 using namespace v1;  // raster generation 1 (see mg_raster_v1.hpp)
@@ -295,6 +297,11 @@ class MortarFamily : public Family {
         return v;
     }
 
+    void expert_actions(const ExpertArgs& x, hipStream_t s) override {
+        if (dirty_) throw std::runtime_error("options that change geometry need a reset before the next step");
+        sets_.upload(s);
+        launch_checked(mortar_expert_kernel, expert_grid(n_), dim3(EXPERT_BLOCK), 0, s, P_, n_, io(), x);
+    }
     void ground_truth64(double* out, hipStream_t s) override {
         if (!gt_dim() || !out) return;
         launch_checked(mortar_gt64_kernel, dim3((n_ + 255) / 256), dim3(256), 0, s, n_, state_.p, out);

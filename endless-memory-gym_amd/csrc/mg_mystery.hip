@@ -14,6 +14,7 @@
 //   mg_mystery_finite.hpp          MysteryPath-v0 / -Grid-v0: reset, step, path service and their three kernels
 //   mg_mystery_endless.hpp         Endless-MysteryPath-v0: segment store, step, resets, queue entries, owed segments and records ahead of time (device functions)
 //   mg_mystery_endless_launch.hpp  ... and its emp_* kernels, launch constants and measurement hooks
+//   mg_mystery_expert.hpp          mystery_expert_kernel: the scripted teacher of the three ids (mg_expert_actions), a launch of its own
 //
 // The launches of a step as shipped (auto-reset, one option set, uint8 observations, agent sprites that fit registers; why, and every other arrangement: DESIGN.md 3.1):
 //   MysteryPath-Grid-v0     mystery_step_kernel, defer 1: every reset is queued -> mystery_raster_paths_kernel: its first 128 workgroups (and helpers, when the queue
@@ -36,6 +37,7 @@
 #include "mg_mystery_finite.hpp"
 #include "mg_mystery_endless.hpp"
 #include "mg_mystery_endless_launch.hpp"
+#include "mg_mystery_expert.hpp"
 
 namespace mg {
 
@@ -160,7 +162,7 @@ class MysteryFamily : public Family {
             segs_.alloc((size_t)n * seg_rows_ * SEG_STRIDE);
             aux_.alloc((size_t)n * AUX_WORDS);
         } else {
-            segs_.alloc(16);
+            segs_.alloc((size_t)n * PATH_ORDER_STRIDE);  // finite: the order of every instance's path (path_order, mg_mystery_types.hpp)
             aux_.alloc(4);
         }
         sets_.alloc();
@@ -379,6 +381,12 @@ class MysteryFamily : public Family {
                                                   {walls_.p, walls_.bytes()}};
         rng_.blobs(v);
         return v;
+    }
+    // (Endless: whatever is owed stays owed -- the node the expert aims at exists when a step has returned, mg_mystery_expert.hpp emp_expert)
+    void expert_actions(const ExpertArgs& x, hipStream_t s) override {
+        if (dirty_) throw std::runtime_error("options that change geometry need a reset before the next step");
+        sets_.upload(s);
+        launch_checked(mystery_expert_kernel, expert_grid(n_), dim3(EXPERT_BLOCK), 0, s, P_, io(), x);
     }
     void ground_truth64(double* out, hipStream_t s) override {
         if (!gt_dim() || !out) return;

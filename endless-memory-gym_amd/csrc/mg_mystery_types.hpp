@@ -95,7 +95,7 @@ static_assert(sizeof(MysteryDesc) == 64, "MysteryDesc must be 64 bytes");
 
 struct MysteryIO {
     MysteryCore* core;
-    uint8_t* segs;      // endless: [N][seg_rows][SEG_STRIDE]; node byte = x_rel | y<<3 | rvis<<6 | svis<<7
+    uint8_t* segs;      // endless: [N][seg_rows][SEG_STRIDE]; node byte = x_rel | y<<3 | rvis<<6 | svis<<7.  finite: [N][PATH_ORDER_STRIDE], see path_order()
     int seg_rows;       // segment records per instance (MAX_SEG by default; mg_set_capacity "path_segments")
     RngSoA rng;
     MysteryDesc* desc;
@@ -117,6 +117,12 @@ struct MysteryIO {
     const int32_t* set_of;
     MysteryDesc* tdesc;  // finite variants, FINAL forms of the step / raster kernels (terminal observations kept): [N] terminal-frame descriptors
 };
+// Finite variants: the ORDER of the current path as the reference's list has it -- END first, a byte per node, flat index x*7+y, path_len of them -- written where a
+// path is generated (serve_mp, the lane generator's caller) and read by the expert kernel alone (mg_mystery_expert.hpp); the step needs only path_mask.  It lives in
+// the pointer the endless variant uses for its segment store: a finite handle has no segments, and MysteryIO -- an argument of every kernel of the family -- stays as it is.
+constexpr int PATH_ORDER_STRIDE = 64;
+static_assert(G * G <= PATH_ORDER_STRIDE, "a path visits a cell once");
+__device__ __forceinline__ uint8_t* path_order(const MysteryIO& io, int i) { return io.segs + (size_t)i * PATH_ORDER_STRIDE; }
 constexpr int QC_COUNT = 0, QC_HEAD = 32, QC_LEFT = 64, QC_BG_COUNT = 96, QC_WORDS = 160;  // one 128-byte line each
 // MysteryDesc::valid: 0 = leave the frame alone (masked reset), 1 = draw, 2 = the instance has a queue entry, 3 = served (and, in
 // the fused launch, drawn by the workgroup that served it).  Only emp_raster_serve_kernel's frame workgroups tell 1 from 2 / 3.

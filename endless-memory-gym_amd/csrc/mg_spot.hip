@@ -13,6 +13,7 @@
 //   mg_spot_sampler.hpp  the grid position sampler for the 16 lanes of an instance (sample_cell), nothing of the environments
 //   mg_spot_logic.hpp    reset and step of one instance: new_spot, new_spots_at_reset, spot_reset, spot_step_body and the clock build's hooks
 //   mg_spot_serve.hpp    spot_reset_kernel, spot_step_kernel and spot_raster_serve_kernel with its launch constants
+//   mg_spot_expert.hpp   spot_expert_kernel: the scripted teacher of both ids (mg_expert_actions), a launch of its own
 //
 // The launches of a step as shipped (auto-reset, one option set, uint8 observations; why, and the figures: DESIGN.md and fuse_resets() below):
 //   two launches   spot_step_kernel: SIXTEEN LANES per instance (4 instances per wave).  Lane s owns spotlight slot s: float64 trajectory (lerp of lerp, un-fused
@@ -41,6 +42,7 @@
 #include "mg_spot_sampler.hpp"
 #include "mg_spot_logic.hpp"
 #include "mg_spot_serve.hpp"
+#include "mg_spot_expert.hpp"
 
 namespace mg {
 
@@ -343,6 +345,11 @@ class SpotFamily : public Family {
         v.push_back({exit_hist_.p, exit_hist_.bytes()});
         rng_.blobs(v);
         return v;
+    }
+    void expert_actions(const ExpertArgs& x, hipStream_t s) override {
+        if (dirty_) throw std::runtime_error("options that change geometry need a reset before the next step");
+        sets_.upload(s);
+        launch_checked(spot_expert_kernel, expert_grid(n_), dim3(EXPERT_BLOCK), 0, s, P_, io(), x);
     }
     void ground_truth64(double* out, hipStream_t s) override {
         if (!gt_dim() || !out) return;

@@ -84,6 +84,8 @@ def _load():
     if hasattr(L, "mg_obs_set_search_ms"):  # (absent from builds of earlier rounds that tools/ A/B against through MEMGYM_HIP_LIB)
         L.mg_obs_set_search_ms.argtypes = [C.c_double]
         L.mg_store_probe.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+    if hasattr(L, "mg_expert_actions"):  # (absent from the older builds tools/ A/B against through MEMGYM_HIP_LIB)
+        L.mg_expert_actions.argtypes = [C.c_void_p, C.c_double, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
     L.mg_enable_peer_access.argtypes = [C.c_int, C.c_int]
     L.mg_debug_rng.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
     L.mg_debug_set_rng.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]

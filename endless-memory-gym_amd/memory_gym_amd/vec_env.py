@@ -246,6 +246,7 @@ class VecMemoryGym:
         # `truncation` is always False in the reference; on_capacity="truncate": True where the episode ended on a capacity of this build
         self._truncated = self.capacity_u8.view(torch.bool) if self.capacity_u8 is not None else torch.zeros(N, dtype=torch.bool, device=dev)
         self._n_actions = self.num_envs * self.action_dim
+        self._expert_calls = 0  # expert_actions(step=None): the per-handle call counter
         self._p_err = C.byref(self._err)
         self._bind_step()
 
@@ -430,6 +431,27 @@ class VecMemoryGym:
                                  1 if self.autoreset else 0, self._raw_stream())
         if rc != 0:
             _native.check(rc, "mg_step")
+
+    def expert_actions(self, eps=0.0, seed=0, step=None, out=None):
+        """The scripted teacher (include/memgym.h: mg_expert_actions): for every instance the action the CPU oracle's expert hook gives
+        in its CURRENT state -- after the last reset() / step(), the new episode's state where that step auto-reset the instance -- as an
+        int32 tensor [N] (Discrete ids) or [N, 2] (MultiDiscrete ids) that step() takes as it is.  With probability `eps` an instance gets
+        a uniformly random action instead: a counter-based hash of (seed, step, instance), the oracle's mgo_batch_expert, so equal
+        arguments give equal actions.  step=None numbers the calls of this handle 0, 1, 2, ...  `out`: a contiguous int32 tensor of that
+        shape on the handle's device to write into.  One small launch on the current stream: nothing synchronises, no state changes, no
+        instance's random stream moves.  Uses: demonstrations for behaviour cloning, DAgger labels (query it in the states the LEARNER
+        reaches), an upper bound on return per curriculum setting, a check that an option set is solvable."""
+        shape = (self.num_envs,) if self.action_dim == 1 else (self.num_envs, 2)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.int32, device=self.device)
+        elif not (isinstance(out, torch.Tensor) and out.dtype == torch.int32 and out.device == self.device and out.is_contiguous() and tuple(out.shape) == shape):
+            raise ValueError("expert_actions: out must be a contiguous int32 tensor of shape %s on %s" % (shape, self.device))
+        mask = (1 << 64) - 1
+        with torch.cuda.device(self.device):
+            _native.check(_native.LIB.mg_expert_actions(self._h, float(eps), int(seed) & mask, int(self._expert_calls if step is None else step) & mask,
+                                                        out.data_ptr(), self._stream()), "mg_expert_actions")
+        self._expert_calls += 1
+        return out
 
     def new_obs_buffer(self):
         """A second observation buffer like `obs` (same shape, dtype, device and -- if `obs` came from mg_obs_alloc -- the same
@@ -722,6 +744,12 @@ class MemoryGymEnv(_EnvBase):
         if self.vec.gt_dim:
             out["ground_truth"] = self._gt_host[:self.vec.gt_dim].copy()
         return self._observation(), r, d, False, out
+
+    def expert_action(self, eps=0.0, seed=0, step=None):
+        """The scripted teacher's action in the current state (VecMemoryGym.expert_actions with one instance): an int for Discrete ids, a
+        numpy int array of two for MultiDiscrete ids -- what step() takes.  Not a hot path (a launch and a copy to the host)."""
+        a = self.vec.expert_actions(eps, seed, step).cpu().numpy()
+        return a[0].copy() if self._two_actions else int(a[0])
 
     def render(self):
         if self.render_mode == "debug_rgb_array":

@@ -97,6 +97,10 @@ class GymnasiumVectorEnv(_Base):
             out.update(final_observation=fobs, _final_observation=d.copy(), final_info=finfo, _final_info=d.copy())
         return self._host(obs), self.env.reward64.cpu().numpy(), term.cpu().numpy(), trunc.cpu().numpy(), out  # (the reference's Python floats: doubles)
 
+    def expert_actions(self, eps=0.0, seed=0, step=None, out=None):
+        """The scripted teacher's actions in the current states (VecMemoryGym.expert_actions): what step() takes; numpy with as_numpy."""
+        return self._host(self.env.expert_actions(eps=eps, seed=seed, step=step, out=out))
+
     # gymnasium.vector.VectorEnv API surface used by trainers
     def step_async(self, actions):
         self._pending = actions

@@ -203,6 +203,23 @@ int mg_step(mg_env* env, const int32_t* actions_dev, void* obs_dev, float* rewar
  * `stream`; a no-op for env ids without ground truth. */
 int mg_ground_truth64(mg_env* env, double* gt64_dev, void* stream);
 
+/* The scripted teacher: for every instance the action the CPU oracle's expert hook gives in the instance's CURRENT state -- what the last
+ * mg_reset / mg_step left, i.e. the new episode's state where that step auto-reset the instance -- written to actions_dev in the layout
+ * mg_step reads (int32 [num_envs] for Discrete ids, [num_envs][2] for MultiDiscrete ids).  The reference itself has no such method; the
+ * DEFINITION is the oracle's hooks, restated on the records the step kernels keep:
+ *   oracle/mgo_mortar.c  mm_expert (:546)                  the five Mortar Mayhem ids: wait while commands are shown and while the tiles
+ *                                                          are on, else move to the target tile (Endless: the shorter way round the wrap)
+ *   oracle/mgo_mystery.c mpf_expert / emp_expert (:713-745) follow the path: the node behind the agent's in the reference's path list
+ *   oracle/mgo_spot.c    sp_expert (:770)                  the first remaining coin, then the exit
+ * With probability eps instance i gets, instead, the uniformly random action of oracle/mgo_api.c mgo_batch_expert (:262-289): a
+ * counter-based hash of (seed, step, i), the same numbers for any eps in [0, 1] -- so a caller that passes its step counter gets the
+ * oracle's policy for "competent play" bit for bit (tests/test_gpu_expert.py, all ten ids).  Per-instance option sets are honoured.
+ * ONE small launch, enqueued on `stream`: no synchronisation, no allocation, no state change, and nothing is drawn from any instance's PCG64
+ * stream -- calling it, or not, changes no later observation, reward or random number.  It can be captured into a HIP graph; eps, seed and
+ * step are kernel arguments, so a captured launch replays the values it was captured with (a trainer that wants fresh random actions per
+ * replay updates the node's arguments or leaves the call outside the graph). */
+int mg_expert_actions(mg_env* env, double eps, uint64_t seed, uint64_t step, int32_t* actions_dev, void* stream);
+
 /* The single-instance fast path (BASELINE config C1: gym.make(id), one instance, numpy in / numpy out -- the reference's own loop,
  * /root/reference/bench.py:12-30).  For a handle with num_envs == 1, mg_single_open allocates every per-call buffer in pinned,
  * device-mapped HOST memory and returns the host addresses: the kernels read the action from it and store observation, reward,
@@ -236,7 +253,9 @@ int mg_single_step(mg_env* env, int32_t a0, int32_t a1, void* stream);
  * mg_state_size: bytes needed.  The blob starts with a 64-byte header {magic "MGSTATE1", MG_STATE_VERSION, num_envs,
  * payload bytes, FNV-1a of the env id}; the layout behind it is private to one MG_STATE_VERSION.  mg_set_state refuses
  * (-1, message in mg_last_error) a blob whose magic, version, env id, num_envs or payload size differ from the handle's
- * instead of mis-assigning it. */
+ * instead of mis-assigning it.  (The finite Mystery Path ids' blobs carry the order of every instance's path since mg_expert_actions exists:
+ * 64 bytes per instance more than before, so an earlier blob of those two ids is refused by its payload size; the other eight ids' layout
+ * is what it was.) */
 #define MG_STATE_VERSION 8u
 size_t mg_state_size(const mg_env* env);
 int mg_get_state(mg_env* env, void* host_buf, size_t size);
