@@ -24,6 +24,17 @@ struct mg_env {
     int variant = 0, family = 0;  // what make_* was called with
     bool started = false;         // a reset has happened
     int64_t final_obs_generic_steps = 0;  // mg_debug_counter: mg_step calls that kept terminal observations on the generic path (see mg_step)
+    int64_t headless_steps = 0;        // mg_debug_counter: mg_step calls with obs_dev == NULL, and the steps of mg_advance's loop form
+    int64_t advance_fused_steps = 0;   // mg_debug_counter: steps mg_advance took inside a family's own launches (Family::advance)
+    // mg_advance: what the loop of its definition passes from launch to launch, allocated at the handle's first call (include/memgym.h)
+    struct Advance {
+        bool ready = false;
+        mg::DevArray<int32_t> actions, ep_length;
+        mg::DevArray<float> reward, aux[MG_INFO_SLOTS];
+        mg::DevArray<uint8_t> done;
+        mg::DevArray<double> reward64, ep_reward;
+        mg_info_buffers ib;
+    } adv;
     std::string id;
     int obs_format = MG_OBS_U8_XYC;
     float* vec_dev = nullptr;     // the caller's vector-observation binding (mg_bind_vector_obs), or the single-instance block's
@@ -336,10 +347,17 @@ int mg_render_debug(mg_env* env, uint8_t* rgb_dev, void* stream) {
 int mg_step(mg_env* env, const int32_t* actions_dev, void* obs_dev, float* reward_dev, uint8_t* done_dev, float* gt_dev,
             const mg_info_buffers* info, int autoreset, void* stream) {
     return guarded(env, [&] {
-        if (!actions_dev || !obs_dev || !reward_dev || !done_dev) throw std::runtime_error("mg_step: NULL buffer");
+        if (!actions_dev || !reward_dev || !done_dev) throw std::runtime_error("mg_step: NULL buffer");
         hipStream_t st = (hipStream_t)stream;
         const mg_info_buffers ib = read_info(info);
         mg::Family* f = env->fam;
+        if (!obs_dev) {  // a headless step: the family's plain arrangement without its raster launch
+            if (ib.final_obs_dev) throw std::runtime_error("mg_step: obs_dev is NULL (a headless step) together with final_obs_dev: terminal observations are frames");
+            f->step(actions_dev, nullptr, reward_dev, done_dev, gt_dev, &ib, autoreset, st);
+            ++env->headless_steps;
+            if (ib.gt64_dev) f->ground_truth64(ib.gt64_dev, st);
+            return;
+        }
         if (autoreset && ib.final_obs_dev && !(mg::sparse_masked_raster() && f->keeps_final_obs(st))) {
             // terminal frames wanted: step without auto-reset (obs rows of finished instances = terminal frames), keep
             // a copy of exactly those rows, then reset the finished instances with seed=None -- the same RNG
@@ -366,6 +384,79 @@ int mg_expert_actions(mg_env* env, double eps, uint64_t seed, uint64_t step, int
         if (!env->started) throw std::runtime_error("mg_expert_actions: before the first mg_reset / mg_set_state");
         if (!(eps >= 0.0 && eps <= 1.0)) throw std::runtime_error("mg_expert_actions: eps outside [0, 1]");
         env->fam->expert_actions(mg::ExpertArgs{eps, mg::expert_base(seed, step), actions_dev}, (hipStream_t)stream);
+    });
+}
+
+}  // extern "C"
+// One step of mg_advance's loop form into the call's sums (the three families share it): row i of the step's reward64 / done / episode
+// record, added to -- at the call's first step: stored as -- sum i.  The same additions in the same order as mortar_advance_kernel's.
+__global__ __launch_bounds__(256) void advance_accumulate_kernel(int n, int first, mg_info_buffers ib, const uint8_t* __restrict__ done, mg_advance_out o) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const bool d = done[i] != 0;
+    if (o.reward_sum_dev) o.reward_sum_dev[i] = (first ? 0.0 : o.reward_sum_dev[i]) + ib.reward64_dev[i];
+    if (o.episodes_dev) o.episodes_dev[i] = (first ? 0 : o.episodes_dev[i]) + (d ? 1 : 0);
+    if (o.ep_reward_sum_dev && (first || d)) o.ep_reward_sum_dev[i] = (first ? 0.0 : o.ep_reward_sum_dev[i]) + (d ? ib.ep_reward_dev[i] : 0.0);
+    if (o.ep_length_sum_dev && (first || d)) o.ep_length_sum_dev[i] = (first ? (int64_t)0 : o.ep_length_sum_dev[i]) + (d ? (int64_t)ib.ep_length_dev[i] : (int64_t)0);
+#pragma unroll
+    for (int k = 0; k < MG_INFO_SLOTS; ++k)
+        if (o.aux_sum_dev[k] && ib.aux_dev[k] && (first || d)) o.aux_sum_dev[k][i] = (first ? 0.0 : o.aux_sum_dev[k][i]) + (d ? (double)ib.aux_dev[k][i] : 0.0);
+}
+extern "C" {
+
+int mg_advance(mg_env* env, int32_t steps, double eps, uint64_t seed, uint64_t step0, float* gt_dev, const mg_advance_out* out, void* stream) {
+    return guarded(env, [&] {
+        if (!env->started) throw std::runtime_error("mg_advance: before the first mg_reset / mg_set_state");
+        if (steps < 1) throw std::runtime_error("mg_advance: steps < 1");
+        if (!(eps >= 0.0 && eps <= 1.0)) throw std::runtime_error("mg_advance: eps outside [0, 1]");
+        mg_advance_out o;
+        memset(&o, 0, sizeof(o));
+        if (out) {  // (as the caller's header laid it out: a shorter struct lacks the later slots)
+            const size_t sz = out->struct_size;
+            if (sz < offsetof(mg_advance_out, aux_sum_dev) || sz > sizeof(o) + 16 * sizeof(void*) || sz % sizeof(void*) != 0)
+                throw std::runtime_error("mg_advance: mg_advance_out.struct_size = " + std::to_string(sz) + " is not a layout of include/memgym.h; set it to sizeof(mg_advance_out)");
+            memcpy(&o, out, sz < sizeof(o) ? sz : sizeof(o));
+        }
+        o.struct_size = sizeof(o);
+        hipStream_t st = (hipStream_t)stream;
+        mg::Family* f = env->fam;
+        const int n = env->num_envs;
+        mg_env::Advance& A = env->adv;
+        if (!A.ready) {  // the handle's first call: the only one that allocates (and therefore not capturable)
+            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+            if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+                throw std::runtime_error("mg_advance: the handle's first call allocates its scratch and cannot be captured; call it once eagerly");
+            A.actions.alloc((size_t)n * 2);
+            A.reward.alloc(n);
+            A.done.alloc(n);
+            A.reward64.alloc(n);
+            A.ep_reward.alloc(n);
+            A.ep_length.alloc(n);
+            memset(&A.ib, 0, sizeof(A.ib));
+            A.ib.struct_size = sizeof(A.ib);
+            A.ib.reward64_dev = A.reward64.p;
+            A.ib.ep_reward_dev = A.ep_reward.p;
+            A.ib.ep_length_dev = A.ep_length.p;
+            for (int k = 0; k < MG_INFO_SLOTS && f->info_name(k); ++k) {
+                A.aux[k].alloc(n);
+                A.ib.aux_dev[k] = A.aux[k].p;
+            }
+            A.ready = true;
+        }
+        float* gt = f->gt_dim() ? gt_dev : nullptr;
+        if (f->advance(mg::AdvanceArgs{steps, eps, seed, step0, A.actions.p, A.reward.p, A.done.p, gt, A.ib, o}, st)) {
+            env->advance_fused_steps += steps;
+            return;
+        }
+        for (int t = 0; t < steps; ++t) {  // the loop of the definition
+            f->expert_actions(mg::ExpertArgs{eps, mg::expert_base(seed, step0 + (uint64_t)t), A.actions.p}, st);
+            f->step(A.actions.p, nullptr, A.reward.p, A.done.p, gt, &A.ib, 1, st);
+            if (out) {
+                hipLaunchKernelGGL(advance_accumulate_kernel, dim3((n + 255) / 256), dim3(256), 0, st, n, t == 0 ? 1 : 0, A.ib, (const uint8_t*)A.done.p, o);
+                MG_HIP(hipGetLastError());
+            }
+        }
+        env->headless_steps += steps;
     });
 }
 
@@ -606,6 +697,10 @@ int mg_debug_counter(mg_env* env, const char* name, int64_t* value) {
         MG_HIP(hipDeviceSynchronize());
         if (std::string(name) == "final_obs_generic_steps") {  // every id: which way mg_step kept the terminal observations is decided in this file
             *value = env->final_obs_generic_steps;
+            return;
+        }
+        if (std::string(name) == "headless_steps" || std::string(name) == "advance_fused_steps") {  // every id: counted in this file
+            *value = std::string(name) == "headless_steps" ? env->headless_steps : env->advance_fused_steps;
             return;
         }
         if (!env->fam->debug_counter(name, value)) throw std::runtime_error(std::string("mg_debug_counter: no counter named ") + name + " for " + env->id);

@@ -201,6 +201,21 @@ struct KernelProfile {
 
 struct ExpertArgs;  // mg_expert.hpp
 
+// mg_advance (include/memgym.h) as it reaches a family that can run the whole loop inside its own launches: the policy's arguments, the handle's
+// scratch rows (what the loop's mg_expert_actions / mg_step calls would be given: info holds reward64, the episode record and the named aux slots,
+// nothing else) and the caller's sums.
+struct AdvanceArgs {
+    int steps;
+    double eps;
+    uint64_t seed, step0;
+    int32_t* actions;
+    float* reward;
+    uint8_t* done;
+    float* gt;  // the caller's, or NULL
+    mg_info_buffers info;
+    mg_advance_out out;
+};
+
 // What the C ABI (mg_api.hip) sees of an environment family, and the host-side plumbing the three families share: the error
 // word, the RNG streams, the "seeded" / "geometry changed" guards and the debug view's scratch frames.
 class Family {
@@ -234,8 +249,13 @@ class Family {
         if (set_of_dev) throw OptionError{-3, "this env id has no per-instance option sets in this build (use one handle per option set)"};
     }
     virtual void reset(const int64_t* seeds, const uint8_t* mask, void* obs, float* gt, hipStream_t s) = 0;
+    // obs == NULL: a HEADLESS step (include/memgym.h: mg_step) -- the family's plain arrangement without its raster launch; everything but the
+    // frames, the descriptors included, is what a drawn step of the same handle leaves (info->final_obs_dev is NULL then: mg_step refuses the pair)
     virtual void step(const int32_t* actions, void* obs, float* reward, uint8_t* done, float* gt,
                       const mg_info_buffers* info, int autoreset, hipStream_t s) = 0;
+    // mg_advance: true = the family has run the loop of include/memgym.h's definition inside launches of its own (the mortar family:
+    // mortar_advance_kernel); false = it has no such form (or the lab build switched it off) and nothing happened: mg_api.hip runs the loop.
+    virtual bool advance(const AdvanceArgs& /*v*/, hipStream_t /*s*/) { return false; }
     // rasterise the CURRENT frame descriptors of the instances with only[i] != 0 into `obs` (others untouched)
     virtual void raster_only(void* obs, const uint8_t* only, hipStream_t s) = 0;
     // true: step(..., autoreset = 1) with info->final_obs_dev set keeps the terminal observations ITSELF (the frame workgroup of a finishing

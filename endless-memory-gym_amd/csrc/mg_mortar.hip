@@ -14,6 +14,7 @@
 //   mg_mortar_step.hpp        reset and step of one instance (mortar_reset, mortar_step_body); mortar_reset_kernel, mortar_step_kernel
 //   mg_mortar_one_launch.hpp  mortar_step_raster_kernel: the step as one launch, its claim / hand-over word, RESCUE_AFTER_TICKS
 //   mg_mortar_expert.hpp      mortar_expert_kernel: the scripted teacher of the five ids (mg_expert_actions), a launch of its own
+//   mg_mortar_advance.hpp     mortar_advance_kernel: K steps under the teacher without a frame (mg_advance), teacher + step + sums per lane in one launch
 //
 // The launches of a step as shipped:
 //   ONE launch for handles with one option set, in every observation format (mortar_step_raster_kernel: the step's workgroups lead the raster's grid and a frame waits for its own
@@ -35,6 +36,7 @@
 #include "mg_mortar_step.hpp"
 #include "mg_mortar_one_launch.hpp"
 #include "mg_mortar_expert.hpp"
+#include "mg_mortar_advance.hpp"
 
 namespace mg {
 using namespace v1;  // raster generation 1 (see mg_raster_v1.hpp)
@@ -250,7 +252,8 @@ class MortarFamily : public Family {
         sets_.upload(s);
         const MortarStepArgs sa{P_, n_, io(), actions, reward, done, gt_dim() ? gt : nullptr, ib, autoreset, handover_.p, nullptr};
         // one launch: mortar_step_raster_kernel (handles with ONE option set: the per-set step code reads its parameters from memory)
-        if (one_launch(s)) {
+        // (a headless step, obs == NULL: mortar_step_kernel alone)
+        if (obs && one_launch(s)) {
             epoch_ = epoch_ % 255u + 1u;  // 1 .. 255: never the 0 of a fresh hand-over array (resets and two-launch steps do not write the words)
             ++ticket_;                    // claim words hold the ticket of the last one-launch step: never this one
             const int logic_wgs = (n_ + 255) / 256;
@@ -286,9 +289,28 @@ class MortarFamily : public Family {
         const int sb = step_block(256);
         with_bool(sets_.per_set(), [&](auto PS) { launch(mortar_step_kernel<decltype(PS)::value>, dim3((n_ + sb - 1) / sb), dim3(sb), 0, s, sa); });
         end_logic(s);
+        if (!obs) return;
         prof.begin(1, s);
         raster(obs, s);
         prof.end(1, s);
+    }
+
+    // mg_advance inside ONE launch per ADVANCE_MAX_STEPS steps (mg_mortar_advance.hpp); lab build, MEMGYM_MORTAR_ADVANCE_FUSE=0: the loop form
+    // of mg_api.hip -- expert launch, headless step, accumulate launch per step -- for A/B measurements (tools/headless_bench.py flips it
+    // between calls of one process: read at every call)
+    bool advance(const AdvanceArgs& v, hipStream_t s) override {
+        if (!lab_flag("MEMGYM_MORTAR_ADVANCE_FUSE", true)) return false;
+        if (dirty_) throw std::runtime_error("options that change geometry need a reset before the next step");
+        sets_.upload(s);
+        const MortarStepArgs sa{P_, n_, io(), v.actions, v.reward, v.done, gt_dim() ? v.gt : nullptr, v.info, 1, handover_.p, nullptr};
+        for (int t0 = 0; t0 < v.steps; t0 += ADVANCE_MAX_STEPS) {
+            const int k = v.steps - t0 < ADVANCE_MAX_STEPS ? v.steps - t0 : ADVANCE_MAX_STEPS;
+            const MortarAdvanceArgs aa{k, t0 == 0 ? 1 : 0, v.eps, v.seed, v.step0 + (uint64_t)t0, v.actions, v.out};
+            with_bool(sets_.per_set(), [&](auto PS) {
+                launch_checked(mortar_advance_kernel<decltype(PS)::value>, dim3((n_ + 255) / 256), dim3(256), 0, s, sa, aa);
+            });
+        }
+        return true;
     }
 
     std::vector<std::pair<void*, size_t>> state_blobs() override {

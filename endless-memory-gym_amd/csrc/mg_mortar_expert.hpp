@@ -1,13 +1,12 @@
 // mg_mortar_expert.hpp -- Mortar Mayhem family (included by mg_mortar.hip only): the scripted teacher of all five ids, oracle/mgo_mortar.c mm_expert restated on
-// MortarState -- wait while commands are shown and while the tiles are on, else move to the target tile.
+// MortarState -- wait while commands are shown and while the tiles are on, else move to the target tile.  mortar_expert_lane is the teacher of ONE instance:
+// mortar_expert_kernel (mg_expert_actions) and mortar_advance_kernel (mg_advance, mg_mortar_advance.hpp) both call it.
 #pragma once
 #include "mg_expert.hpp"
 #include "mg_mortar_types.hpp"
 
 namespace mg {
-__global__ __launch_bounds__(EXPERT_BLOCK) void mortar_expert_kernel(MortarParams P0, int n, MortarIO io, ExpertArgs x) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
+__device__ __forceinline__ void mortar_expert_lane(const MortarParams& P0, const MortarIO& io, const ExpertArgs& x, int i) {
     const MortarParams& P = io.set_of ? io.sets[set_index(io.set_of, i)] : P0;
     const MortarState s = io.state[i];
     const bool grid = P.variant == V_GRID;
@@ -27,5 +26,11 @@ __global__ __launch_bounds__(EXPERT_BLOCK) void mortar_expert_kernel(MortarParam
         a1 = expert_axis_action(dy, P.v_axis_i);
     }
     expert_store(x, i, grid, a0, a1);
+}
+
+__global__ __launch_bounds__(EXPERT_BLOCK) void mortar_expert_kernel(MortarParams P0, int n, MortarIO io, ExpertArgs x) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    mortar_expert_lane(P0, io, x, i);
 }
 }  // namespace mg

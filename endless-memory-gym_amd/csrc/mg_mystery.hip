@@ -282,12 +282,14 @@ class MysteryFamily : public Family {
             // lazy initial segments need the fused launch (its frame workgroups carry the background jobs); any other path
             // first generates what earlier fused steps left owed
             // (per-instance option sets: the plain arrangement -- step kernel, queue server, raster -- whose kernels have a <PS> form)
-            const bool fused = steps_fused();
+            // (a headless step, obs == NULL: the plain arrangement as well, without its raster launch; the next drawn step is fused again)
+            const bool fused = obs && steps_fused();
             P_.lazy = (fused && lazy_wanted_) ? 1 : 0;
             P_.pre = (P_.lazy && pre_wanted_) ? 1 : 0;
             static const int lazy_append = lab_int("MEMGYM_EMP_LAZY_APPEND", 1);
             P_.lazy_append = (P_.lazy && lazy_append) ? 1 : 0;
-            if (!P_.lazy && owed_possible_) flush_owed(s);
+            // (a headless step that is being captured flushes whether or not anything is owed NOW: drawn steps may run between the replays)
+            if (!P_.lazy && (owed_possible_ || (!obs && capturing(s)))) flush_owed(s);
             if (P_.lazy) owed_possible_ = true;
             sets_.upload(s);
             const int sb = step_block(256);
@@ -347,7 +349,8 @@ class MysteryFamily : public Family {
             serve(false, nullptr, reward, done, gt, ib, autoreset, s);
         } else {
             // (per-instance option sets: only this kernel has a <PS> form -- the raster launch's path service reads nothing of the options)
-            const int defer = (autoreset && !big_sprites_) ? defer_mode() : 0;
+            // (a headless step, obs == NULL: the paths are generated in the step kernel -- there is no raster launch to serve them)
+            const int defer = (obs && autoreset && !big_sprites_) ? defer_mode() : 0;
             sets_.upload(s);
             // (three of the four <PS, FINAL> forms exist: terminal observations are kept by handles with one option set only)
             auto step_launch = [&](auto kernel) { launch(kernel, dim3(blocks()), dim3(256), WS_BYTES, s, P_, io(), actions, reward, done, nullptr, ib, autoreset, lpw(), defer); };
@@ -370,6 +373,7 @@ class MysteryFamily : public Family {
             }
         }
         end_logic(s);
+        if (!obs) return;
         prof.begin(1, s);
         raster(obs, s);
         prof.end(1, s);
@@ -445,6 +449,10 @@ class MysteryFamily : public Family {
     void raster_debug(void* frames, hipStream_t s) override;
 
    private:
+    static bool capturing(hipStream_t s) {
+        hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+        return hipStreamIsCapturing(s, &st) == hipSuccess && st != hipStreamCaptureStatusNone;
+    }
     int64_t emp_fused_steps_ = 0;  // debug_counter("emp_fused_steps")
     // instance-carrying lanes per wave (see instance_of_lane); MEMGYM_MYSTERY_LPW overrides for tuning
     int lpw() const {

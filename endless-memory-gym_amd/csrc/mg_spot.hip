@@ -293,7 +293,8 @@ class SpotFamily : public Family {
         // (a call that keeps terminal observations: always deferred -- the service workgroup draws the terminal frame from the descriptor this
         // launch leaves, then resets: keeps_final_obs)
         const bool keep_final = autoreset && ib.final_obs_dev && keeps_final_obs(s);
-        const int defer = (autoreset && (fuse_resets() || keep_final) && !sets_.per_set() && fused_here(s)) ? 1 : 0;
+        // (a headless step, obs == NULL: never deferred -- there is no raster launch to serve the resets)
+        const int defer = (obs && autoreset && (fuse_resets() || keep_final) && !sets_.per_set() && fused_here(s)) ? 1 : 0;
         const int sb = step_block(256);
         const SpotStepArgs sa{P_, io(), actions, reward, done, gt, ib, autoreset, defer};
         const dim3 sg((n_ * SLOTS + sb - 1) / sb);
@@ -328,7 +329,7 @@ class SpotFamily : public Family {
                 });
             });
             ++spot_fused_steps_;
-        } else {
+        } else if (obs) {
             raster(obs, s);
         }
         prof.end(1, s);

@@ -27,6 +27,11 @@ class SingleIO(C.Structure):  # include/memgym.h: mg_single_io (host addresses o
                 ("gt", C.c_void_p), ("ep_reward", C.c_void_p), ("ep_length", C.c_void_p), ("aux", C.c_void_p * MG_INFO_SLOTS)]
 
 
+class AdvanceOut(C.Structure):  # include/memgym.h: mg_advance_out (device arrays [num_envs], any may be NULL)
+    _fields_ = [("struct_size", C.c_size_t), ("reward_sum_dev", C.c_void_p), ("episodes_dev", C.c_void_p), ("ep_reward_sum_dev", C.c_void_p),
+                ("ep_length_sum_dev", C.c_void_p), ("aux_sum_dev", C.c_void_p * MG_INFO_SLOTS)]
+
+
 class ObsAllocInfo(C.Structure):
     _fields_ = [("zones", C.c_int), ("pieces", C.c_int), ("piece_bytes", C.c_size_t), ("searched_bytes", C.c_size_t),
                 ("probe_same_tbps", C.c_double), ("probe_cross_tbps", C.c_double), ("search_ms", C.c_double)]
@@ -86,6 +91,8 @@ def _load():
         L.mg_store_probe.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
     if hasattr(L, "mg_expert_actions"):  # (absent from the older builds tools/ A/B against through MEMGYM_HIP_LIB)
         L.mg_expert_actions.argtypes = [C.c_void_p, C.c_double, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
+    if hasattr(L, "mg_advance"):  # (absent from the older builds tools/ A/B against through MEMGYM_HIP_LIB)
+        L.mg_advance.argtypes = [C.c_void_p, C.c_int32, C.c_double, C.c_uint64, C.c_uint64, C.c_void_p, C.POINTER(AdvanceOut), C.c_void_p]
     L.mg_enable_peer_access.argtypes = [C.c_int, C.c_int]
     L.mg_debug_rng.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
     L.mg_debug_set_rng.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]

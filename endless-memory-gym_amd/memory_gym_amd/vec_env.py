@@ -243,6 +243,8 @@ class VecMemoryGym:
         self.autoreset = True
         self._seeded = False  # no instance has an RNG stream before the first reset (or load_state_dict)
         self._swapped = False  # use_obs_buffer() since the last call that wrote every row
+        self._stale = False    # step(render=False) / advance(render=False) since the last call that wrote every row: `obs` holds old bytes
+        self._adv = None       # advance(): the sums' tensors and the mg_advance_out over them, made at the first call
         # `truncation` is always False in the reference; on_capacity="truncate": True where the episode ended on a capacity of this build
         self._truncated = self.capacity_u8.view(torch.bool) if self.capacity_u8 is not None else torch.zeros(N, dtype=torch.bool, device=dev)
         self._n_actions = self.num_envs * self.action_dim
@@ -391,12 +393,13 @@ class VecMemoryGym:
                 self._apply_options_masked(options, mask)
             s = self._seed_tensor(seed)
             m = None if mask is None else mask.to(device=self.device, dtype=torch.uint8).contiguous()
-            if m is not None and self._swapped:
+            if m is not None and (self._swapped or self._stale):
                 # a masked reset writes the rows of the masked instances only; after use_obs_buffer() the other rows of the new
-                # buffer hold whatever was there: draw every instance's CURRENT frame into it first (one raster launch, this
-                # sequence only).  (Rows a masked reset had left untouched right before the swap stay as they are: mg_render.)
+                # buffer hold whatever was there, and after headless steps (render=False) frames of long ago: draw every instance's
+                # CURRENT frame into it first (one raster launch, these sequences only).  (Rows a masked reset had left untouched
+                # right before the swap stay as they are: mg_render.)
                 _native.check(_native.LIB.mg_render(self._h, self.obs.data_ptr(), self._stream()), "mg_render")
-            self._swapped = False
+            self._swapped = self._stale = False
             _native.check(_native.LIB.mg_reset(self._h, None if s is None else s.data_ptr(),
                                                None if m is None else m.data_ptr(), self.obs.data_ptr(),
                                                self.gt.data_ptr() if self.gt_dim else None, self._stream()), "mg_reset")
@@ -406,7 +409,13 @@ class VecMemoryGym:
         info = {"ground_truth": self.gt if self.gt64 is None else self.gt64} if self.gt_dim else {}
         return self._obs(), info
 
-    def step(self, actions):
+    def step(self, actions, render=True):
+        """Env.step for every instance.  render=False is the HEADLESS step (include/memgym.h: mg_step with obs_dev == NULL): everything but
+        the frames -- state, random streams, rewards, dones, infos -- is what the drawn step gives, the first element of the returned tuple
+        is None and `obs` keeps its old bytes until redraw(), the next drawn step or a reset.  Terminal observations are frames: a handle
+        made with final_observation=True refuses render=False (ValueError) before anything is stepped."""
+        if not render and self.final_obs is not None:
+            raise ValueError("step(render=False) on a handle with final_observation=True: terminal observations are frames")
         a = actions
         if not (isinstance(a, torch.Tensor) and a.dtype == torch.int32 and a.device == self.device and a.is_contiguous()):
             a = a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a))
@@ -414,23 +423,75 @@ class VecMemoryGym:
         assert a.numel() == self._n_actions, "actions must have shape [N] or [N, 2]"
         if torch.cuda.current_device() != self.device.index:
             with torch.cuda.device(self.device):
-                self._launch_step(a)
+                self._launch_step(a, render)
         else:
-            self._launch_step(a)
-        self._swapped = False  # a step writes every row
+            self._launch_step(a, render)
+        if render:
+            self._swapped = self._stale = False  # a drawn step writes every row
+        else:
+            self._stale = True
         _native.LIB.mg_peek_errors(self._h, self._p_err)  # host-mapped word: no synchronisation
         if self._err.value & ~self._tolerated:
             self.check_errors()
         info = dict(self._info_dict)
         if self.final_obs is not None and self.autoreset:  # rows valid where done_mask is set
             info["final_observation"] = self.final_obs
-        return self._obs(), self.reward, self._done_bool, self._truncated, info
+        return (self._obs() if render else None), self.reward, self._done_bool, self._truncated, info
 
-    def _launch_step(self, a):
-        rc = _native.LIB.mg_step(self._h, a.data_ptr(), self.obs.data_ptr(), self._p_reward, self._p_done, self._p_gt, self._p_info,
+    def _launch_step(self, a, render=True):
+        rc = _native.LIB.mg_step(self._h, a.data_ptr(), self.obs.data_ptr() if render else None, self._p_reward, self._p_done, self._p_gt, self._p_info,
                                  1 if self.autoreset else 0, self._raw_stream())
         if rc != 0:
             _native.check(rc, "mg_step")
+
+    def redraw(self):
+        """Draw every instance's CURRENT frame into `obs` (include/memgym.h: mg_render) -- after headless steps exactly the frame the
+        last step would have drawn, the first frame of the new episode where that step auto-reset the instance.  Returns what reset()
+        returns as observation.  One raster launch on the current stream; no state changes."""
+        with torch.cuda.device(self.device):
+            _native.check(_native.LIB.mg_render(self._h, self.obs.data_ptr(), self._stream()), "mg_render")
+        self._swapped = self._stale = False
+        return self._obs()
+
+    def advance(self, steps, eps=0.0, seed=0, step=None, render=True, stats=True):
+        """`steps` steps under the scripted teacher without a frame (include/memgym.h: mg_advance): state, random streams and error
+        bits afterwards are those after `for t: step(expert_actions(eps, seed, step + t), render=False)` with auto-reset, whatever
+        `autoreset` says.  eps = 0 is the teacher, eps = 1 the uniformly random policy.  Uses: the warm-up behind reset(seed=...) that takes
+        the episodes out of phase; the teacher's return and success rate per curriculum setting; a check that an option set is solvable.
+        -> (obs or None, stats).  render=True draws the frames the last step left (redraw()); render=False leaves `obs` stale.
+        stats (None with stats=False): a dict of [N] tensors over THIS call's steps, overwritten by the next call -- "reward" (float64,
+        the step rewards added in step order), "episodes" (int32, episodes that ended), "episode_reward" (float64) / "episode_length" (int64):
+        sums of info["reward"] / info["length"] over those episodes, and one float64 sum per entry of `info_names` (e.g. "success").
+        step=None continues the call numbering of expert_actions() and advances it by `steps`.  Episodes that end inside the call are
+        counted, not shown: there are no terminal observations here, on any handle.  Nothing synchronises; the handle's first call
+        allocates scratch, every later one is capturable (the arguments are then the captured values).  The five Mortar Mayhem ids
+        run the whole loop inside one launch per 1,024 steps; the other five take it launch by launch."""
+        steps = int(steps)
+        if self._adv is None and stats:
+            N, dev = self.num_envs, self.device
+            t = {"reward": torch.zeros(N, dtype=torch.float64, device=dev), "episodes": torch.zeros(N, dtype=torch.int32, device=dev),
+                 "episode_reward": torch.zeros(N, dtype=torch.float64, device=dev), "episode_length": torch.zeros(N, dtype=torch.int64, device=dev)}
+            out = _native.AdvanceOut()
+            out.struct_size = C.sizeof(_native.AdvanceOut)
+            out.reward_sum_dev, out.episodes_dev = t["reward"].data_ptr(), t["episodes"].data_ptr()
+            out.ep_reward_sum_dev, out.ep_length_sum_dev = t["episode_reward"].data_ptr(), t["episode_length"].data_ptr()
+            for k, nm in enumerate(self.info_names):
+                t[nm] = torch.zeros(N, dtype=torch.float64, device=dev)
+                out.aux_sum_dev[k] = t[nm].data_ptr()
+            self._adv = (t, out)
+        mask = (1 << 64) - 1
+        with torch.cuda.device(self.device):
+            _native.check(_native.LIB.mg_advance(self._h, steps, float(eps), int(seed) & mask, int(self._expert_calls if step is None else step) & mask,
+                                                 self._p_gt, C.byref(self._adv[1]) if stats else None, self._stream()), "mg_advance")
+            if self.gt64 is not None:
+                _native.check(_native.LIB.mg_ground_truth64(self._h, self.gt64.data_ptr(), self._stream()), "mg_ground_truth64")
+        if step is None:
+            self._expert_calls += steps
+        self._stale = True
+        _native.LIB.mg_peek_errors(self._h, self._p_err)  # host-mapped word: no synchronisation
+        if self._err.value & ~self._tolerated:
+            self.check_errors()
+        return (self.redraw() if render else None), (dict(self._adv[0]) if stats else None)
 
     def expert_actions(self, eps=0.0, seed=0, step=None, out=None):
         """The scripted teacher (include/memgym.h: mg_expert_actions): for every instance the action the CPU oracle's expert hook gives

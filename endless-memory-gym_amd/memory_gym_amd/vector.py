@@ -101,6 +101,12 @@ class GymnasiumVectorEnv(_Base):
         """The scripted teacher's actions in the current states (VecMemoryGym.expert_actions): what step() takes; numpy with as_numpy."""
         return self._host(self.env.expert_actions(eps=eps, seed=seed, step=step, out=out))
 
+    def advance(self, steps, eps=0.0, seed=0, step=None, render=True, stats=True):
+        """`steps` steps under the scripted teacher without a frame (VecMemoryGym.advance) -> (obs or None, stats); numpy with as_numpy.
+        Episodes that end inside the call are NOT reported as `final_observation` / `final_info`: they are counted and summed in `stats`."""
+        obs, st = self.env.advance(steps, eps=eps, seed=seed, step=step, render=render, stats=stats)
+        return (None if obs is None else self._host(obs)), (None if st is None else self._host(st))
+
     # gymnasium.vector.VectorEnv API surface used by trainers
     def step_async(self, actions):
         self._pending = actions

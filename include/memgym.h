@@ -194,7 +194,19 @@ int mg_render_debug(mg_env* env, uint8_t* rgb_dev, void* stream);
  * done_dev: uint8 [num_envs] (`truncation` is always False in the reference).
  * autoreset != 0: an instance that reports done is reset in the same call with seed=None (its RNG
  * stream continues, exactly what `env.reset()` right after a terminal step does) and obs_dev/gt_dev
- * hold the first observation of the new episode; the finished episode's info is in `info`. */
+ * hold the first observation of the new episode; the finished episode's info is in `info`.
+ *
+ * HEADLESS STEP: obs_dev == NULL steps without drawing -- every env id, every observation format, one or several option sets,
+ * autoreset 0 and 1, with or without any of the optional buffers.  State, every instance's PCG64 stream, reward, done, ground truth,
+ * the episode records, the error bits and the frame descriptors the step leaves are bit for bit those of a drawn step of the same
+ * handle; the frames are simply not written (the raster is 85-95 % of a drawn step).  mg_render after any number of headless steps
+ * writes for every instance exactly the frame the last step would have drawn -- for an instance that step auto-reset, the first frame of
+ * the new episode.  Headless and drawn steps alternate freely in one handle.  A headless step takes the family's plain arrangement
+ * without its raster launch: the mortar family's step kernel alone; the spotlight family's and the finite Mystery Path ids' step
+ * kernel with the resets / paths generated in it; Endless-MysteryPath-v0's step kernel and its queue server as a launch of its own
+ * (whatever earlier fused steps left owed is generated first, and the next drawn step is fused again) -- a linear chain of launches,
+ * capturable into a HIP graph.  Refused (-1): obs_dev == NULL together with info->final_obs_dev -- terminal observations are frames.
+ * mg_reset and mg_single_step keep requiring their buffers.  mg_debug_counter "headless_steps" counts these calls. */
 int mg_step(mg_env* env, const int32_t* actions_dev, void* obs_dev, float* reward_dev, uint8_t* done_dev,
             float* gt_dev, const mg_info_buffers* info, int autoreset, void* stream);
 
@@ -219,6 +231,35 @@ int mg_ground_truth64(mg_env* env, double* gt64_dev, void* stream);
  * step are kernel arguments, so a captured launch replays the values it was captured with (a trainer that wants fresh random actions per
  * replay updates the node's arguments or leaves the call outside the graph). */
 int mg_expert_actions(mg_env* env, double eps, uint64_t seed, uint64_t step, int32_t* actions_dev, void* stream);
+
+/* `steps` steps under the scripted teacher WITHOUT A FRAME: the warm-up behind reset(seed) that takes the instances' episodes out of
+ * phase, the return of the teacher per curriculum setting, the check that an option set is solvable.  DEFINITION: state, streams, frame
+ * descriptors and error bits afterwards equal bit for bit those after
+ *     for t in 0 .. steps-1:
+ *         mg_expert_actions(env, eps, seed, step0 + t, A, stream)
+ *         mg_step(env, A, NULL, R, D, gt_dev, info, 1, stream)            (headless, auto-reset)
+ * and the sums in `out` are the ones that loop produces; eps = 1 is therefore the uniformly random policy and eps = 0 the teacher.
+ * gt_dev may be NULL, otherwise it holds the ground truth after the last step.  `out` may be NULL.  mg_render draws the frames the last
+ * step left.  Nothing synchronises.  The scratch the loop needs (actions, reward, done, one row of episode records: about 50 bytes per
+ * instance) is allocated AT THE HANDLE'S FIRST mg_advance; every later call allocates nothing and can be captured into a HIP graph --
+ * steps, eps, seed and step0 are then the captured values, as with mg_expert_actions.
+ * The five Mortar Mayhem ids run the loop INSIDE one launch (mortar_advance_kernel: a lane per instance plays teacher, step and sums by
+ * itself; at most 1,024 steps per launch, a longer call is split); mg_debug_counter "advance_fused_steps" counts the steps taken this
+ * way, which are no "headless_steps".  The other five ids take the loop above on the host -- expert launch, headless step, one small
+ * accumulate launch per step; their resets are cooperative (A* paths, 16 lanes per spotlight instance), so there is no in-launch form
+ * for them yet -- and count as "headless_steps".  Terminal observations do not exist here: episodes that end inside the call are
+ * counted and summed, not shown.
+ * Errors (-1): before the first mg_reset / mg_set_state; steps < 1; eps outside [0, 1]; a geometry option set since the last reset. */
+typedef struct mg_advance_out {      /* all device arrays [num_envs], any may be NULL; OVERWRITTEN with this call's sums */
+    size_t   struct_size;             /* in: sizeof(mg_advance_out) of the caller's header                                                 */
+    double*  reward_sum_dev;          /* step rewards as the reference's doubles, added in step order                      */
+    int32_t* episodes_dev;            /* episodes that ended in these steps (capacity ends included)                       */
+    double*  ep_reward_sum_dev;       /* sum of info["reward"] over those episodes, in order of ending                     */
+    int64_t* ep_length_sum_dev;       /* sum of info["length"]                                                             */
+    double*  aux_sum_dev[MG_INFO_SLOTS]; /* sum of aux slot k (mg_info_name), e.g. "success"; slots without a name are not written */
+} mg_advance_out;
+int mg_advance(mg_env* env, int32_t steps, double eps, uint64_t seed, uint64_t step0,
+               float* gt_dev, const mg_advance_out* out, void* stream);
 
 /* The single-instance fast path (BASELINE config C1: gym.make(id), one instance, numpy in / numpy out -- the reference's own loop,
  * /root/reference/bench.py:12-30).  For a handle with num_envs == 1, mg_single_open allocates every per-call buffer in pinned,
@@ -373,7 +414,9 @@ int mg_enable_peer_access(int device, int peer_device);
  * (spot_raster_serve_kernel), counted on the host.  "emp_fused_steps" (Endless-MysteryPath): mg_step calls of this handle that went out as the
  * fused raster / service launch (emp_raster_serve_kernel), counted on the host.  "final_obs_generic_steps" (every id): mg_step calls of this handle that kept terminal observations
  * (mg_info_buffers.final_obs_dev, autoreset) on the generic path -- a step without auto-reset, a copy of the finished rows, a masked reset --
- * instead of inside the step's own launches, counted on the host.  Unknown name: -1.  Synchronous. */
+ * instead of inside the step's own launches, counted on the host.  "headless_steps" (every id): headless steps of this handle -- mg_step calls
+ * with obs_dev == NULL and the steps mg_advance took through its loop form; "advance_fused_steps" (every id; only the mortar family has the
+ * form): steps mg_advance took inside mortar_advance_kernel.  Both counted on the host.  Unknown name: -1.  Synchronous. */
 int mg_debug_counter(mg_env* env, const char* name, int64_t* value);
 
 /* Test hook: copy the numpy-compatible PCG64 words of instance i to host:
