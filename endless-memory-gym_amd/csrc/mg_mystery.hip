@@ -63,6 +63,7 @@ __global__ __launch_bounds__(256) void mystery_debug_desc_kernel(MysteryParams P
     d.valid = 1;
     d.tile_mask[0] = d.tile_mask[1] = 0;
     if (!P.endless) {
+        mp_desc(P, s, d);  // from the state alone: a handle restored by mg_set_state has no frame descriptors before its first step
         d.pad8[0] = 1;
         const uint64_t ends = (1ull << (s.sx * G + s.sy)) | (1ull << (s.ex * G + s.ey));
         d.tile_mask[0] = s.path_mask & ~ends;
@@ -414,7 +415,7 @@ class MysteryFamily : public Family {
             *out = name == "emp_segments_sum" ? sum : (name == "emp_segments_max" ? mx : fmx);
             return true;
         }
-        const int k = name == "path_gen_ticks" ? 0 : (name == "path_gen_paths" ? 1 : (name == "emp_own_resets" ? 2 : (name == "emp_ahead_records" ? 3 : (name == "emp_final_served" ? 4 : -1))));
+        const int k = name == "path_gen_ticks" ? 0 : (name == "path_gen_paths" ? 1 : (name == "emp_own_resets" ? 2 : (name == "emp_ahead_records" ? 3 : (name == "emp_final_served" ? 4 : (name == "path_lane_paths" ? 5 : -1)))));
         if (k < 0 || !stats_.p) return false;
         unsigned long long v = 0;
         MG_HIP(hipMemcpy(&v, stats_.p + k, sizeof v, hipMemcpyDeviceToHost));

@@ -109,6 +109,7 @@ struct MysteryIO {
     const uint4* jump;  // [64][2] PCG64 jump constants {A^(k+1), S_(k+1)} (WaveRng)
     // telemetry of the finite variants' path generation inside the step's launches (bench.py: C3's measured reset share):
     // [0] wave-ticks (real-time clock, 10 ns) spent generating paths, [1] paths generated; mg_debug_counter "path_gen_ticks" / "path_gen_paths"
+    // finite: [5] those of [1] that the lane-per-path generator of mass resets made; mg_debug_counter "path_lane_paths"
     // endless: [2] resets a step did itself from a record generated ahead of time (counted by the lab build only), [3] such records generated
     unsigned long long* stats;
     // per-instance option sets (mg_set_option_set / mg_bind_option_sets): instance i runs under sets[set_of[i]]; both NULL while the

@@ -344,6 +344,8 @@ class SpotFamily : public Family {
         for (auto* a : {&sp_t_, &sp_speed_}) v.push_back({a->p, a->bytes()});
         v.push_back({flags_.p, flags_.bytes()});
         v.push_back({exit_hist_.p, exit_hist_.bytes()});
+        // (the frame descriptors: what mg_render, mg_render_debug and a reset's stale holes read BEFORE the restored handle's first step)
+        v.push_back({desc_.p, desc_.bytes()});
         rng_.blobs(v);
         return v;
     }

@@ -185,7 +185,10 @@ int mg_render(mg_env* env, void* obs_dev, void* stream);
  * rgb_dev uint8 [num_envs][336 y][336 x][3].  Changes nothing the observations, rewards or RNG streams depend on; the
  * only state it touches is the mortar family's counter of entries popped from the reference's CLONE of the command
  * visualisation list (mortar_mayhem_grid.py:122: every debug render pops one), so that zero, one or several renders
- * between steps show what the reference shows.  Synchronous (allocates and frees a scratch buffer); not a hot path. */
+ * between steps show what the reference shows.  After headless steps (obs_dev == NULL) or mg_advance it shows the state the last
+ * of those steps left -- the view a drawn run of the same steps gives, episodes that ended inside included -- and right after
+ * mg_set_state the view of the handle the blob was taken from (tests/test_gpu_debug_arrangements.py).  Synchronous (allocates and
+ * frees a scratch buffer); not a hot path. */
 int mg_render_debug(mg_env* env, uint8_t* rgb_dev, void* stream);
 
 /* Env.step(action) (e.g. mortar_mayhem_grid.py:280-375) for all instances.
@@ -296,7 +299,9 @@ int mg_single_step(mg_env* env, int32_t a0, int32_t a1, void* stream);
  * (-1, message in mg_last_error) a blob whose magic, version, env id, num_envs or payload size differ from the handle's
  * instead of mis-assigning it.  (The finite Mystery Path ids' blobs carry the order of every instance's path since mg_expert_actions exists:
  * 64 bytes per instance more than before, so an earlier blob of those two ids is refused by its payload size; the other eight ids' layout
- * is what it was.) */
+ * is what it was.  The spotlight family's blobs carry the frame descriptors as well, 128 bytes per instance more -- what mg_render,
+ * mg_render_debug and a reset's stale holes read before the restored handle's first step; an earlier blob of those two ids is refused
+ * by its payload size in the same way.) */
 #define MG_STATE_VERSION 8u
 size_t mg_state_size(const mg_env* env);
 int mg_get_state(mg_env* env, void* host_buf, size_t size);
@@ -406,7 +411,8 @@ int mg_enable_peer_access(int device, int peer_device);
 /* Test / telemetry hook: named counters of a handle.  "one_launch_rescues" (mortar family): 64-instance slots of the one-launch
  * step that a frame wave stepped itself because the step workgroup's wave had not claimed them in time (0 on a GPU that
  * dispatches the step workgroups first; tests/test_gpu_one_launch.py forces the other order).  "path_gen_ticks" / "path_gen_paths"
- * (finite Mystery Path: wave-ticks and paths of the A* generation inside the step's launches).  "emp_ahead_records"
+ * (finite Mystery Path: wave-ticks and paths of the A* generation inside the step's launches; "path_lane_paths": those of them that the
+ * lane-per-path generator made, which serves a raster launch's queue of more than 1,024 resets).  "emp_ahead_records"
  * (Endless-MysteryPath: first segments of NEXT episodes generated ahead of time, which a finishing instance's own step turns into its
  * reset -- EndlessMysteryPathEnv.reset, endless_mystery_path.py:195-280, without a queue entry); "emp_own_resets" (such resets; counted
  * by the lab build only).  "one_launch_steps" (mortar family): mg_step calls of this handle that went out as the one-launch kernel, counted

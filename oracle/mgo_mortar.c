@@ -55,6 +55,7 @@ typedef struct {
     int* vis; /* _command_visualization, entries 0..8 or 9 for "" */
     int vis_head, vis_len, vis_cap;
     int clone_pops; /* render(): entries popped so far from _command_visualization_clone (copied at reset and at an endless regeneration) */
+    int scene_dbg, scene_glyph; /* scene hook: the debug view shows scene_glyph instead of popping the clone (until the next reset / step) */
     int glyph; /* glyph drawn in the last frame (-1 none) */
     mgo_surf* glyph_surf[10];
     int tx, ty, cur_cmd, cmd_steps, verify_step, total_completed, t;
@@ -178,8 +179,12 @@ static void mm_debug(mgo_env* e, mgo_surf* dst) {
     } else {
         mgo_blit(dst, m->agent.sprites[0], m->agent.rect.x, m->agent.rect.y);
     }
-    if (m->vis_head < m->vis_len) {
-        int idx = m->clone_pops++, g = idx >= 0 && idx < m->vis_len ? m->vis[idx] : 9;
+    if (m->scene_dbg || m->vis_head < m->vis_len) {
+        int g = m->scene_dbg ? m->scene_glyph : 9;
+        if (!m->scene_dbg) {
+            int idx = m->clone_pops++;
+            if (idx >= 0 && idx < m->vis_len) g = m->vis[idx];
+        }
         if (g >= 0 && g < 9) { /* 9 = "" (delay frames) */
             double rect_dim = 88 * e->scale;
             int p = (int)((e->screen_dim / 2) - floor(rect_dim / 2));
@@ -192,7 +197,12 @@ static void mm_debug(mgo_env* e, mgo_surf* dst) {
     mgo_draw_circle(dst, MGO_RGB(0, 255, 0), px, py, (int)floor(m->tile_dim / 2), (int)(8 * e->scale));
 }
 
-/* scene hook: v = {ax, ay, sprite (0..7, -1 none), tiles_on, tx, ty, glyph (0..8, 9 blank, -1 none)} */
+static void mm_set_disp(mm_t* m, int sprite, int rect_is_agent);
+
+/* scene hook: v = {ax, ay, sprite (0..7, -1 none), tiles_on, tx, ty, glyph (0..8, 9 blank, -1 none)}
+ * optionally followed by {reserved (the fixture makers keep a mismatch count there), debug}: with debug != 0 the DEBUG view
+ * shows this scene as well -- the sprite at the scene's rect and the scene's glyph instead of the clone list's next entry,
+ * until the next reset / step.  Seven or eight values leave the debug view's state alone. */
 static int mm_scene(mgo_env* e, const double* v, int n) {
     mm_t* m = (mm_t*)e->impl;
     if (n < 7) return -1;
@@ -203,6 +213,12 @@ static int mm_scene(mgo_env* e, const double* v, int n) {
     m->ty = (int)v[5];
     if (on) mm_toggle_tiles(m, e->scale, 1, m->tx, m->ty, 1);
     mm_draw_frame(e, m, sprite >= 0 ? m->agent.sprites[sprite & 7] : NULL, &m->agent.rect, glyph);
+    if (n >= 9 && (int)v[8]) {
+        if (sprite >= 0) mm_set_disp(m, sprite & 7, 1);
+        else m->have_disp = 0;
+        m->scene_dbg = 1;
+        m->scene_glyph = glyph;
+    }
     return 0;
 }
 
@@ -224,6 +240,7 @@ static const mgo_rect* mm_disp_rect(const mm_t* m) { return m->disp_rect_is_agen
 static void mm_reset(mgo_env* e) {
     mm_t* m = (mm_t*)e->impl;
     double S = e->scale;
+    m->scene_dbg = 0;
     m->has_info = 0;
     m->t = 0;
     if (m->variant == MM_ENDLESS) {
@@ -357,6 +374,7 @@ static void mm_step(mgo_env* e, const int action[2]) {
     double reward = 0;
     int done = 0, success = 0, glyph = -1;
 
+    m->scene_dbg = 0;
     if (mm_vis_nonempty(m)) {
         glyph = mm_vis_pop(m);
         if (m->variant == MM_ENDLESS) {
@@ -505,6 +523,7 @@ static double mm_get(mgo_env* e, const char* f, int* ok) {
     F("expl_dur", m->expl_dur) F("expl_delay", m->expl_delay) F("max_episode_steps", m->max_episode_steps)
     F("total_completed", m->total_completed) F("t", m->t) F("show_dur", m->show_dur) F("show_delay", m->show_delay_v)
     F("gt0", e->gt[0]) F("gt1", e->gt[1])
+    F("clone_pops", m->clone_pops) F("vis_total", m->vis_len) /* the debug view's clone list: entries popped, entries it had */
     if (m->has_info) {
         F("info_reward", m->info_reward) F("info_length", m->info_length)
         if (m->variant != MM_ENDLESS) { F("info_success", m->info_success) }

@@ -332,10 +332,31 @@ static void mpf_step(mgo_env* e, const int action[2]) {
     e->done = done;
 }
 
-/* scene hook (finite variants): v = {ax, ay, sprite, cross_on, cross_cx, cross_cy, sx, sy, ex, ey, show_origin, show_goal} */
+/* scene hook (finite variants): v = {ax, ay, sprite, cross_on, cross_cx, cross_cy, sx, sy, ex, ey, show_origin, show_goal}
+ * optionally followed by {reserved (the fixture makers keep a mismatch count there), n_path, n_path x (x, y) END FIRST,
+ * n_walls, n_walls x (x, y)}: these cells replace the instance's path and walls, which only the debug view draws.  Twelve
+ * or thirteen values leave them alone. */
 static int mpf_scene(mgo_env* e, const double* v, int n) {
     mp_t* m = (mp_t*)e->impl;
     if (n < 12) return -1;
+    if (n >= 14) {
+        const int np_ = (int)v[13];
+        if (np_ < 0 || np_ > G * G || n < 15 + 2 * np_) return -1;
+        const int nw = (int)v[14 + 2 * np_];
+        if (nw < 0 || nw > G * G || n < 15 + 2 * np_ + 2 * nw) return -1;
+        const double* w = v + 15 + 2 * np_;
+        for (int i = 0; i < 2 * (np_ + nw); i++) {
+            const double c = i < 2 * np_ ? v[14 + i] : w[i - 2 * np_];
+            if (!(c >= 0 && c < G)) return -1;
+        }
+        m->path_len = np_;
+        for (int i = 0; i < np_; i++) m->path[i] = (pnode){(int)v[14 + 2 * i], (int)v[15 + 2 * i], 0, 0};
+        m->n_walls = nw;
+        for (int i = 0; i < nw; i++) {
+            m->walls[i][0] = (int)w[2 * i];
+            m->walls[i][1] = (int)w[2 * i + 1];
+        }
+    }
     const int d = (int)m->tile_dim;
     mgo_fill(m->path_surf, 0);
     if ((int)v[11]) mgo_draw_rect(m->path_surf, MGO_RGB(0, 255, 0), (int)((int)v[8] * m->tile_dim), (int)((int)v[9] * m->tile_dim), d, d, 0);

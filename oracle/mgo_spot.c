@@ -52,6 +52,7 @@ typedef struct {
     /* episode state */
     mgo_agent agent;
     int have_disp, disp_sprite, disp_x, disp_y; /* (rotated_agent_surface, rotated_agent_rect): informational only */
+    int disp_rect_is_agent; /* 1: rotated_agent_rect IS the current agent's rect (set by step); reset() makes a new agent */
     double health;
     spot_t spots[SP_MAX];
     int n_spots, spawn_timer, t, coin_t;
@@ -376,10 +377,14 @@ static void sp_reset(mgo_env* e) {
     e->ep_sum = 0;
     e->ep_len = 0;
     p->last_action[0] = p->last_action[1] = 0;
-    if (p->have_disp) { /* the stale (surface, rect) pair of the previous agent object lives on until the first step */
+    /* the stale (surface, rect) pair lives on until the first step: the rect of the agent object that STEPPED last
+     * (searing_spotlights.py:362 makes a new agent at every reset, :462 re-points the pair at a step only) -- after two resets
+     * in a row still that one, not the rect of the agent in between, which never stepped */
+    if (p->have_disp && p->disp_rect_is_agent) {
         p->disp_x = mgo_rect_cx(&p->agent.rect);
         p->disp_y = mgo_rect_cy(&p->agent.rect);
     }
+    p->disp_rect_is_agent = 0;
     static const int ROT[8] = {0, 45, 90, 135, 180, 225, 270, 315};
     int rotation = ROT[mgo_choice_index(&e->rng, 8)];
     mgo_agent_init(&p->agent, p->agent_speed, p->agent_scale, rotation);
@@ -497,6 +502,7 @@ static void sp_step(mgo_env* e, const int action[2]) {
     static const uint32_t ACT[3] = {MGO_RGB(120, 120, 120), MGO_RGB(116, 1, 113), MGO_RGB(255, 94, 14)};
     mgo_agent_step(&p->agent, action, &p->walkable);
     p->have_disp = 1;
+    p->disp_rect_is_agent = 1;
     p->disp_sprite = p->agent.rotation / 45;
     p->disp_x = mgo_rect_cx(&p->agent.rect);
     p->disp_y = mgo_rect_cy(&p->agent.rect);

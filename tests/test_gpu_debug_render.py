@@ -1,6 +1,10 @@
 """GPU (-m gpu): render("debug_rgb_array") -- mg_render_debug, the ground-truth view of every instance stretched to
 336 x 336 -- against the oracle's debug view (itself pinned to the reference's *_gt.gif recordings,
-tests/test_oracle_debug_views.py), for all ten env ids, after the reset, after every step and across same-step auto-resets."""
+tests/test_oracle_debug_views.py, and to {mortar_mayhem,mystery_path}_0_gt.gif for the finite ids' views, tests/test_oracle_old_gt_gifs.py),
+for all ten env ids, after the reset, after every step and across same-step auto-resets: n = 24, drawn steps, one option set, the default
+format.  Every other arrangement that writes the state only the view reads -- headless steps, mg_advance, the three path generators, two
+option sets, a checkpoint, kept terminal frames, several renders per step, masked resets, n up to 1,094 (the stretch kernel's stride
+loop) -- is tests/test_gpu_debug_arrangements.py's."""
 import numpy as np
 import pytest
 

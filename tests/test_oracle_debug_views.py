@@ -55,6 +55,29 @@ def test_debug_view_equals_the_recording(name, options):
     assert checked > 190 and not bad, "%d of %d debug frames differ from the recording, first %s" % (len(bad), checked, bad[:8])
 
 
+@pytest.mark.parametrize("env_id", ["SearingSpotlights-v0", "Endless-SearingSpotlights-v0"])
+def test_stale_pair_survives_two_resets_in_a_row(env_id):
+    """The view's (sprite, rect) pair is re-pointed by step() only, and every reset() makes a new agent object (searing_spotlights.py:
+    362 / 462): after an auto-reset AND a second reset with no step between them the view still shows the
+    agent where the last step left it -- not where the agent of the episode in between stood, which never stepped."""
+    env = oracle_lib.OracleEnv(env_id, 0.25)
+    env.reset(5)
+    for _ in range(6):
+        env.step([2, 1])
+    pair = (env.get("disp_sprite"), env.get("disp_x"), env.get("disp_y"))
+    assert pair == (env.get("arot") // 45, env.get("ax"), env.get("ay"))
+    moved = 0
+    for _ in range(2):
+        env.reset(None)
+        assert (env.get("disp_sprite"), env.get("disp_x"), env.get("disp_y")) == pair
+        moved += (env.get("ax"), env.get("ay")) != pair[1:]
+    assert moved  # (the new agents stand elsewhere)
+    body = (debug_view(env) == np.array((250, 204, 153), np.uint8)).all(-1)
+    ys, xs = np.nonzero(body)
+    assert abs((xs.min() + xs.max() + 1) / 8 - pair[1]) <= 1 and abs((ys.min() + ys.max() + 1) / 8 - pair[2]) <= 1  # the body's disc is centred on the stale rect
+    env.close()
+
+
 def test_debug_view_is_the_debug_surface_stretched_to_336():
     """SCALE 0.25: every pixel of the 84x84 debug surface becomes a 4x4 block (pygame.transform.scale = transform.c stretch())."""
     env = oracle_lib.OracleEnv("MysteryPath-v0", 0.25)
