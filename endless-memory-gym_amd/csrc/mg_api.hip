@@ -423,8 +423,7 @@ int mg_advance(mg_env* env, int32_t steps, double eps, uint64_t seed, uint64_t s
         const int n = env->num_envs;
         mg_env::Advance& A = env->adv;
         if (!A.ready) {  // the handle's first call: the only one that allocates (and therefore not capturable)
-            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-            if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+            if (mg::stream_capturing(st))
                 throw std::runtime_error("mg_advance: the handle's first call allocates its scratch and cannot be captured; call it once eagerly");
             A.actions.alloc((size_t)n * 2);
             A.reward.alloc(n);

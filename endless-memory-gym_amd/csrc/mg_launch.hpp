@@ -38,6 +38,12 @@ inline void with_obs_format(int fmt, F&& f) {
     else f(std::integral_constant<int, MG_OBS_U8_XYC>{});
 }
 
+// Is work put on this stream being recorded into a graph (hipStreamBeginCapture) instead of being run?
+inline bool stream_capturing(hipStream_t s) {
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    return hipStreamIsCapturing(s, &st) == hipSuccess && st != hipStreamCaptureStatusNone;
+}
+
 // A launch, and a launch whose error is looked at right away.  Which launches are checked is history, not design (the checked
 // ones are those that were followed by a hipGetLastError() when this header was written); the rule lives in check_launch().
 #ifdef __HIPCC__

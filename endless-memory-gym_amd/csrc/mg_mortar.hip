@@ -367,14 +367,10 @@ class MortarFamily : public Family {
     uint32_t epoch_ = 0;  // the one-launch step's hand-over epoch, 1 .. 255 (every one-launch step rewrites every word, so the only stale
                           // values a frame workgroup can meet are the previous one-launch step's and the 0 of the fresh array)
     // step() goes out as mortar_step_raster_kernel (instantiated for every observation format: profiles/chw_final.md has each one against the two launches)
-    bool one_launch(hipStream_t s) { return fuse_step() && !sets_.per_set() && !capturing(s); }
+    bool one_launch(hipStream_t s) { return fuse_step() && !sets_.per_set() && !stream_capturing(s); }
     static bool fuse_step() {  // lab build: MEMGYM_MORTAR_FUSE=0 selects the two-launch form for A/B measurements
         static const bool on = lab_flag("MEMGYM_MORTAR_FUSE", true);
         return on;
-    }
-    static bool capturing(hipStream_t s) {
-        hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-        return hipStreamIsCapturing(s, &st) == hipSuccess && st != hipStreamCaptureStatusNone;
     }
     MortarIO io() {
         MortarIO o;

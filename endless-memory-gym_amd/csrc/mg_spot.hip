@@ -537,8 +537,7 @@ class SpotFamily : public Family {
     // they took everywhere before the fused launch learnt them; the uint8 frame's fused launch is captured as it always was)
     bool fused_here(hipStream_t s) const {
         if (obs_format == MG_OBS_U8_XYC) return true;
-        hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-        return !(hipStreamIsCapturing(s, &st) == hipSuccess && st != hipStreamCaptureStatusNone);
+        return !stream_capturing(s);
     }
 
     // Resets served inside the raster launch: on for the finite variant up to FUSE_MAX instances (more instances finish per step
