@@ -24,6 +24,7 @@ struct mg_env {
     int variant = 0, family = 0;  // what make_* was called with
     bool started = false;         // a reset has happened
     int64_t final_obs_generic_steps = 0;  // mg_debug_counter: mg_step calls that kept terminal observations on the generic path (see mg_step)
+    int64_t masked_steps = 0;          // mg_debug_counter: mg_step_masked calls with active_dev != NULL
     int64_t headless_steps = 0;        // mg_debug_counter: mg_step calls with obs_dev == NULL, and the steps of mg_advance's loop form
     int64_t advance_fused_steps = 0;   // mg_debug_counter: steps mg_advance took inside a family's own launches (Family::advance)
     // mg_advance: what the loop of its definition passes from launch to launch, allocated at the handle's first call (include/memgym.h)
@@ -344,37 +345,56 @@ int mg_render_debug(mg_env* env, uint8_t* rgb_dev, void* stream) {
     });
 }
 
+}  // extern "C"
+namespace {
+// mg_step and mg_step_masked (`who` names the entry point in messages).  active == NULL: every instance steps, in the family's own arrangement.
+// active != NULL: the same three branches with the mask handed through to Family::step -- a masked step never takes a family's fused forms, so
+// kept terminal observations always go the generic way: inactive instances report done == 0 there, and the copy and the masked reset need nothing new.
+void step_call(mg_env* env, const char* who, const int32_t* actions_dev, const uint8_t* active_dev, void* obs_dev, float* reward_dev, uint8_t* done_dev,
+               float* gt_dev, const mg_info_buffers* info, int autoreset, hipStream_t st) {
+    if (!actions_dev || !reward_dev || !done_dev) throw std::runtime_error(std::string(who) + ": NULL buffer");
+    const mg_info_buffers ib = read_info(info);
+    mg::Family* f = env->fam;
+    if (!obs_dev) {  // a headless step: the family's plain arrangement without its raster launch
+        if (ib.final_obs_dev) throw std::runtime_error(std::string(who) + ": obs_dev is NULL (a headless step) together with final_obs_dev: terminal observations are frames");
+        f->step(actions_dev, active_dev, nullptr, reward_dev, done_dev, gt_dev, &ib, autoreset, st);
+        ++env->headless_steps;
+        if (active_dev) ++env->masked_steps;
+        if (ib.gt64_dev) f->ground_truth64(ib.gt64_dev, st, active_dev);
+        return;
+    }
+    if (autoreset && ib.final_obs_dev && (active_dev || !(mg::sparse_masked_raster() && f->keeps_final_obs(st)))) {
+        // terminal frames wanted: step without auto-reset (obs rows of finished instances = terminal frames), keep
+        // a copy of exactly those rows, then reset the finished instances with seed=None -- the same RNG
+        // consumption and frames as the fused path (tests/test_gpu_vector_api.py)
+        ++env->final_obs_generic_steps;
+        f->step(actions_dev, active_dev, obs_dev, reward_dev, done_dev, gt_dev, &ib, 0, st);
+        if (mg::sparse_masked_raster()) {  // the rows are there: copied, not drawn again (round 6)
+            const int n = env->num_envs, vec_per_row = (int)(mg_obs_bytes(env) / 16);
+            hipLaunchKernelGGL(copy_rows_kernel, dim3(std::min((n + COPY_CHUNK - 1) / COPY_CHUNK, 16384)), dim3(256), 0, st, done_dev, (const row_vec16*)obs_dev,
+                               (row_vec16*)ib.final_obs_dev, n, vec_per_row);
+            MG_HIP(hipGetLastError());
+        } else f->raster_only(ib.final_obs_dev, done_dev, st);
+        f->reset(nullptr, done_dev, obs_dev, gt_dev, st);
+    } else {
+        f->step(actions_dev, active_dev, obs_dev, reward_dev, done_dev, gt_dev, &ib, autoreset, st);
+    }
+    if (active_dev) ++env->masked_steps;
+    if (ib.gt64_dev) f->ground_truth64(ib.gt64_dev, st, active_dev);
+}
+}  // namespace
+extern "C" {
+
 int mg_step(mg_env* env, const int32_t* actions_dev, void* obs_dev, float* reward_dev, uint8_t* done_dev, float* gt_dev,
             const mg_info_buffers* info, int autoreset, void* stream) {
+    return guarded(env, [&] { step_call(env, "mg_step", actions_dev, nullptr, obs_dev, reward_dev, done_dev, gt_dev, info, autoreset, (hipStream_t)stream); });
+}
+
+int mg_step_masked(mg_env* env, const int32_t* actions_dev, const uint8_t* active_dev, void* obs_dev, float* reward_dev, uint8_t* done_dev, float* gt_dev,
+                   const mg_info_buffers* info, int autoreset, void* stream) {
     return guarded(env, [&] {
-        if (!actions_dev || !reward_dev || !done_dev) throw std::runtime_error("mg_step: NULL buffer");
-        hipStream_t st = (hipStream_t)stream;
-        const mg_info_buffers ib = read_info(info);
-        mg::Family* f = env->fam;
-        if (!obs_dev) {  // a headless step: the family's plain arrangement without its raster launch
-            if (ib.final_obs_dev) throw std::runtime_error("mg_step: obs_dev is NULL (a headless step) together with final_obs_dev: terminal observations are frames");
-            f->step(actions_dev, nullptr, reward_dev, done_dev, gt_dev, &ib, autoreset, st);
-            ++env->headless_steps;
-            if (ib.gt64_dev) f->ground_truth64(ib.gt64_dev, st);
-            return;
-        }
-        if (autoreset && ib.final_obs_dev && !(mg::sparse_masked_raster() && f->keeps_final_obs(st))) {
-            // terminal frames wanted: step without auto-reset (obs rows of finished instances = terminal frames), keep
-            // a copy of exactly those rows, then reset the finished instances with seed=None -- the same RNG
-            // consumption and frames as the fused path (tests/test_gpu_vector_api.py)
-            ++env->final_obs_generic_steps;
-            f->step(actions_dev, obs_dev, reward_dev, done_dev, gt_dev, &ib, 0, st);
-            if (mg::sparse_masked_raster()) {  // the rows are there: copied, not drawn again (round 6)
-                const int n = env->num_envs, vec_per_row = (int)(mg_obs_bytes(env) / 16);
-                hipLaunchKernelGGL(copy_rows_kernel, dim3(std::min((n + COPY_CHUNK - 1) / COPY_CHUNK, 16384)), dim3(256), 0, st, done_dev, (const row_vec16*)obs_dev,
-                                   (row_vec16*)ib.final_obs_dev, n, vec_per_row);
-                MG_HIP(hipGetLastError());
-            } else f->raster_only(ib.final_obs_dev, done_dev, st);
-            f->reset(nullptr, done_dev, obs_dev, gt_dev, st);
-        } else {
-            f->step(actions_dev, obs_dev, reward_dev, done_dev, gt_dev, &ib, autoreset, st);
-        }
-        if (ib.gt64_dev) f->ground_truth64(ib.gt64_dev, st);
+        if (!env->started) throw std::runtime_error("mg_step_masked: before the first mg_reset / mg_set_state");
+        step_call(env, "mg_step_masked", actions_dev, active_dev, obs_dev, reward_dev, done_dev, gt_dev, info, autoreset, (hipStream_t)stream);
     });
 }
 
@@ -449,7 +469,7 @@ int mg_advance(mg_env* env, int32_t steps, double eps, uint64_t seed, uint64_t s
         }
         for (int t = 0; t < steps; ++t) {  // the loop of the definition
             f->expert_actions(mg::ExpertArgs{eps, mg::expert_base(seed, step0 + (uint64_t)t), A.actions.p}, st);
-            f->step(A.actions.p, nullptr, A.reward.p, A.done.p, gt, &A.ib, 1, st);
+            f->step(A.actions.p, nullptr, nullptr, A.reward.p, A.done.p, gt, &A.ib, 1, st);
             if (out) {
                 hipLaunchKernelGGL(advance_accumulate_kernel, dim3((n + 255) / 256), dim3(256), 0, st, n, t == 0 ? 1 : 0, A.ib, (const uint8_t*)A.done.p, o);
                 MG_HIP(hipGetLastError());
@@ -565,7 +585,7 @@ int mg_single_step(mg_env* env, int32_t a0, int32_t a1, void* stream) {
         ib.reward64_dev = (double*)(S.dev + S.o_reward);
         mg::Family* f = env->fam;
         f->want_done_flag((uint32_t*)(S.dev + S.o_flag), S.ticket + 1);
-        f->step((const int32_t*)(S.dev + S.o_action), S.dev + S.o_obs, (float*)(S.dev + S.o_reward32), (uint8_t*)(S.dev + S.o_done),
+        f->step((const int32_t*)(S.dev + S.o_action), nullptr, S.dev + S.o_obs, (float*)(S.dev + S.o_reward32), (uint8_t*)(S.dev + S.o_done),
                 f->gt_dim() ? (float*)(S.dev + S.o_gt32) : nullptr, &ib, 0, st);
         const bool stored = f->done_flag_stored();  // the step's own last kernel stores the ticket: nothing may follow it (gt_dim() is 0 then)
         if (stored) ++S.ticket;
@@ -700,6 +720,10 @@ int mg_debug_counter(mg_env* env, const char* name, int64_t* value) {
         }
         if (std::string(name) == "headless_steps" || std::string(name) == "advance_fused_steps") {  // every id: counted in this file
             *value = std::string(name) == "headless_steps" ? env->headless_steps : env->advance_fused_steps;
+            return;
+        }
+        if (std::string(name) == "masked_steps") {  // every id: counted in this file
+            *value = env->masked_steps;
             return;
         }
         if (!env->fam->debug_counter(name, value)) throw std::runtime_error(std::string("mg_debug_counter: no counter named ") + name + " for " + env->id);

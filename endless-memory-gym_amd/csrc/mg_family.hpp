@@ -63,6 +63,14 @@ __device__ __forceinline__ void queue_leave(int* left, int participants, int* co
     *count = 0; *head = 0; *left = 0;  // (in this order)
     if (bg_count) *bg_count = 0;
 }
+// mg_step_masked, an instance whose active flag is 0, from its own lane of the MASKED form of a step kernel: the step's outputs that stay usable as
+// masks and sums without another look at the flags are zeroed -- plain stores -- and nothing else of the instance is read or written.
+__device__ __forceinline__ void masked_out(int i, float* reward_out, uint8_t* done_out, const mg_info_buffers& info) {
+    reward_out[i] = 0.0f;
+    done_out[i] = 0;
+    if (info.reward64_dev) info.reward64_dev[i] = 0.0;
+    if (info.capacity_dev) info.capacity_dev[i] = 0;
+}
 #endif
 
 // RAII device array
@@ -251,7 +259,9 @@ class Family {
     virtual void reset(const int64_t* seeds, const uint8_t* mask, void* obs, float* gt, hipStream_t s) = 0;
     // obs == NULL: a HEADLESS step (include/memgym.h: mg_step) -- the family's plain arrangement without its raster launch; everything but the
     // frames, the descriptors included, is what a drawn step of the same handle leaves (info->final_obs_dev is NULL then: mg_step refuses the pair)
-    virtual void step(const int32_t* actions, void* obs, float* reward, uint8_t* done, float* gt,
+    // active != NULL: a MASKED step (include/memgym.h: mg_step_masked) -- the arrangement of a headless step with the MASKED form of its step kernel, which
+    // leaves the instances with active[i] == 0 alone but for their zeroed reward / done, then, with obs, masked_frames(): the active instances' frames
+    virtual void step(const int32_t* actions, const uint8_t* active, void* obs, float* reward, uint8_t* done, float* gt,
                       const mg_info_buffers* info, int autoreset, hipStream_t s) = 0;
     // mg_advance: true = the family has run the loop of include/memgym.h's definition inside launches of its own (the mortar family:
     // mortar_advance_kernel); false = it has no such form (or the lab build switched it off) and nothing happened: mg_api.hip runs the loop.
@@ -279,7 +289,8 @@ class Family {
     // info["ground_truth"] as the reference returns it -- float64 (e.g. endless_mortar_mayhem.py:259,358) -- of every instance,
     // [num_envs][gt_dim], computed from the CURRENT state (the float32 gt_dev of mg_step / mg_reset is its rounding); a small
     // launch of its own, only when a caller asks (mg_info_buffers.gt64_dev, mg_ground_truth64).  No-op for gt_dim() == 0.
-    virtual void ground_truth64(double* /*gt64_dev*/, hipStream_t /*s*/) {}
+    // only != NULL (mg_step_masked): the rows of the instances with only[i] != 0, the others are not written
+    virtual void ground_truth64(double* /*gt64_dev*/, hipStream_t /*s*/, const uint8_t* /*only*/ = nullptr) {}
     // mg_expert_actions: the oracle's expert action of every instance from the CURRENT state (or the random one its draw gives it, ExpertArgs /
     // mg_expert.hpp), into x.actions in the layout step() reads.  One small launch; changes no state, draws from no instance's stream.
     virtual void expert_actions(const ExpertArgs& x, hipStream_t s) = 0;
@@ -314,6 +325,15 @@ class Family {
             sparse(mask);
             check_launch();
         } else dense();
+    }
+    // tail of a masked step(): the frames of the active instances, rows of the others untouched.  Always the family's dense raster launch with the mask as
+    // its filter, never launch_raster_sparse: the host does not know how many instances are active or where they lie, and the sparse launch, whose
+    // workgroups own 16 consecutive instances each, is made for FEW frames spread over the batch -- measured (profiles/masked_step.md) it wins up to 12 us
+    // at 1/8 and 1/64 of scattered instances and loses up to 100 us with half of them active, with all of them, or with the active ones in one block
+    void masked_frames(void* obs, const uint8_t* active, hipStream_t s) {
+        prof.begin(1, s);
+        raster_only(obs, active, s);
+        prof.end(1, s);
     }
     // raster_debug(): `fill(dbg)` writes the debug view's descriptors of all instances into scratch, `raster(dbg)` draws them
     template <typename Desc, typename Fill, typename Raster>

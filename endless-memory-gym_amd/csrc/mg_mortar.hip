@@ -59,6 +59,14 @@ __global__ __launch_bounds__(256) void mortar_gt64_kernel(int n, const MortarSta
     out[2 * i + 1] = s.ty / 5.0;
 }
 
+__global__ __launch_bounds__(256) void mortar_gt64_masked_kernel(int n, const MortarState* state, double* out, const uint8_t* __restrict__ only) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n || !only[i]) return;
+    const MortarState s = state[i];
+    out[2 * i] = s.tx / 5.0;
+    out[2 * i + 1] = s.ty / 5.0;
+}
+
 // Debug view: the frame descriptors of the current frames with (a) the glyph the reference's CLONE of the display schedule
 // yields -- its next entry, popped (dbg_pops, the only state a debug render changes), only while the real schedule still
 // holds entries (oracle/mgo_mortar.c mm_debug) -- and (b) the ring around the target tile.
@@ -241,7 +249,7 @@ class MortarFamily : public Family {
                      [&] { raster(obs, s); });
     }
 
-    void step(const int32_t* actions, void* obs, float* reward, uint8_t* done, float* gt, const mg_info_buffers* info,
+    void step(const int32_t* actions, const uint8_t* active, void* obs, float* reward, uint8_t* done, float* gt, const mg_info_buffers* info,
               int autoreset, hipStream_t s) override {
         struct Consume {  // want_done_flag() holds for this call only, whichever way it ends
             uint32_t*& flag;
@@ -252,8 +260,8 @@ class MortarFamily : public Family {
         sets_.upload(s);
         const MortarStepArgs sa{P_, n_, io(), actions, reward, done, gt_dim() ? gt : nullptr, ib, autoreset, handover_.p, nullptr};
         // one launch: mortar_step_raster_kernel (handles with ONE option set: the per-set step code reads its parameters from memory)
-        // (a headless step, obs == NULL: mortar_step_kernel alone)
-        if (obs && one_launch(s)) {
+        // (a headless step, obs == NULL: mortar_step_kernel alone; a masked step, active != NULL: its MASKED form, then the active instances' frames)
+        if (obs && !active && one_launch(s)) {
             epoch_ = epoch_ % 255u + 1u;  // 1 .. 255: never the 0 of a fresh hand-over array (resets and two-launch steps do not write the words)
             ++ticket_;                    // claim words hold the ticket of the last one-launch step: never this one
             const int logic_wgs = (n_ + 255) / 256;
@@ -287,9 +295,13 @@ class MortarFamily : public Family {
         }
         prof.begin(0, s);
         const int sb = step_block(256);
-        with_bool(sets_.per_set(), [&](auto PS) { launch(mortar_step_kernel<decltype(PS)::value>, dim3((n_ + sb - 1) / sb), dim3(sb), 0, s, sa); });
+        with_bool(sets_.per_set(), [&](auto PS) {
+            if (active) launch(mortar_step_masked_kernel<decltype(PS)::value>, dim3((n_ + sb - 1) / sb), dim3(sb), 0, s, sa, active);
+            else launch(mortar_step_kernel<decltype(PS)::value>, dim3((n_ + sb - 1) / sb), dim3(sb), 0, s, sa);
+        });
         end_logic(s);
         if (!obs) return;
+        if (active) return masked_frames(obs, active, s);
         prof.begin(1, s);
         raster(obs, s);
         prof.end(1, s);
@@ -324,8 +336,9 @@ class MortarFamily : public Family {
         sets_.upload(s);
         launch_checked(mortar_expert_kernel, expert_grid(n_), dim3(EXPERT_BLOCK), 0, s, P_, n_, io(), x);
     }
-    void ground_truth64(double* out, hipStream_t s) override {
+    void ground_truth64(double* out, hipStream_t s, const uint8_t* only = nullptr) override {
         if (!gt_dim() || !out) return;
+        if (only) return launch_checked(mortar_gt64_masked_kernel, dim3((n_ + 255) / 256), dim3(256), 0, s, n_, state_.p, out, only);
         launch_checked(mortar_gt64_kernel, dim3((n_ + 255) / 256), dim3(256), 0, s, n_, state_.p, out);
     }
     bool debug_counter(const std::string& name, int64_t* out) override {

@@ -419,4 +419,13 @@ __global__ __launch_bounds__(256) void mortar_step_kernel(MortarStepArgs a) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < a.n) mortar_step_body<false, false, PS>(i, a, 0u);
 }
+
+// The MASKED form (mg_step_masked): the lane of an instance with active[i] == 0 zeroes the instance's reward / done and leaves; the others step as above.
+template <bool PS>
+__global__ __launch_bounds__(256) void mortar_step_masked_kernel(MortarStepArgs a, const uint8_t* __restrict__ active) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.n) return;
+    if (active[i]) mortar_step_body<false, false, PS>(i, a, 0u);
+    else masked_out(i, a.reward_out, a.done_out, a.info);
+}
 }  // namespace mg

@@ -56,6 +56,15 @@ __global__ __launch_bounds__(256) void mystery_gt64_kernel(int n, const MysteryC
     out[3 * i + 2] = (double)s.td[2];
 }
 
+__global__ __launch_bounds__(256) void mystery_gt64_masked_kernel(int n, const MysteryCore* core, double* out, const uint8_t* __restrict__ only) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n || !only[i]) return;
+    const MysteryCore s = load_core(core + i);
+    out[3 * i + 0] = (double)s.td[0];
+    out[3 * i + 1] = (double)s.td[1];
+    out[3 * i + 2] = (double)s.td[2];
+}
+
 // Debug descriptors from the state and the current frame descriptors (see MysteryDebugComposer; oracle/mgo_mystery.c
 // mpf_debug / emp_debug).
 template <bool PS>
@@ -286,10 +295,12 @@ class MysteryFamily : public Family {
             else launch_raster_sparse<MysteryComposer>(desc_.p, atlas_->dev(), obs, obs_format, n_, s, m);
         }, [&] { raster(obs, s); });
     }
-    // tail of a step() in the plain arrangement: the logic is out, the frames are a launch of their own (a headless step has none)
-    void plain_frames(void* obs, hipStream_t s) {
+    // tail of a step() in the plain arrangement: the logic is out, the frames are a launch of their own (a headless step has none; a masked step, active != NULL:
+    // the active instances' alone)
+    void plain_frames(void* obs, hipStream_t s, const uint8_t* active = nullptr) {
         end_logic(s);
         if (!obs) return;
+        if (active) return masked_frames(obs, active, s);
         prof.begin(1, s);
         raster(obs, s);
         prof.end(1, s);
@@ -375,14 +386,20 @@ class MysteryFiniteFamily final : public MysteryFamily {
         draw_reset_frames(mask, obs, s);
     }
 
-    void step(const int32_t* actions, void* obs, float* reward, uint8_t* done, float* gt, const mg_info_buffers* info,
+    void step(const int32_t* actions, const uint8_t* active, void* obs, float* reward, uint8_t* done, float* gt, const mg_info_buffers* info,
               int autoreset, hipStream_t s) override {
         const mg_info_buffers ib = begin_step(info);
         prof.begin(0, s);
         // (per-instance option sets: only this kernel has a <PS> form -- the raster launch's path service reads nothing of the options)
         // (a headless step, obs == NULL: the paths are generated in the step kernel -- there is no raster launch to serve them)
-        const int defer = (obs && autoreset && !big_sprites_) ? defer_mode() : 0;
+        const int defer = (obs && !active && autoreset && !big_sprites_) ? defer_mode() : 0;
         sets_.upload(s);
+        if (active) {  // a masked step: the MASKED form of the step kernel with the paths generated in it, then the active instances' frames
+            with_bool(sets_.per_set(), [&](auto PS) {
+                launch(mystery_step_masked_kernel<decltype(PS)::value>, dim3(blocks()), dim3(256), WS_BYTES, s, P_, io(), actions, active, reward, done, ib, autoreset, lpw());
+            });
+            return plain_frames(obs, s, active);
+        }
         // (three of the four <PS, FINAL> forms exist: terminal observations are kept by handles with one option set only)
         auto step_launch = [&](auto kernel) { launch(kernel, dim3(blocks()), dim3(256), WS_BYTES, s, P_, io(), actions, reward, done, nullptr, ib, autoreset, lpw(), defer); };
         if (autoreset && ib.final_obs_dev && keeps_final_obs(s)) {  // terminal observations kept by these two launches (defer != 0, one option set)
@@ -528,7 +545,7 @@ class MysteryEndlessFamily final : public MysteryFamily {
         draw_reset_frames(mask, obs, s);
     }
 
-    void step(const int32_t* actions, void* obs, float* reward, uint8_t* done, float* gt, const mg_info_buffers* info,
+    void step(const int32_t* actions, const uint8_t* active, void* obs, float* reward, uint8_t* done, float* gt, const mg_info_buffers* info,
               int autoreset, hipStream_t s) override {
         const mg_info_buffers ib = begin_step(info);
         prof.begin(0, s);
@@ -536,13 +553,15 @@ class MysteryEndlessFamily final : public MysteryFamily {
         // first generates what earlier fused steps left owed
         // (per-instance option sets: the plain arrangement -- step kernel, queue server, raster -- whose kernels have a <PS> form)
         // (a headless step, obs == NULL: the plain arrangement as well, without its raster launch; the next drawn step is fused again)
-        const bool fused = obs && steps_fused();
+        // (a masked step, active != NULL: the plain arrangement with the MASKED form of the step kernel and the active instances' frames.  What earlier fused
+        // steps left owed is flushed first for EVERY instance, the inactive ones included: an owed segment is work put off, and generating it changes no result)
+        const bool fused = obs && !active && steps_fused();
         P_.lazy = (fused && lazy_wanted_) ? 1 : 0;
         P_.pre = (P_.lazy && pre_wanted_) ? 1 : 0;
         static const int lazy_append = lab_int("MEMGYM_EMP_LAZY_APPEND", 1);
         P_.lazy_append = (P_.lazy && lazy_append) ? 1 : 0;
         // (a headless step that is being captured flushes whether or not anything is owed NOW: drawn steps may run between the replays)
-        if (!P_.lazy && (owed_possible_ || (!obs && stream_capturing(s)))) flush_owed(s);
+        if (!P_.lazy && (owed_possible_ || ((!obs || active) && stream_capturing(s)))) flush_owed(s);
         if (P_.lazy) owed_possible_ = true;
         sets_.upload(s);
         const int sb = step_block(256);
@@ -551,12 +570,16 @@ class MysteryEndlessFamily final : public MysteryFamily {
         const bool keep_final = autoreset && ib.final_obs_dev && fused && keeps_final_obs(s);
         // (three of the four <PS, FINAL> forms exist: terminal observations are kept by handles with one option set only)
         auto step_launch = [&](auto kernel) { launch(kernel, dim3((n_ + sb - 1) / sb), dim3(sb), 0, s, P_, io(), actions, reward, done, gt, ib, autoreset); };
-        if (sets_.per_set()) step_launch(emp_step_kernel<true>);
+        if (active) {
+            with_bool(sets_.per_set(), [&](auto PS) {
+                launch(emp_step_masked_kernel<decltype(PS)::value>, dim3((n_ + sb - 1) / sb), dim3(sb), 0, s, P_, io(), actions, active, reward, done, gt, ib, autoreset);
+            });
+        } else if (sets_.per_set()) step_launch(emp_step_kernel<true>);
         else if (keep_final) step_launch(emp_step_kernel<false, true>);
         else step_launch(emp_step_kernel<false>);
         if (!fused) {
             serve(false, nullptr, reward, done, gt, ib, autoreset, s);
-            plain_frames(obs, s);
+            plain_frames(obs, s, active);
             return;
         }
         // the queue is served inside the raster launch
@@ -610,8 +633,9 @@ class MysteryEndlessFamily final : public MysteryFamily {
         return wanted && steps_fused();
     }
 
-    void ground_truth64(double* out, hipStream_t s) override {
+    void ground_truth64(double* out, hipStream_t s, const uint8_t* only = nullptr) override {
         if (!out) return;
+        if (only) return launch_checked(mystery_gt64_masked_kernel, dim3((n_ + 255) / 256), dim3(256), 0, s, n_, core_.p, out, only);
         launch_checked(mystery_gt64_kernel, dim3((n_ + 255) / 256), dim3(256), 0, s, n_, core_.p, out);
     }
     bool debug_counter(const std::string& name, int64_t* out) override {

@@ -64,6 +64,37 @@ __global__ __launch_bounds__(256) void emp_step_kernel(MysteryParams P0, Mystery
     LAB_STEP_CLOCK(4);
 }
 
+// The MASKED form (mg_step_masked): emp_step_kernel as a masked step launches it -- the plain arrangement, P.lazy == 0, no terminal observations kept.  The lane
+// of an instance with active[i] == 0 zeroes the instance's reward / done and leaves: it queues nothing, so emp_serve_kernel behind this launch serves the
+// active instances' entries alone.  io.bgflag / the background queue: a plain step neither reads nor writes them (nothing is owed: the host has flushed), so
+// they stay as they are for every instance, and the next fused step rewrites every instance's flag from its state.  (A kernel of its own, not a shared body:
+// with the body moved into a function the compiler schedules the existing forms differently, and those stay the code they were.)
+template <bool PS>
+__global__ __launch_bounds__(256) void emp_step_masked_kernel(MysteryParams P0, MysteryIO io, const int32_t* actions, const uint8_t* __restrict__ active,
+                                                              float* reward_out, uint8_t* done_out, float* gt, mg_info_buffers info, int autoreset) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= P0.n) return;
+    if (!active[i]) return masked_out(i, reward_out, done_out, info);
+    const MysteryParams& P = PS ? io.sets[set_index(io.set_of, i)] : P0;
+    const int act = actions[i];
+    MysteryCore s = load_core(&io.core[i]);
+    int nx = 0, ny = 0;
+    const int ra = emp_step_a(P, i, s, act, nx, ny, io.err);
+    if (ra & EMP_DUE) {  // the agent entered the last-but-one segment: the rest of its step needs the new one (emp_serve_kernel)
+        queue_push(io.queue, &io.qctr[QC_COUNT], P.n, i | EMP_Q_SEGMENT, io.err);
+        io.core[i] = s;
+        io.desc[i].valid = DESC_QUEUED;  // (the rest of the descriptor is last step's)
+        return;
+    }
+    MysteryDesc d;
+    if (emp_step_b<!PS, true, false>(P, io, i, s, nx, ny, reward_out, done_out, gt ? gt + 3 * i : nullptr, info, autoreset, d, (ra & EMP_CAP) != 0)) {
+        queue_push(io.queue, &io.qctr[QC_COUNT], P.n, i, io.err);
+        d.valid = DESC_QUEUED;
+    }
+    io.core[i] = s;
+    io.desc[i] = d;
+}
+
 __global__ __launch_bounds__(256) void emp_enqueue_kernel(int n, MysteryIO io, const uint8_t* mask) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;

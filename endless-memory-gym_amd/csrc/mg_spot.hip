@@ -55,6 +55,14 @@ __global__ __launch_bounds__(256) void spot_gt64_kernel(SpotParams P0, SpotIO io
     write_gt(out + 4 * i, P, s.ax, s.ay, s);
 }
 
+__global__ __launch_bounds__(256) void spot_gt64_masked_kernel(SpotParams P0, SpotIO io, double* out, const uint8_t* __restrict__ only) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= P0.n || !only[i]) return;
+    const SpotParams& P = io.set_of ? io.sets[set_index(io.set_of, i)] : P0;
+    const SpotCore s = io.core[i];
+    write_gt(out + 4 * i, P, s.ax, s.ay, s);
+}
+
 __global__ __launch_bounds__(256) void spot_init_kernel(int n, SpotCore* core) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -284,7 +292,7 @@ class SpotFamily : public Family {
         }, [&] { raster(obs, s); });
     }
 
-    void step(const int32_t* actions, void* obs, float* reward, uint8_t* done, float* gt, const mg_info_buffers* info,
+    void step(const int32_t* actions, const uint8_t* active, void* obs, float* reward, uint8_t* done, float* gt, const mg_info_buffers* info,
               int autoreset, hipStream_t s) override {
         const mg_info_buffers ib = begin_step(info);
         sets_.upload(s);
@@ -293,15 +301,23 @@ class SpotFamily : public Family {
         // (a call that keeps terminal observations: always deferred -- the service workgroup draws the terminal frame from the descriptor this
         // launch leaves, then resets: keeps_final_obs)
         const bool keep_final = autoreset && ib.final_obs_dev && keeps_final_obs(s);
-        // (a headless step, obs == NULL: never deferred -- there is no raster launch to serve the resets)
-        const int defer = (obs && autoreset && (fuse_resets() || keep_final) && !sets_.per_set() && fused_here(s)) ? 1 : 0;
+        // (a headless step, obs == NULL: never deferred -- there is no raster launch to serve the resets; nor is a masked step, active != NULL: the
+        // MASKED form of the step kernel, then the active instances' frames)
+        const int defer = (obs && !active && autoreset && (fuse_resets() || keep_final) && !sets_.per_set() && fused_here(s)) ? 1 : 0;
         const int sb = step_block(256);
         const SpotStepArgs sa{P_, io(), actions, reward, done, gt, ib, autoreset, defer};
         const dim3 sg((n_ * SLOTS + sb - 1) / sb);
         with_bool(P_.endless, [&](auto EN) {
-            with_bool(sets_.per_set(), [&](auto PS) { launch(spot_step_kernel<decltype(EN)::value, decltype(PS)::value>, sg, dim3(sb), 0, s, sa); });
+            with_bool(sets_.per_set(), [&](auto PS) {
+                if (active) launch(spot_step_masked_kernel<decltype(EN)::value, decltype(PS)::value>, sg, dim3(sb), 0, s, sa, active);
+                else launch(spot_step_kernel<decltype(EN)::value, decltype(PS)::value>, sg, dim3(sb), 0, s, sa);
+            });
         });
         end_logic(s);
+        if (active) {
+            if (obs) masked_frames(obs, active, s);
+            return;
+        }
         prof.begin(1, s);
         if (defer) {
             const int grid = frames_grid(n_) + SPOT_SVC_WGS;
@@ -354,9 +370,10 @@ class SpotFamily : public Family {
         sets_.upload(s);
         launch_checked(spot_expert_kernel, expert_grid(n_), dim3(EXPERT_BLOCK), 0, s, P_, io(), x);
     }
-    void ground_truth64(double* out, hipStream_t s) override {
+    void ground_truth64(double* out, hipStream_t s, const uint8_t* only = nullptr) override {
         if (!gt_dim() || !out) return;
         sets_.upload(s);
+        if (only) return launch_checked(spot_gt64_masked_kernel, dim3((n_ + 255) / 256), dim3(256), 0, s, P_, io(), out, only);
         launch_checked(spot_gt64_kernel, dim3((n_ + 255) / 256), dim3(256), 0, s, P_, io(), out);
     }
 

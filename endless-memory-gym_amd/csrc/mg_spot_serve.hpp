@@ -44,6 +44,20 @@ __global__ __launch_bounds__(256) void spot_step_kernel(SpotStepArgs a) {
     if (i < a.P.n) spot_step_body<EN, PS>(i, lane_ctx((int)threadIdx.x), a, disc_lds, core_lds, Trig{a.P.cos_tab, a.P.sin_tab});
 }
 
+// The MASKED form (mg_step_masked): the sixteen lanes of an instance with active[i] == 0 skip the step together -- its first lane zeroes the instance's reward / done.
+// Nothing in spot_step_body reaches beyond the instance's own 16-lane group: its shuffles are 16 wide, its ballots are read through the group's own 16 bits
+// (LaneCtx::gshift), the disc and core slots in LDS are the group's (LaneCtx::grp), and it has no barrier -- the lanes beyond n of the last group leave the same way.
+template <bool EN, bool PS>
+__global__ __launch_bounds__(256) void spot_step_masked_kernel(SpotStepArgs a, const uint8_t* __restrict__ active) {
+    __shared__ int disc_lds[(256 / 16) * DISC_INTS];
+    __shared__ SpotCore core_lds[256 / 16];
+    const int gid = blockIdx.x * blockDim.x + threadIdx.x;
+    const int i = gid >> 4;
+    if (i >= a.P.n) return;
+    if (active[i]) spot_step_body<EN, PS>(i, lane_ctx((int)threadIdx.x), a, disc_lds, core_lds, Trig{a.P.cos_tab, a.P.sin_tab});
+    else if ((gid & 15) == 0) masked_out(i, a.reward_out, a.done_out, a.info);
+}
+
 // The step's raster launch with the put-off resets served inside it: the first workgroups take the queue entries, eight
 // each (the 16 lanes of a quarter wave reset one instance, like spot_reset_kernel; waves 2 and 3 wait), then draw those
 // eight frames; all other workgroups walk the frames of the instances that were not queued (SpotDesc::valid == 1).  The

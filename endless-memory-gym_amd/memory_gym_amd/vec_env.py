@@ -409,13 +409,31 @@ class VecMemoryGym:
         info = {"ground_truth": self.gt if self.gt64 is None else self.gt64} if self.gt_dim else {}
         return self._obs(), info
 
-    def step(self, actions, render=True):
+    def step(self, actions, render=True, mask=None):
         """Env.step for every instance.  render=False is the HEADLESS step (include/memgym.h: mg_step with obs_dev == NULL): everything but
         the frames -- state, random streams, rewards, dones, infos -- is what the drawn step gives, the first element of the returned tuple
         is None and `obs` keeps its old bytes until redraw(), the next drawn step or a reset.  Terminal observations are frames: a handle
-        made with final_observation=True refuses render=False (ValueError) before anything is stepped."""
+        made with final_observation=True refuses render=False (ValueError) before anything is stepped.
+        mask: step a SUBSET (include/memgym.h: mg_step_masked) -- a bool or uint8 tensor [N] on the device, or anything torch.as_tensor
+        takes; instance i steps iff mask[i] != 0, and its results are those of a handle in which it alone had been stepped by step() with
+        the same actions in the same order.  The other instances are left alone: state, random stream and their row of `obs`, of the
+        ground truth and of final_observation stay; the action entries of inactive instances are not interpreted.  The return values keep
+        their shapes: `reward` is 0 and info["done_mask"] False for inactive instances, the OTHER info rows of inactive instances (the
+        episode record "reward" / "length", the named aux infos, "capacity_exceeded" aside, which is False) keep their previous contents.
+        A mask of the wrong length raises ValueError before anything is stepped; mask=None is the ordinary step.  render=False with a
+        mask is the masked headless step.  Evaluation of one episode per seed: `finished |= done` and step(a, mask=~finished) until all
+        are finished (examples/evaluate_seeds.py)."""
         if not render and self.final_obs is not None:
             raise ValueError("step(render=False) on a handle with final_observation=True: terminal observations are frames")
+        m = None
+        if mask is not None:
+            m = mask if isinstance(mask, torch.Tensor) else torch.as_tensor(mask)
+            if m.numel() != self.num_envs or m.dim() != 1:
+                raise ValueError("step(mask=...): the mask must have shape [%d], got %s" % (self.num_envs, tuple(m.shape)))
+            if m.dtype == torch.bool and m.device == self.device and m.is_contiguous():
+                m = m.view(torch.uint8)  # (the same bytes: True is 1)
+            elif not (m.dtype == torch.uint8 and m.device == self.device and m.is_contiguous()):
+                m = (m != 0).to(device=self.device, dtype=torch.uint8).contiguous()
         a = actions
         if not (isinstance(a, torch.Tensor) and a.dtype == torch.int32 and a.device == self.device and a.is_contiguous()):
             a = a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a))
@@ -423,11 +441,11 @@ class VecMemoryGym:
         assert a.numel() == self._n_actions, "actions must have shape [N] or [N, 2]"
         if torch.cuda.current_device() != self.device.index:
             with torch.cuda.device(self.device):
-                self._launch_step(a, render)
+                self._launch_step(a, render, m)
         else:
-            self._launch_step(a, render)
+            self._launch_step(a, render, m)
         if render:
-            self._swapped = self._stale = False  # a drawn step writes every row
+            self._swapped = self._stale = False  # a drawn step writes every row (a masked one: has drawn every row first where one was old)
         else:
             self._stale = True
         _native.LIB.mg_peek_errors(self._h, self._p_err)  # host-mapped word: no synchronisation
@@ -438,7 +456,17 @@ class VecMemoryGym:
             info["final_observation"] = self.final_obs
         return (self._obs() if render else None), self.reward, self._done_bool, self._truncated, info
 
-    def _launch_step(self, a, render=True):
+    def _launch_step(self, a, render=True, m=None):
+        if m is not None:
+            if render and (self._swapped or self._stale):
+                # a drawn masked step writes the rows of the active instances only: after use_obs_buffer() or headless steps the other rows
+                # hold old bytes -- draw every instance's CURRENT frame first, as the masked reset() does (one raster launch, these sequences only)
+                _native.check(_native.LIB.mg_render(self._h, self.obs.data_ptr(), self._raw_stream()), "mg_render")
+            rc = _native.LIB.mg_step_masked(self._h, a.data_ptr(), m.data_ptr(), self.obs.data_ptr() if render else None, self._p_reward, self._p_done,
+                                            self._p_gt, self._p_info, 1 if self.autoreset else 0, self._raw_stream())
+            if rc != 0:
+                _native.check(rc, "mg_step_masked")
+            return
         rc = _native.LIB.mg_step(self._h, a.data_ptr(), self.obs.data_ptr() if render else None, self._p_reward, self._p_done, self._p_gt, self._p_info,
                                  1 if self.autoreset else 0, self._raw_stream())
         if rc != 0:

@@ -213,6 +213,32 @@ int mg_render_debug(mg_env* env, uint8_t* rgb_dev, void* stream);
 int mg_step(mg_env* env, const int32_t* actions_dev, void* obs_dev, float* reward_dev, uint8_t* done_dev,
             float* gt_dev, const mg_info_buffers* info, int autoreset, void* stream);
 
+/* Env.step(action) (e.g. mortar_mayhem_grid.py:280-375) of the SELECTED instances: those with active_dev[i] != 0 step, the others are left alone.
+ * active_dev: uint8 [num_envs], read on `stream` by the step's launches; the host never looks at it (no synchronisation, no allocation).
+ * active_dev == NULL is mg_step with the remaining arguments -- same launches, same fused arrangements -- and counts as an ordinary step.
+ * DEFINITION: take the subsequence of calls in which instance i was active; its results are exactly what a handle stepped with plain mg_step
+ * gives instance i for the same actions in the same order.
+ *   active_dev[i] != 0  everything mg_step would do to the instance, bit for bit: state, PCG64 stream, frame descriptor, reward_dev[i], done_dev[i],
+ *                       its gt_dev row, every mg_info_buffers row, obs_dev row i, final_obs_dev row i, same-call auto-reset, capacity ends, error bits.
+ *   active_dev[i] == 0  nothing of the instance changes: state, stream and descriptor stay; row i of obs_dev, gt_dev, final_obs_dev, ep_reward_dev,
+ *                       ep_length_dev, aux_dev[k], gt64_dev and the bound vector observation is NOT written.  Written are reward_dev[i] = 0 and done_dev[i] = 0, and where given reward64_dev[i] = 0 and capacity_dev[i] = 0, so
+ *                       that the step's outputs serve as masks and sums without another look at active_dev.  Its action entry is not interpreted.
+ * A mask of all zeros is legal.  Uses: one episode per seed (active = not yet finished, autoreset 0 or 1 -- the evaluation protocol of the Memory Gym
+ * paper without stepping an instance past its end), instances stepped at different rates (action repeat, asynchronous samplers), pausing part of a batch.
+ * Launches: the arrangement of a HEADLESS step with the MASKED form of its step kernel (mortar_step_masked_kernel; spot_step_masked_kernel, never deferred;
+ * mystery_step_masked_kernel with the paths generated in it; Endless-MysteryPath-v0: whatever earlier fused steps left owed is generated first -- for every
+ * instance, which changes no result -- then emp_step_masked_kernel and the queue server, which serves the active instances' entries alone; the next
+ * unmasked drawn step is fused again), then, with obs_dev, ONE raster launch restricted to the active instances.  A linear chain, capturable into a HIP
+ * graph: the mask is read from memory at replay.  obs_dev == NULL is a masked headless step (refused together with final_obs_dev, like mg_step).
+ * With final_obs_dev and autoreset the generic path of mg_step is taken -- masked step without auto-reset, the finished rows copied, masked reset by
+ * done_dev.  mg_render afterwards behaves as after mg_step: inactive instances keep the descriptor they had.  Per-instance option sets, every observation
+ * format, mg_set_capacity, checkpoints between masked steps (MG_STATE_VERSION is unchanged: no state is added), mg_expert_actions / mg_advance before and
+ * after work as documented.  An all-ones mask costs the plain arrangement, not the fused one (profiles/masked_step.md).
+ * mg_debug_counter "masked_steps" counts the calls with active_dev != NULL (a masked headless step is counted there and in "headless_steps").
+ * Errors (-1): a NULL actions_dev, reward_dev or done_dev; before the first mg_reset / mg_set_state; a geometry option set since the last reset. */
+int mg_step_masked(mg_env* env, const int32_t* actions_dev, const uint8_t* active_dev, void* obs_dev, float* reward_dev,
+                   uint8_t* done_dev, float* gt_dev, const mg_info_buffers* info, int autoreset, void* stream);
+
 /* The float64 ground truth of every instance from the CURRENT state (what the last mg_reset / mg_step left), [num_envs][mg_gt_dim]
  * on the device: the doubles the reference puts into info["ground_truth"] after reset() as well as after step().  Enqueued on
  * `stream`; a no-op for env ids without ground truth. */
