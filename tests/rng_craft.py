@@ -10,7 +10,8 @@ craft() returns the stream in the six words of rng_words() / mg_debug_rng: {stat
 
 The second half is the INJECTION PLAN that tests/test_rng_craft.py (the oracle alone, no GPU) and tests/test_gpu_rng_edges.py (HIP against
 the oracle) share: which instance receives which stream, per env id the options and the sweep of positions, and the coverage conditions
-read from the oracle's bookkeeping (oracle/mgo_rng.h mgo_rng_book)."""
+read from the oracle's bookkeeping (oracle/mgo_rng.h mgo_rng_book).  The third part, "the arrangement axis", is the table, the driver and the
+conditions that tests/test_gpu_rng_edges_arrangements.py shares with tests/test_rng_craft.py in the same way."""
 import numpy as np
 
 M64 = (1 << 64) - 1
@@ -339,3 +340,339 @@ def check_spot_wirings(label, cov):
 
 def random_actions(prng, n, discrete):
     return (prng.integers(0, 4, n) if discrete else prng.integers(0, 3, (n, 2))).astype(np.int32)
+
+
+# ---- the arrangement axis ---------------------------------------------------------------------------------------------------------------
+# The cases above reach every draw through the launches a default handle takes.  The same draws sit in other kernels too -- the headless
+# step, the masked step and the masked resets, the per-set <PS> instantiations, mg_advance, the finite ids' lane generator -- and
+# ARRANGEMENT_CASES sends the crafted streams through each of them (tests/test_gpu_rng_edges_arrangements.py; the oracle alone:
+# tests/test_rng_craft.py).  One driver, run_arrangement(), plays a case on whatever `make` returns: OracleSide below (no GPU), or the GPU
+# test's pair of a handle and an OracleSide, whose methods make the device call, let the OracleSide do the oracle's and compare.  Both
+# therefore see the same injection, actions and masks.
+
+# The second option set of the two-set case: list lengths 5 and 6 (thresholds 2^32 mod 5 = 1, mod 6 = 4) where the first set has 3
+# (threshold 1), a radius range of span 5 (7 .. 11) where the first has 7 (7 .. 13: threshold 4).  No geometry key differs, so a handle
+# accepts both sets side by side.  Endless-MysteryPath-v0 has no option that sets a span: its sets differ in max_steps and a reward.
+_MM_SECOND = {"command_count": [8, 9, 10, 11, 12], "command_show_duration": [1] * 5, "command_show_delay": [0] * 5, "explosion_delay": [2] * 6,
+              "explosion_duration": [1] * 6}
+TWO_SETS = {
+    "MortarMayhem-v0": (_MM_SHORT, _MM_SECOND),
+    "MysteryPath-v0": (dict(SHORT_OPTIONS["MysteryPath-v0"], **RESET_OPTIONS["MysteryPath-v0"]), {"max_steps": 7, "cardinal_origin_choice": [0, 1, 2, 3, 1]}),
+    "Endless-MysteryPath-v0": ({"max_steps": 8}, {"max_steps": 9, "reward_fall_off": -0.2}),
+    "SearingSpotlights-v0": (dict(SHORT_OPTIONS["SearingSpotlights-v0"], **RESET_OPTIONS["SearingSpotlights-v0"]),
+                             dict(SHORT_OPTIONS["SearingSpotlights-v0"], spot_min_radius=7.0, spot_max_radius=11.0, num_coins=[1, 2, 3, 4, 5])),
+    "Endless-SearingSpotlights-v0": (dict(SHORT_OPTIONS["Endless-SearingSpotlights-v0"], **RESET_OPTIONS["Endless-SearingSpotlights-v0"]),
+                                     dict(SHORT_OPTIONS["Endless-SearingSpotlights-v0"], spot_min_radius=7.0, spot_max_radius=11.0)),
+}
+# spans only ONE of the two sets draws (the condition "each set rejected under a span the other does not draw"); None: no such span exists.
+# (MortarMayhem-v0 draws a span of 6 under either set -- the second set's lists of six share it --, so 5 alone is its own.  MysteryPath-v0:
+# the number of outer-wall candidates takes the values 3 and 5 too, in either set, and the books know spans, not call sites; there the
+# choice is the reset's FIRST draw, and check_arrangement asks for a rejected word of output 0 in plan instance 0 (p 0, no buffered
+# half, pattern Z: a word of 0, which 3 and 5 both reject) instead of for a span the other set never drew.)
+TWO_SETS_OWN_SPANS = {"MortarMayhem-v0": ({3}, {5}), "MysteryPath-v0": ({3}, {5}), "Endless-MysteryPath-v0": None,
+                      "SearingSpotlights-v0": ({7, 3}, {5}), "Endless-SearingSpotlights-v0": ({7}, {5})}
+
+MORTAR = tuple(e for e in ALL_IDS if "Mortar" in e)
+ADVANCE_EPS, ADVANCE_SEED = 0.3, 4711
+LANE_N, LANE_INJECTED, LANE_WARMUP, LANE_EXPERT_STEPS = 1091, 8 * 60, 6, 4  # 17 waves + 3, more than PATH_MASS = 1,024 (mg_mystery_finite.hpp)
+EPISODE_WARMUP = {c[0]: c[3] for c in EPISODE_CASES}
+
+
+def _cases():
+    """(env id, arrangement, injected instances or None = the id's sweep, handle size or None = handle_size(), options, step cap).
+    The caps are MEASURED: the calls the oracle alone needs under the case's inputs (tests/test_rng_craft.py asserts that it stays within
+    them, the GPU test that the handle needs exactly as many); where the arrangement fixes the number of calls, that number."""
+    caps = {
+        "headless": [24, 19, 14, 15, 9, 7, 7, 8, 9, 9], "masked": [50, 54, 50, 28, 22, 27, 27, 29, 35, 32],
+        "masked-reset": [24, 19, 14, 15, 9, 7, 7, 8, 9, 9], "masked-blocks": [15, 15, 16, 25, 25],
+    }
+    rows = []
+    for k, e in enumerate(ALL_IDS):
+        rows.append((e, "headless", None, None, short_options(e), caps["headless"][k]))
+    for e, n_inj, _, _, options in EPISODE_CASES[:3]:
+        rows.append((e, "headless-episode", n_inj, None, options, EPISODE_STEPS))
+    rows.append(("Endless-MysteryPath-v0", "headless-episode", 320, 323, {}, EPISODE_STEPS))
+    for k, e in enumerate(ALL_IDS):
+        rows.append((e, "masked", None, None, short_options(e), caps["masked"][k]))
+    for k, e in enumerate(MYSTERY + SPOT):
+        rows.append((e, "masked-blocks", None, None, short_options(e), caps["masked-blocks"][k]))
+    for k, e in enumerate(ALL_IDS):
+        rows.append((e, "masked-reset", None, None, short_options(e), caps["masked-reset"][k]))
+    for e in ("MortarMayhem-Grid-v0", "SearingSpotlights-v0"):
+        rows.append((e, "masked-reset-final", None, None, short_options(e), caps["masked-reset"][ALL_IDS.index(e)]))
+    rows.append(("Endless-MysteryPath-v0", "masked-reset-sets", None, None, None, 9))
+    for e, cap in zip(TWO_SETS, (23, 7, 9, 9, 9)):
+        rows.append((e, "two-sets", None, None, None, cap))
+    for e, cap in zip(MORTAR + ("MysteryPath-Grid-v0", "SearingSpotlights-v0"), (35, 24, 14, 30, 12, 7, 9)):
+        rows.append((e, "advance", None, None, short_options(e), cap))
+    for e in ("MysteryPath-Grid-v0", "MysteryPath-v0"):
+        rows.append((e, "lane-generator", LANE_INJECTED, LANE_N, {"max_steps": 7}, 1))
+    return rows
+
+
+ARRANGEMENT_CASES = _cases()
+MEASURE_LIMIT = 200  # run_arrangement(cap=None): how long a measuring run may last
+MASK_ROWS = 200      # rows of the masked cases' mask and action tables, whatever the cap (bernoulli_inputs draws the actions behind the mask: another
+                     # number of rows is another table)
+
+
+def case_id(case):
+    return "%s-%s" % (case[1], case[0])
+
+
+def inject_at(ref, env, instances, plan_ids=None):
+    """The stream of plan(plan_ids[k]) into instance instances[k] of the oracle batch and -- env not None -- of the HIP handle, at whatever
+    point of a run; the oracle's books of these instances start over.  plan_ids None: 0, 1, 2, ..."""
+    instances = [int(i) for i in instances]
+    plan_ids = list(range(len(instances))) if plan_ids is None else [int(p) for p in plan_ids]
+    words = plan_words(max(plan_ids) + 1)
+    for i, p in zip(instances, plan_ids):
+        ref.envs[i].set_rng_words(words[p])
+        if env is not None:
+            env.set_rng_words(i, words[p])
+        ref.envs[i].rng_stats(clear=True)
+
+
+class _Some:
+    """the chosen instances of an oracle batch, where Coverage looks for `envs`"""
+
+    def __init__(self, ref, instances):
+        self.envs = [ref.envs[int(i)] for i in instances]
+
+
+def coverage_of(env_id, ref, instances):
+    """Coverage over the listed instances; entry k of its stats belongs to instances[k]"""
+    return Coverage(env_id, _Some(ref, instances), len(instances))
+
+
+class OracleSide:
+    """The oracle's part of every call of an arrangement case.  Alone it is the CPU form of a case; the GPU test wraps it.  Each stepping
+    method returns done (bool [n]) and leaves the call's rewards in `reward`."""
+
+    def __init__(self, env_id, n, options=None, sets=None, ref=None):
+        import oracle_lib
+
+        self.env_id, self.n = env_id, n
+        self.ref = ref if ref is not None else oracle_lib.OracleBatch(env_id, n, options=options)
+        self.discrete = self.ref.discrete
+        self.reward = np.zeros(n)
+        self.plan_id = {}  # instance -> index into the plan
+        self._masked = None
+        if sets is not None:  # instance i runs under sets[i & 1]: the reference's options belong to ONE instance, the oracle's too
+            for i, e in enumerate(self.ref.envs):
+                e.set_options(sets[i & 1])
+
+    def close(self):
+        self.ref.close()
+
+    def counter(self, name):
+        return None  # (a handle's debug counter; the oracle has none)
+
+    def reset(self, seeds, where=""):
+        self.ref.reset_digest(seeds)
+
+    reset_sets = reset
+
+    def inject_at(self, instances, plan_ids=None):
+        inject_at(self.ref, None, instances, plan_ids)
+        self._injected(instances, plan_ids)
+
+    def _injected(self, instances, plan_ids):
+        self.plan_id = dict(zip([int(i) for i in instances], range(len(instances)) if plan_ids is None else [int(p) for p in plan_ids]))
+
+    def step_unwatched(self, a, where=""):
+        return self.ref.step(a, autoreset=True, want_obs=False)[2].astype(bool)
+
+    def step(self, a, where="", autoreset=True):
+        _, rew, done = self.ref.step(a, autoreset=autoreset, want_obs=False)
+        self.reward = rew
+        return done.astype(bool)
+
+    headless = step
+
+    def noreset_step(self, a, where=""):
+        return self.step(a, where, autoreset=False)
+
+    def masked(self, a, m, where=""):
+        if self._masked is None:
+            import masked_step_inputs as mi
+
+            self._masked = mi.MaskedOracle(self.env_id, self.n, None, (), ref=self.ref)
+        self.reward, done, _ = self._masked.step(a, m)
+        return done
+
+    def masked_reset(self, m, where=""):
+        for i in np.nonzero(m)[0]:
+            self.ref.envs[i].reset(None, want_obs=False)
+
+    def advance(self, steps, eps, seed, step0, where=""):
+        """-> episodes ended (int [n]); `reward`: the step rewards added in step order"""
+        total, episodes = np.zeros(self.n), np.zeros(self.n, np.int32)
+        for t in range(steps):
+            _, r, d = self.ref.step(self.ref.expert_actions(eps, seed, step0 + t), autoreset=True, want_obs=False)
+            total += r
+            episodes += d.astype(np.int32)
+        self.reward = total
+        return episodes
+
+    def redraw(self, where=""):
+        pass
+
+    def expert(self, eps, seed, t, where=""):
+        return self.ref.expert_actions(eps, seed, t)
+
+    def screens(self):
+        """uint64 [n]: the digest of what lies on every instance's screen"""
+        import frame_digest as fd
+
+        return fd.digest_numpy(self.ref.frames(range(self.n)))
+
+    def vector(self):
+        return np.stack([e.get_list("vec") for e in self.ref.envs]).astype(np.float32)
+
+
+def _seeds(n):
+    return np.arange(n, dtype=np.int64) + 500
+
+
+def run_arrangement(case, make, cap=-1):
+    """Play one row of ARRANGEMENT_CASES on make(env_id, n, options, final=..., autoreset=..., sets=...) -> a side.
+    -> (side, calls, [(label, instances, Coverage)]): the caller asserts the cap and the conditions, then closes the side.
+    cap: the row's by default; None = a measuring run (up to MEASURE_LIMIT calls)."""
+    import masked_step_inputs as mi
+
+    env_id, arr, n_inj, size, options, row_cap = case
+    cap = row_cap if cap == -1 else cap
+    limit = MEASURE_LIMIT if cap is None else cap
+    n_inj = n_inj or injected(env_id)
+    n = size or handle_size(n_inj)
+    who = np.arange(n_inj)
+    label = "%s %s" % (env_id, arr)
+    prng = np.random.Generator(np.random.PCG64(21))
+    finished = np.zeros(2 * n if arr == "two-sets" else n, bool)
+    calls = 0
+
+    def unfinished():
+        return "%s: %d injected instances have not finished after %d calls" % (label, int((~finished[who]).sum()), calls)
+
+    if arr in ("headless", "headless-episode"):
+        side = make(env_id, n, options)
+        side.reset(_seeds(n), "seeded reset")
+        t0 = 0
+        if arr == "headless-episode":  # as case c: the warm-up drawn, under the oracle's expert
+            t0 = EPISODE_WARMUP[env_id]
+            for t in range(t0):
+                side.step_unwatched(side.expert(EPISODE_EPS, EPISODE_POLICY_SEED, t), "step %d" % t)
+        side.inject_at(who)
+        c0 = side.counter("headless_steps")
+        while (calls < limit) if arr == "headless-episode" else not finished[who].all():
+            assert calls < limit, unfinished()
+            a = side.expert(EPISODE_EPS, EPISODE_POLICY_SEED, t0 + calls) if arr == "headless-episode" else random_actions(prng, n, side.discrete)
+            finished |= side.headless(a, "headless step %d" % calls)
+            calls += 1
+        assert c0 is None or side.counter("headless_steps") - c0 == calls, "%s: headless_steps grew by %d in %d calls" % (label, side.counter("headless_steps") - c0, calls)
+        side.redraw("redraw() after the headless steps")
+        side.step(random_actions(prng, n, side.discrete), "the drawn step at the end")
+    elif arr in ("masked", "masked-blocks"):
+        side = make(env_id, n, options)
+        side.reset(_seeds(n), "seeded reset")
+        side.inject_at(who)
+        if arr == "masked":
+            mask, act = mi.bernoulli_inputs(side.discrete, MASK_ROWS, n)
+        else:
+            mask, act = mi.block_masks(MASK_ROWS, n), mi.actions(np.random.default_rng(7), side.discrete, MASK_ROWS, n)
+        counts = np.zeros(n, np.int64)
+        c0 = side.counter("masked_steps")
+        while not finished[who].all():
+            assert calls < limit, unfinished()
+            finished |= side.masked(mi.pick(act, counts), mask[calls], "masked step %d" % calls)
+            counts += mask[calls]
+            calls += 1
+        assert c0 is None or side.counter("masked_steps") - c0 == calls
+    elif arr in ("masked-reset", "masked-reset-final", "masked-reset-sets"):
+        if arr.endswith("sets"):  # (Endless-MysteryPath-v0: with option sets a masked reset goes through the queue server)
+            n, who = 2 * n, np.arange(2 * n_inj)
+            finished = np.zeros(n, bool)
+            side = make(env_id, n, None, autoreset=False, sets=TWO_SETS[env_id])
+            side.reset_sets(_seeds(n), "seeded resets under the two sets")
+            side.inject_at(who, who >> 1)
+        else:
+            side = make(env_id, n, options, final=arr.endswith("final"), autoreset=False)
+            side.reset(_seeds(n), "seeded reset")
+            side.inject_at(who)
+        while not finished[who].all():  # (finished: has been reset by a masked reset)
+            assert calls < limit, unfinished()
+            d = side.noreset_step(random_actions(prng, n, side.discrete), "step %d without auto-reset" % calls)
+            if d.any():
+                side.masked_reset(d, "reset(seed=None, mask=done) after step %d" % calls)
+            finished |= d
+            calls += 1
+    elif arr == "two-sets":
+        n, who = 2 * n, np.arange(2 * n_inj)
+        side = make(env_id, n, None, sets=TWO_SETS[env_id])
+        side.reset_sets(_seeds(n), "seeded resets under the two sets")
+        side.inject_at(who, who >> 1)  # (each set's instances take the whole sweep: instance i runs under set i & 1)
+        while not finished[who].all():
+            assert calls < limit, unfinished()
+            finished |= side.step(random_actions(prng, n, side.discrete), "step %d" % calls)
+            calls += 1
+        cov = [("%s, set %d" % (label, s), who[s::2], coverage_of(env_id, side.ref, who[s::2])) for s in (0, 1)]
+        return side, calls, cov
+    elif arr == "advance":
+        side = make(env_id, n, options)
+        side.reset(_seeds(n), "seeded reset")
+        side.inject_at(who)
+        c0 = side.counter("advance_fused_steps")
+        first = limit // 2
+        for steps, step0 in ((first, 0), (limit - first, first)):
+            finished |= side.advance(steps, ADVANCE_EPS, ADVANCE_SEED, step0, "advance(%d) from step %d" % (steps, step0)) > 0
+        calls = limit
+        assert c0 is None or side.counter("advance_fused_steps") - c0 == (calls if env_id in MORTAR else 0)
+        assert finished[who].all(), unfinished()
+    elif arr == "lane-generator":
+        side = make(env_id, n, options)
+        side.reset(_seeds(n), "seeded reset")
+        for t in range(LANE_WARMUP):
+            d = side.step_unwatched(random_actions(prng, n, side.discrete), "step %d" % t)
+            assert not d.any(), "%s: an instance finished before the truncation" % label
+        side.inject_at(who)
+        c0 = side.counter("path_lane_paths")
+        finished |= side.step(random_actions(prng, n, side.discrete), "the step that truncates everybody")
+        calls = 1
+        assert finished.all(), "%s: %d of %d instances were truncated" % (label, int(finished.sum()), n)
+        if c0 is not None:  # more than PATH_MASS paths in the queue, the injected instances' among them: the lane generator made (nearly) all
+            grew = side.counter("path_lane_paths") - c0
+            assert grew > 1024 and grew >= n_inj, "%s: the lane generator made %d of %d paths" % (label, grew, n)
+        for t in range(LANE_EXPERT_STEPS):  # the expert is the only reader of path_order
+            side.step(side.expert(0.0, ADVANCE_SEED, t, "expert_actions %d steps behind the truncation" % t), "step %d behind the truncation" % t)
+    else:
+        raise ValueError(arr)
+    return side, calls, [(label, who, coverage_of(env_id, side.ref, who))]
+
+
+def check_arrangement(case, side, calls, covs, exact):
+    """The conditions of a case, from the oracle's books: the cap (exact: as many calls as the row says, otherwise no more), 32 injected
+    instances with a rejection per Coverage, and what the arrangement adds."""
+    env_id, arr, cap = case[0], case[1], case[5]
+    assert calls == cap if exact else calls <= cap, "%s %s: %d calls, the row says %d" % (env_id, arr, calls, cap)
+    for label, _, cov in covs:
+        print("\n%s (%d calls): %s" % (label, calls, cov.summary()))
+        cov.assert_instances(label)
+    if arr == "two-sets" and TWO_SETS_OWN_SPANS[env_id] is not None:
+        for s, own in enumerate(TWO_SETS_OWN_SPANS[env_id]):
+            label, cov, other = covs[s][0], covs[s][2], covs[1 - s][2]
+            rejected = {sp for st in cov.stats for sp, (_, r) in st["spans"].items() if r}
+            drawn_by_other = {sp for st in other.stats for sp in st["spans"]}
+            assert rejected & own, "%s: rejected under %s, none of its own spans %s" % (label, sorted(rejected), sorted(own))
+            if env_id in MYSTERY:
+                assert 0 in cov.rejected_outputs(0), "%s: plan instance 0 rejected no word of the reset's first output (the cardinal choice)" % label
+            else:
+                assert not (own & drawn_by_other), "%s: the other set drew %s too" % (label, sorted(own & drawn_by_other))
+    if arr == "lane-generator":  # both has_uint32 values with a rejection behind the hand-over to the path generator
+        (label, who, cov), = covs
+        seen = {0: 0, 1: 0}
+        for k in range(len(who)):
+            has = plan(k)[1]
+            seen[has] += any(o >= handover_outputs(env_id, has) for o in cov.rejected_outputs(k))
+        assert seen[0] and seen[1], "%s: instances with a rejection behind the hand-over, by has_uint32: %s" % (label, seen)
+        print("   rejections behind the hand-over, by has_uint32: %s" % seen)

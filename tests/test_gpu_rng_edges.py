@@ -42,6 +42,10 @@ class Pair:
         self.env.close()
         self.ref.close()
 
+    def plan(self, i):
+        """(p, has, pattern) of the stream instance i received (tests/test_gpu_rng_edges_arrangements.py injects other instances than 0, 1, 2, ...)"""
+        return rc.plan(i)
+
     @staticmethod
     def _visual(o):
         return o["visual_observation"] if isinstance(o, dict) else o
@@ -56,13 +60,13 @@ class Pair:
             if what == "frames":  # (the oracle's screens still hold these; terminal frames are gone after its reset)
                 pixels = ", %d pixels of instance %d" % (int((obs[int(bad[0])].cpu().numpy() != self.ref.frames(bad[:1])[0]).any(-1).sum()), bad[0])
             raise AssertionError("%s %s: %d of %d %s differ from the oracle's; instances %s (p, has, pattern: %s)%s" % (
-                self.env_id, where, len(bad), self.n, what, bad[:8], [rc.plan(int(i)) for i in bad[:4]], pixels))
+                self.env_id, where, len(bad), self.n, what, bad[:8], [self.plan(int(i)) for i in bad[:4]], pixels))
 
     def _words(self, where):
         for i in self.watch:
             got, want = self.env.rng_words(i), self.ref.envs[i].rng_words()
             assert np.array_equal(got, want), "%s %s: RNG words of instance %d (p, has, pattern: %s): device %s, oracle %s" % (
-                self.env_id, where, i, rc.plan(i), [hex(int(x)) for x in got], [hex(int(x)) for x in want])
+                self.env_id, where, i, self.plan(i), [hex(int(x)) for x in got], [hex(int(x)) for x in want])
         self.env.check_errors()
 
     def reset(self, seeds, where):

@@ -191,3 +191,40 @@ def test_plan_draws_during_an_episode(env_id, n_inj, size, warmup, options):
     print("\n%s x%s draws during an episode: %s" % (env_id, size or n, cov.summary()))
     cov.assert_instances("%s x%s draws during an episode" % (env_id, size or n))
     ref.close()
+
+
+# ---- the arrangement cases of tests/test_gpu_rng_edges_arrangements.py on the oracle alone -------------------------------------------------
+
+def test_second_option_sets_have_other_spans_that_can_reject():
+    """list lengths 3 against 5 or 6, radius spans 7 against 5: every threshold non-zero; the two dictionaries of an id name the same
+    keys or keys no handle treats as geometry (lists, radii, max_steps, health, a reward)"""
+    assert all(rc.threshold(s) > 0 for s in (3, 5, 6, 7))
+    geometry = ("arena_size", "agent_scale", "agent_speed", "coin_scale", "show_last_action", "initial_spawn_interval", "spawn_interval_threshold",
+                "exit_scale", "camera_offset_scale")
+    for env_id, (a, b) in rc.TWO_SETS.items():
+        assert a != b and not any(k in geometry for k in list(a) + list(b)), env_id
+        own = rc.TWO_SETS_OWN_SPANS[env_id]
+        if own is not None:
+            assert not (own[0] & own[1]) and all(rc.threshold(s) > 0 for s in own[0] | own[1]), env_id
+
+
+def test_arrangement_table_sizes():
+    """no case above 1,300 instances or 200 calls; every size leaves the last wave partial (n % 64 == 3, twice that for two sets)"""
+    seen = set()
+    for case in rc.ARRANGEMENT_CASES:
+        env_id, arr, n_inj, size, _, cap = case
+        n = size or rc.handle_size(n_inj or rc.injected(env_id))
+        n *= 2 if arr.endswith("sets") else 1
+        assert n <= 1300 and 1 <= cap <= 200 and n % 64 in (3, 6), case
+        assert rc.case_id(case) not in seen
+        seen.add(rc.case_id(case))
+    assert {c[0] for c in rc.ARRANGEMENT_CASES if c[1] in ("headless", "masked", "masked-reset")} == set(rc.ALL_IDS)
+
+
+@pytest.mark.parametrize("case", rc.ARRANGEMENT_CASES, ids=rc.case_id)
+def test_plan_arrangement(case):
+    """The oracle needs exactly the calls of the row's cap (so it stays within it) and its books show the case's conditions (rc.check_arrangement): 32 injected instances with
+    a rejection (per set where there are two), each set's own span, both has_uint32 values behind the lane generator's hand-over."""
+    side, calls, covs = rc.run_arrangement(case, lambda env_id, n, options, final=False, autoreset=True, sets=None: rc.OracleSide(env_id, n, options, sets=sets))
+    rc.check_arrangement(case, side, calls, covs, exact=True)
+    side.close()
