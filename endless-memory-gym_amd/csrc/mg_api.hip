@@ -7,6 +7,7 @@
 
 #include "mg_expert.hpp"
 #include "mg_family.hpp"
+#include "mg_instances.hpp"
 #include "mg_lab.hpp"
 
 namespace mg {
@@ -36,6 +37,15 @@ struct mg_env {
         mg::DevArray<double> reward64, ep_reward;
         mg_info_buffers ib;
     } adv;
+    // mg_save_instances / mg_load_instances: the handle's number in this process (mg_instance_layout), the host-side counters, and what a load passes
+    // from its claim launch to the launches behind it, allocated at the handle's first load (include/memgym.h)
+    uint64_t serial = 0;
+    int64_t instance_saves = 0, instance_loads = 0;
+    struct Instances {
+        bool ready = false;
+        mg::DevArray<int32_t> claim;  // [num_envs] the entry of the current load that holds the instance
+        mg::DevArray<uint8_t> mask;   // [num_envs] the row mask a load with obs_dev draws by
+    } inst;
     std::string id;
     int obs_format = MG_OBS_U8_XYC;
     float* vec_dev = nullptr;     // the caller's vector-observation binding (mg_bind_vector_obs), or the single-instance block's
@@ -171,6 +181,12 @@ int mg_create(const char* env_id, int32_t num_envs, int device, mg_env** out) {
         e->id = id;
         e->family = family;
         e->variant = variant;
+        static std::mutex serial_mutex;
+        static uint64_t serials = 0;
+        {
+            std::lock_guard<std::mutex> lock(serial_mutex);
+            e->serial = ++serials;
+        }
         try {
             e->fam = make_family(family, variant, num_envs);
         } catch (...) {
@@ -479,6 +495,76 @@ int mg_advance(mg_env* env, int32_t steps, double eps, uint64_t seed, uint64_t s
     });
 }
 
+// ---- instance records (include/memgym.h: mg_save_instances / mg_load_instances; the kernels: mg_instances.hpp) ----
+}  // extern "C"
+namespace {
+// head of both calls: the refusals of include/memgym.h, then the family's row table
+mg::InstanceRows instance_call(mg_env* env, const char* who, int32_t count, const void* rec_dev) {
+    if (!env->started) throw std::runtime_error(std::string(who) + ": before the first mg_reset / mg_set_state");
+    if (count < 0) throw std::runtime_error(std::string(who) + ": count < 0");
+    if (!rec_dev || ((uintptr_t)rec_dev & 15u)) throw std::runtime_error(std::string(who) + ": rec_dev is NULL or not 16-byte aligned");
+    if (env->fam->geometry_dirty()) throw std::runtime_error(std::string(who) + ": options that change geometry need a reset first");
+    return mg::make_instance_rows(env->fam->instance_rows());
+}
+}  // namespace
+extern "C" {
+
+size_t mg_instance_bytes(const mg_env* env) {
+    if (!env || !env->fam) return 0;
+    try {
+        return mg::make_instance_rows(env->fam->instance_rows()).rec_bytes;
+    } catch (const std::exception& e) {
+        mg::set_error(e.what());
+        return 0;
+    }
+}
+
+uint64_t mg_instance_layout(const mg_env* env) {
+    if (!env || !env->fam) return 0;
+    return (env->serial << 24) | (env->fam->geometry_generation() & 0xFFFFFFull);
+}
+
+int mg_save_instances(mg_env* env, const int32_t* idx_dev, int32_t count, void* rec_dev, void* stream) {
+    return guarded(env, [&] {
+        const mg::InstanceRows t = instance_call(env, "mg_save_instances", count, rec_dev);
+        if (count == 0) return;
+        hipStream_t st = (hipStream_t)stream;
+        env->fam->before_instance_save(st);
+        hipLaunchKernelGGL(mg::instance_rows_kernel<true>, dim3((count + mg::INSTANCE_WAVES - 1) / mg::INSTANCE_WAVES, mg::instance_splits(t)),
+                           dim3(64 * mg::INSTANCE_WAVES), 0, st, t, idx_dev, (const int32_t*)nullptr, (const int32_t*)nullptr, count, env->num_envs,
+                           (char*)rec_dev, env->fam->error_word());
+        MG_HIP(hipGetLastError());
+        ++env->instance_saves;
+    });
+}
+
+int mg_load_instances(mg_env* env, const int32_t* idx_dev, const int32_t* rec_of_dev, int32_t count, const void* rec_dev, void* obs_dev, void* stream) {
+    return guarded(env, [&] {
+        const mg::InstanceRows t = instance_call(env, "mg_load_instances", count, rec_dev);
+        if (count == 0) return;
+        hipStream_t st = (hipStream_t)stream;
+        const int n = env->num_envs;
+        mg_env::Instances& I = env->inst;
+        if (!I.ready) {  // the handle's first load: the only one that allocates (and therefore not capturable)
+            if (mg::stream_capturing(st))
+                throw std::runtime_error("mg_load_instances: the handle's first call allocates its scratch and cannot be captured; call it once eagerly");
+            I.claim.alloc(n);
+            I.mask.alloc(n);
+            I.ready = true;
+        }
+        if (obs_dev) MG_HIP(hipMemsetAsync(I.mask.p, 0, (size_t)n, st));
+        hipLaunchKernelGGL(mg::load_claim_kernel, dim3((count + 255) / 256), dim3(256), 0, st, idx_dev, rec_of_dev, count, n, I.claim.p,
+                           obs_dev ? I.mask.p : (uint8_t*)nullptr, env->fam->error_word());
+        MG_HIP(hipGetLastError());
+        hipLaunchKernelGGL(mg::instance_rows_kernel<false>, dim3((count + mg::INSTANCE_WAVES - 1) / mg::INSTANCE_WAVES, mg::instance_splits(t)),
+                           dim3(64 * mg::INSTANCE_WAVES), 0, st, t, idx_dev, rec_of_dev, (const int32_t*)I.claim.p, count, n, (char*)rec_dev,
+                           env->fam->error_word());
+        MG_HIP(hipGetLastError());
+        if (obs_dev) env->fam->raster_only(obs_dev, I.mask.p, st);  // the masked step's dense launch: the loaded instances' frames, other rows untouched
+        ++env->instance_loads;
+    });
+}
+
 int mg_ground_truth64(mg_env* env, double* gt64_dev, void* stream) {
     return guarded(env, [&] {
         if (!env->fam->gt_dim()) return;
@@ -720,6 +806,10 @@ int mg_debug_counter(mg_env* env, const char* name, int64_t* value) {
         }
         if (std::string(name) == "headless_steps" || std::string(name) == "advance_fused_steps") {  // every id: counted in this file
             *value = std::string(name) == "headless_steps" ? env->headless_steps : env->advance_fused_steps;
+            return;
+        }
+        if (std::string(name) == "instance_saves" || std::string(name) == "instance_loads") {  // every id: counted in this file
+            *value = std::string(name) == "instance_saves" ? env->instance_saves : env->instance_loads;
             return;
         }
         if (std::string(name) == "masked_steps") {  // every id: counted in this file

@@ -105,6 +105,10 @@ struct RngStore {
     DevArray<uint64_t> s_hi, s_lo, i_hi, i_lo, buf;
     void alloc(size_t n) { s_hi.alloc(n); s_lo.alloc(n); i_hi.alloc(n); i_lo.alloc(n); buf.alloc(n); }
     RngSoA view() { return RngSoA{s_hi.p, s_lo.p, i_hi.p, i_lo.p, buf.p}; }
+    // (Family::instance_rows: the five words of one instance, 8 bytes each)
+    void rows(std::vector<std::pair<void*, size_t>>& v) {
+        for (auto* a : {&s_hi, &s_lo, &i_hi, &i_lo, &buf}) v.push_back({a->p, sizeof(uint64_t)});
+    }
     void blobs(std::vector<std::pair<void*, size_t>>& v) {
         v.push_back({s_hi.p, s_hi.bytes()}); v.push_back({s_lo.p, s_lo.bytes()}); v.push_back({i_hi.p, i_hi.bytes()});
         v.push_back({i_lo.p, i_lo.bytes()}); v.push_back({buf.p, buf.bytes()});
@@ -277,6 +281,13 @@ class Family {
     virtual void raster_debug(void* frames, hipStream_t s) = 0;
     // checkpoint: list of (device pointer, bytes) making up the state
     virtual std::vector<std::pair<void*, size_t>> state_blobs() = 0;
+    // mg_save_instances / mg_load_instances (mg_instances.hpp): the arrays that ARE [num_envs][row], as (device pointer, bytes per instance) -- everything the
+    // checkpoint holds per instance and the frame descriptor row; at most INSTANCE_MAX_ROWS.  What belongs to the handle and not to an instance stays out
+    virtual std::vector<std::pair<void*, size_t>> instance_rows() = 0;
+    // in front of a save's launch, on its stream: work a family has put off is done before the rows are read (Endless Mystery Path: owed path segments)
+    virtual void before_instance_save(hipStream_t /*s*/) {}
+    bool geometry_dirty() const { return dirty_; }                   // a geometry option was set since the last reset
+    uint64_t geometry_generation() const { return geom_gen_; }       // rebuilds of the geometry so far (mg_instance_layout)
     // called by mg_set_state after the blobs were restored: the instances now carry seeded RNG streams
     virtual void on_state_loaded() { seeded_ = true; }
     // called before anything looks at the state from outside (mg_get_state, mg_debug_rng, mg_render_debug): work a family has
@@ -299,6 +310,7 @@ class Family {
         MG_HIP(hipDeviceSynchronize());
         return err_.take();
     }
+    int* error_word() { return err_.dev; }  // the device address of the word, for kernels outside the families (mg_instances.hpp)
     // the same bits as seen right now, without synchronising or clearing
     virtual int peek_errors() { return err_.peek(); }
     // test / telemetry counters by name (mg_debug_counter); false = this family has no such counter.  Synchronous.
@@ -352,6 +364,7 @@ class Family {
     RngStore rng_;
     bool dirty_ = true;    // a geometry option changed: the next reset rebuilds atlases and constants first
     bool seeded_ = false;  // some reset carried seeds (or a state was loaded)
+    uint64_t geom_gen_ = 0;  // counts what makes earlier instance records invalid: every rebuild(), mg_set_capacity, a new vector-observation binding
 };
 
 Family* make_mortar(int variant, int num_envs);

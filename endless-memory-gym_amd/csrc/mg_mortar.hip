@@ -164,6 +164,7 @@ class MortarFamily : public Family {
         MG_HIP(hipDeviceSynchronize());
         P_.cmd_cap = (int)v;
         cmds_.alloc((size_t)n_ * P_.cmd_cap);
+        ++geom_gen_;
         sets_.refresh_geometry();
     }
     int64_t capacity(const std::string& what) const override {
@@ -183,7 +184,10 @@ class MortarFamily : public Family {
     int action_dim() const override { return P_.variant == V_GRID ? 1 : 2; }
     int gt_dim() const override { return P_.variant == V_ENDLESS ? 2 : 0; }
     int vec_dim() const override { return P_.taskb ? VEC_DIM : 0; }
-    void bind_vector_obs(float* dev) override { vec_ = dev; }
+    void bind_vector_obs(float* dev) override {
+        if (dev != vec_) ++geom_gen_;  // (the bound row travels in an instance record: instance_rows)
+        vec_ = dev;
+    }
     const char* info_name(int k) const override {
         if (P_.variant == V_ENDLESS) return k == 0 ? "commands_completed" : (k == 1 ? "max_command_sequence" : nullptr);
         return k == 0 ? "success" : (k == 1 ? "commands_completed" : nullptr);
@@ -331,6 +335,15 @@ class MortarFamily : public Family {
         return v;
     }
 
+    // (MortarMayhemB ids: the bound vector observation's row is CARRIED in the record -- it is constant over an episode and written by resets alone, so the
+    // row of the saved instance is the row the loaded one shows; handover_, claims_ and tdesc_ are words of one launch)
+    std::vector<std::pair<void*, size_t>> instance_rows() override {
+        std::vector<std::pair<void*, size_t>> v = {{state_.p, sizeof(MortarState)}, {cmds_.p, (size_t)P_.cmd_cap}, {desc_.p, sizeof(MortarDesc)}};
+        rng_.rows(v);
+        if (vec_) v.push_back({vec_, sizeof(float) * VEC_DIM});
+        return v;
+    }
+
     void expert_actions(const ExpertArgs& x, hipStream_t s) override {
         if (dirty_) throw std::runtime_error("options that change geometry need a reset before the next step");
         sets_.upload(s);
@@ -429,6 +442,7 @@ class MortarFamily : public Family {
         atlas_->upload();
         P_.glyph_x0 = (int)((SCREEN / 2) - std::floor(88 * SCALE / 2));
         dirty_ = false;
+        ++geom_gen_;
         sets_.refresh_geometry();
     }
 

@@ -151,6 +151,16 @@ class MysteryFamily : public Family {
         rng_.blobs(v);
         return v;
     }
+    // core, the segment store / path order and the frame descriptor of every id; the endless id's aux row (fall-off list, the record ahead of time: EMP_PRE travels
+    // in `core`), the finite ids' wall cells.  Not rows: the finite ids' 16-byte aux_ (no kernel reads it) and the endless id's walls_ (no kernel is given it);
+    // queue_, bgq_, bgflag_, tdesc_ and stats_ are words of a launch or counters of the handle.
+    std::vector<std::pair<void*, size_t>> instance_rows() override {
+        std::vector<std::pair<void*, size_t>> v = {{core_.p, sizeof(MysteryCore)}, {segs_.p, segs_.bytes() / (size_t)n_}, {desc_.p, sizeof(MysteryDesc)}};
+        if (P_.endless) v.push_back({aux_.p, sizeof(uint32_t) * AUX_WORDS});
+        else v.push_back({walls_.p, sizeof(uint64_t)});
+        rng_.rows(v);
+        return v;
+    }
     // (Endless: whatever is owed stays owed -- the node the expert aims at exists when a step has returned, mg_mystery_expert.hpp emp_expert)
     void expert_actions(const ExpertArgs& x, hipStream_t s) override {
         if (dirty_) throw std::runtime_error("options that change geometry need a reset before the next step");
@@ -284,6 +294,7 @@ class MysteryFamily : public Family {
         add_templates(*atlas_);
         atlas_->upload();
         dirty_ = false;
+        ++geom_gen_;
     }
     virtual void add_templates(Atlas&) {}  // rebuild(): the id's background templates, if it has any
 
@@ -492,6 +503,7 @@ class MysteryEndlessFamily final : public MysteryFamily {
         seg_rows_ = (int)v;
         segs_.alloc((size_t)n_ * seg_rows_ * SEG_STRIDE);
         P_.seg_cap = seg_rows_;
+        ++geom_gen_;
         sets_.refresh_geometry();
     }
     int64_t capacity(const std::string& what) const override {
@@ -661,6 +673,10 @@ class MysteryEndlessFamily final : public MysteryFamily {
     void on_state_loaded() override {
         seeded_ = true;
         owed_possible_ = true;  // the blob may carry owed segments
+    }
+    // (as a headless step does: stream-ordered; while capturing whether or not anything is owed NOW -- drawn steps may run between the replays)
+    void before_instance_save(hipStream_t s) override {
+        if (owed_possible_ || stream_capturing(s)) flush_owed(s);
     }
     void sync_state() override {
         if (owed_possible_) {

@@ -365,6 +365,15 @@ class SpotFamily : public Family {
         rng_.blobs(v);
         return v;
     }
+    // (flags_ and exit_hist_ are the handle's: ordered_holes only ever goes from 0 to 1, for every instance alive; the exit generations change with a rebuild
+    // alone, which changes mg_instance_layout; queue_ is a launch's)
+    std::vector<std::pair<void*, size_t>> instance_rows() override {
+        std::vector<std::pair<void*, size_t>> v = {{core_.p, sizeof(SpotCore)}, {coins_.p, sizeof(uint32_t) * MAX_COINS}, {sp_r_.p, sizeof(uint8_t) * SLOTS},
+                                                  {sp_ang_.p, sizeof(uint32_t) * SLOTS}, {sp_t_.p, sizeof(double) * SLOTS}, {sp_speed_.p, sizeof(double) * SLOTS},
+                                                  {desc_.p, sizeof(SpotDesc)}};
+        rng_.rows(v);
+        return v;
+    }
     void expert_actions(const ExpertArgs& x, hipStream_t s) override {
         if (dirty_) throw std::runtime_error("options that change geometry need a reset before the next step");
         sets_.upload(s);
@@ -474,6 +483,7 @@ class SpotFamily : public Family {
         atlas_->set_templates(build_chessboards(SCALE, SCREEN));
         atlas_->upload();
         dirty_ = false;
+        ++geom_gen_;
         sets_.refresh_geometry();
         {   // (the defaults' own radius / dim values, whatever set 0 holds by now)
             SpotOpt D;

@@ -96,6 +96,13 @@ def _load():
         L.mg_expert_actions.argtypes = [C.c_void_p, C.c_double, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
     if hasattr(L, "mg_advance"):  # (absent from the older builds tools/ A/B against through MEMGYM_HIP_LIB)
         L.mg_advance.argtypes = [C.c_void_p, C.c_int32, C.c_double, C.c_uint64, C.c_uint64, C.c_void_p, C.POINTER(AdvanceOut), C.c_void_p]
+    if hasattr(L, "mg_save_instances"):  # (absent from the older builds tools/ A/B against through MEMGYM_HIP_LIB)
+        L.mg_instance_bytes.argtypes = [C.c_void_p]
+        L.mg_instance_bytes.restype = C.c_size_t
+        L.mg_instance_layout.argtypes = [C.c_void_p]
+        L.mg_instance_layout.restype = C.c_uint64
+        L.mg_save_instances.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+        L.mg_load_instances.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.mg_enable_peer_access.argtypes = [C.c_int, C.c_int]
     L.mg_debug_rng.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
     L.mg_debug_set_rng.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]

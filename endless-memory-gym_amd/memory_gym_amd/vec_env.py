@@ -122,6 +122,78 @@ def alloc_obs_buffer(shape, dtype, device, search_budget_bytes=None, frame_bytes
     return t, owner.info
 
 
+class InstanceSnapshot:
+    """What VecMemoryGym.save_instances returns: `records`, a uint8 tensor [k, instance_bytes] on the handle's device (record j = the j-th saved
+    instance; the layout of a record is private), `layout`, the value of mg_instance_layout when it was taken (unique to the handle, new after every
+    rebuild of its geometry: load_instances refuses a snapshot whose layout is not the handle's current one), and `set_of`, the saved instances'
+    option-set indices (int32 [k]) or None where the handle had one option set."""
+    __slots__ = ("records", "layout", "set_of")
+
+    def __init__(self, records, layout, set_of=None):
+        self.records, self.layout, self.set_of = records, int(layout), set_of
+
+    @property
+    def count(self):
+        return int(self.records.shape[0])
+
+
+def _instance_index(what, name, t, device=None):
+    """An index argument of save_instances / load_instances / copy_instances -> a contiguous int32 tensor [m] (on `device` if given).  Integer
+    tensors, arrays and lists are taken; anything else, and anything that is not one-dimensional, is a ValueError."""
+    if not isinstance(t, torch.Tensor):
+        a = np.asarray(t)
+        if a.dtype.kind not in "iu":
+            raise ValueError("%s: %s must hold integers, got dtype %s" % (what, name, a.dtype))
+        t = torch.as_tensor(a.astype(np.int64))
+    if t.dtype not in (torch.int32, torch.int64):
+        raise ValueError("%s: %s must be an int32 or int64 tensor, got %s" % (what, name, t.dtype))
+    if t.dim() != 1:
+        raise ValueError("%s: %s must have one dimension, got shape %s" % (what, name, tuple(t.shape)))
+    t = t.to(dtype=torch.int32) if device is None else t.to(device=device, dtype=torch.int32)
+    return t.contiguous()
+
+
+def check_instance_load(snap, layout, instance_bytes, num_envs, idx=None, rec=None, device=None):
+    """The argument checks of load_instances, which need no handle: -> (idx, rec) as int32 tensors or None.  ValueError for a snapshot of another
+    handle or of an earlier geometry (`layout`), records of the wrong width, index tensors of the wrong dtype or length."""
+    what = "load_instances"
+    if not isinstance(snap, InstanceSnapshot):
+        raise ValueError("%s: need the InstanceSnapshot save_instances returned" % what)
+    if snap.layout != int(layout):
+        raise ValueError("%s: the snapshot (layout 0x%x) was taken from another handle, or before this handle's geometry was rebuilt (layout 0x%x): "
+                         "records are valid for the handle and the geometry they were saved under" % (what, snap.layout, int(layout)))
+    r = snap.records
+    if not (isinstance(r, torch.Tensor) and r.dtype == torch.uint8 and r.dim() == 2 and r.shape[1] == int(instance_bytes) and r.is_contiguous()):
+        raise ValueError("%s: snapshot.records must be a contiguous uint8 tensor [k, %d]" % (what, int(instance_bytes)))
+    if idx is not None:
+        idx = _instance_index(what, "idx", idx, device)
+    if rec is not None:
+        rec = _instance_index(what, "rec", rec, device)
+    m = num_envs if idx is None else idx.numel()
+    if rec is not None and rec.numel() != m:
+        raise ValueError("%s: rec must have one entry per loaded instance (%d), got %d" % (what, m, rec.numel()))
+    if rec is None and m > snap.count:
+        raise ValueError("%s: %d instances named, the snapshot holds %d records (pass rec= to load a record into several instances)" % (what, m, snap.count))
+    if snap.set_of is not None and tuple(snap.set_of.shape) != (snap.count,):
+        raise ValueError("%s: snapshot.set_of must have one entry per record" % what)
+    return idx, rec
+
+
+def check_instance_save(instance_bytes, num_envs, idx=None, out=None, device=None):
+    """The argument checks of save_instances, which need no handle: -> (idx as an int32 tensor or None, number of records)."""
+    what = "save_instances"
+    if idx is not None:
+        idx = _instance_index(what, "idx", idx, device)
+    k = num_envs if idx is None else idx.numel()
+    if out is not None:
+        if not isinstance(out, InstanceSnapshot):
+            raise ValueError("%s: out must be an InstanceSnapshot" % what)
+        r = out.records
+        if not (isinstance(r, torch.Tensor) and r.dtype == torch.uint8 and tuple(r.shape) == (k, int(instance_bytes)) and r.is_contiguous()):
+            raise ValueError("%s: out.records must be a contiguous uint8 tensor [%d, %d]" % (what, k, int(instance_bytes)))
+    return idx, k
+
+
 class VecMemoryGym:
     metadata = {"render_modes": ["rgb_array", "debug_rgb_array"], "render_fps": 25}
 
@@ -244,6 +316,7 @@ class VecMemoryGym:
         self._seeded = False  # no instance has an RNG stream before the first reset (or load_state_dict)
         self._swapped = False  # use_obs_buffer() since the last call that wrote every row
         self._stale = False    # step(render=False) / advance(render=False) since the last call that wrote every row: `obs` holds old bytes
+        self._copy_snap = None  # copy_instances(): the scratch snapshot, kept from call to call
         self._adv = None       # advance(): the sums' tensors and the mg_advance_out over them, made at the first call
         # `truncation` is always False in the reference; on_capacity="truncate": True where the episode ended on a capacity of this build
         self._truncated = self.capacity_u8.view(torch.bool) if self.capacity_u8 is not None else torch.zeros(N, dtype=torch.bool, device=dev)
@@ -542,6 +615,132 @@ class VecMemoryGym:
         self._expert_calls += 1
         return out
 
+    # ------------------------------------------------------------------ instance records
+    @property
+    def instance_bytes(self):
+        return int(_native.LIB.mg_instance_bytes(self._h))
+
+    @property
+    def instance_layout(self):
+        return int(_native.LIB.mg_instance_layout(self._h))
+
+    def _require_started(self, what):
+        if not self._seeded:
+            raise ValueError("%s: before the first reset (or load_state_dict)" % what)
+
+    def save_instances(self, idx=None, out=None):
+        """Save single instances to device memory (include/memgym.h: mg_save_instances) -> InstanceSnapshot.  idx: the instances, an integer
+        tensor / list (None: all, in order); entries < 0 are skipped (their records keep their bytes).  out: a snapshot of the same number of
+        records to write into (its tensors are reused, nothing is allocated with one option set).  One small launch on the current stream;
+        nothing synchronises and nothing observable changes on any instance."""
+        self._require_started("save_instances")
+        nbytes = self.instance_bytes
+        idx, k = check_instance_save(nbytes, self.num_envs, idx, out, self.device)
+        records = out.records if out is not None else torch.empty((k, nbytes), dtype=torch.uint8, device=self.device)
+        if records.device != self.device or records.data_ptr() % 16:
+            raise ValueError("save_instances: out.records must be a 16-byte aligned tensor on %s" % (self.device,))
+        with torch.cuda.device(self.device):
+            _native.check(_native.LIB.mg_save_instances(self._h, None if idx is None else idx.data_ptr(), k, records.data_ptr(), self._stream()), "mg_save_instances")
+            set_of = None
+            if self._set_of is not None:  # the caller owns the set index (include/memgym.h): it travels beside the records
+                set_of = self._set_of.clone() if idx is None else self._set_of[idx.clamp(0, self.num_envs - 1).long()]
+        if out is not None:
+            out.layout, out.set_of = self.instance_layout, set_of
+            return out
+        return InstanceSnapshot(records, self.instance_layout, set_of)
+
+    def _scatter_rows(self, dst, tgt, rows):
+        """dst[tgt[j]] = rows[j]; tgt[j] == len(dst) names nobody (a skipped entry).  No host look."""
+        ext = torch.cat([dst, dst[:1]])
+        ext.index_copy_(0, tgt, rows.to(dst.dtype))
+        dst.copy_(ext[:dst.shape[0]])
+
+    def load_instances(self, snap, idx=None, rec=None, render=True):
+        """Load records of `snap` into instances (include/memgym.h: mg_load_instances): instance idx[j] <- record rec[j] (rec=None: record j;
+        idx=None: instance j).  From then on instance idx[j] gives, for the same actions, bit for bit what the saved instance gave from the moment
+        of the save; every other instance keeps everything.  Entries idx[j] < 0 are skipped; the instances named must be distinct; one record may go
+        to many instances.  render=True returns `obs` like redraw(): the loaded instances' rows are drawn -- and, where `obs` was stale
+        (render=False steps, use_obs_buffer()), everybody's, so `obs` never holds a mixture.  render=False draws nothing, marks `obs` stale and
+        returns None (refused on a final_observation handle, like step(render=False)).  The option-set indices saved with the records are copied
+        into the handle's binding, the loaded rows of the ground truth are refreshed, `final_observation` rows are left alone.  ValueError,
+        before anything is enqueued: a snapshot of another handle or of an earlier geometry, records of the wrong width, index tensors of the
+        wrong dtype or length.  Launches only; nothing synchronises."""
+        self._require_started("load_instances")
+        if not render and self.final_obs is not None:
+            raise ValueError("load_instances(render=False) on a handle with final_observation=True: terminal observations are frames")
+        N = self.num_envs
+        idx, rec = check_instance_load(snap, self.instance_layout, self.instance_bytes, N, idx, rec, self.device)
+        if snap.records.device != self.device or snap.records.data_ptr() % 16:
+            raise ValueError("load_instances: snapshot.records must be a 16-byte aligned tensor on %s" % (self.device,))
+        if snap.set_of is not None and self._set_of is None:
+            raise ValueError("load_instances: the snapshot was taken under per-instance option sets, which a full reset has dropped since")
+        k = snap.count
+        m = N if idx is None else idx.numel()
+        draw_all = render and (self._swapped or self._stale)
+        obs_ptr = self.obs.data_ptr() if (render and not draw_all) else None
+        with torch.cuda.device(self.device):
+            # The C call takes ONE count for its entries and its records (rec_of_dev[j] in 0 .. count-1): the entries are dealt out in calls of
+            # exactly k, padded with idx = -1, so that any record of the snapshot can be named and none beyond it
+            if m == k:
+                calls = [(idx, rec)]
+            else:
+                total = (m + k - 1) // k * k
+                pi = torch.full((total,), -1, dtype=torch.int32, device=self.device)
+                pi[:m] = torch.arange(m, dtype=torch.int32, device=self.device) if idx is None else idx
+                pr = torch.zeros(total, dtype=torch.int32, device=self.device)
+                pr[:m] = torch.arange(m, dtype=torch.int32, device=self.device) if rec is None else rec
+                calls = [(pi[c:c + k], pr[c:c + k]) for c in range(0, total, k)]
+            for ci, cr in calls:
+                _native.check(_native.LIB.mg_load_instances(self._h, None if ci is None else ci.data_ptr(), None if cr is None else cr.data_ptr(), k,
+                                                            snap.records.data_ptr(), obs_ptr, self._stream()), "mg_load_instances")
+            # what the handle keeps beside the state: the set index (the caller's, include/memgym.h) and the ground truth rows
+            whole = idx is None and rec is None  # instance j <- record j for every j
+            tgt = src = None
+            if not whole and (self._set_of is not None or self.gt_dim):
+                i64 = (torch.arange(m, device=self.device) if idx is None else idx.long())
+                src = (torch.arange(m, device=self.device) if rec is None else rec.long())
+                ok = (i64 >= 0) & (i64 < N) & (src >= 0) & (src < k)
+                tgt = torch.where(ok, i64, torch.full_like(i64, N))
+                src = src.clamp(0, k - 1)
+            if self._set_of is not None:
+                sets = snap.set_of if snap.set_of is not None else torch.zeros(k, dtype=torch.int32, device=self.device)
+                if whole:
+                    self._set_of.copy_(sets)
+                else:
+                    self._scatter_rows(self._set_of, tgt, sets[src])
+            if self.gt_dim:
+                g = torch.empty((N, self.gt_dim), dtype=torch.float64, device=self.device)
+                _native.check(_native.LIB.mg_ground_truth64(self._h, g.data_ptr(), self._stream()), "mg_ground_truth64")
+                for dst in (self.gt, self.gt64):
+                    if dst is None:
+                        continue
+                    if whole:
+                        dst.copy_(g.to(dst.dtype))
+                    else:
+                        self._scatter_rows(dst, tgt, g[tgt.clamp(0, N - 1)])
+        if not render:  # (an index out of range raises bit 512, sticky: the next step() / check_errors() reports it)
+            self._stale = True
+            return None
+        if draw_all:
+            return self.redraw()
+        return self._obs()
+
+    def copy_instances(self, src, dst, render=True):
+        """Instance dst[j] <- instance src[j] inside the handle: a save followed by a load through a scratch snapshot the handle keeps, so `src` and
+        `dst` may overlap (a permutation in place).  Returns what load_instances returns."""
+        self._require_started("copy_instances")
+        src = _instance_index("copy_instances", "src", src, self.device)
+        dst = _instance_index("copy_instances", "dst", dst, self.device)
+        if src.numel() != dst.numel():
+            raise ValueError("copy_instances: src and dst must have the same length, got %d and %d" % (src.numel(), dst.numel()))
+        if src.numel() == 0:
+            return self._obs() if render else None
+        s = self._copy_snap
+        if s is None or tuple(s.records.shape) != (src.numel(), self.instance_bytes):
+            s = None
+        self._copy_snap = self.save_instances(src, out=s)
+        return self.load_instances(self._copy_snap, idx=dst, render=render)
+
     def new_obs_buffer(self):
         """A second observation buffer like `obs` (same shape, dtype, device and -- if `obs` came from mg_obs_alloc -- the same
         zone-balanced placement), for consumers that double-buffer (use_obs_buffer)."""
@@ -664,7 +863,8 @@ class VecMemoryGym:
                   16: "past-path window wider than 16 columns",
                   32: "Endless Mortar Mayhem command list reached its 512-entry capacity (the episode was ended)",
                   64: "a deferred-reset queue overflowed (a previous fused launch did not drain it)",
-                  256: "use_exit=False for an instance that never had an exit (the reference raises AttributeError at this reset)"}
+                  256: "use_exit=False for an instance that never had an exit (the reference raises AttributeError at this reset)",
+                  512: "save_instances / load_instances: an instance or record index out of range (the entry was skipped)"}
 
     def check_errors(self):
         """Raise if a kernel flagged a capacity/failure condition since the last call (synchronises the device).
@@ -850,6 +1050,21 @@ class MemoryGymEnv(_EnvBase):
 
     def load_state_dict(self, sd):
         self.vec.load_state_dict(sd)
+
+    def snapshot(self):
+        """The instance as it stands, in device memory (VecMemoryGym.save_instances) -- for restore()."""
+        return self.vec.save_instances()
+
+    def restore(self, snap):
+        """Put the instance back where snapshot() found it (VecMemoryGym.load_instances): the following steps give what the steps after the
+        snapshot gave.  -> the observation of that moment, as reset() returns it.  Not a hot path (a launch, a frame and a copy to the host)."""
+        v = self.vec
+        v.load_instances(snap, render=True)
+        torch.cuda.current_stream(v.device).synchronize()
+        self._obs_host[...] = v.obs[0].cpu().numpy()
+        if v.gt_dim:
+            self._gt_host[:v.gt_dim] = (v.gt64 if v.gt64 is not None else v.gt)[0].double().cpu().numpy()
+        return self._observation()
 
     def close(self):
         self.vec.close()

@@ -107,6 +107,20 @@ class GymnasiumVectorEnv(_Base):
         obs, st = self.env.advance(steps, eps=eps, seed=seed, step=step, render=render, stats=stats)
         return (None if obs is None else self._host(obs)), (None if st is None else self._host(st))
 
+    def save_instances(self, idx=None, out=None):
+        """VecMemoryGym.save_instances: single instances to device memory -> InstanceSnapshot."""
+        return self.env.save_instances(idx=idx, out=out)
+
+    def load_instances(self, snap, idx=None, rec=None, render=True):
+        """VecMemoryGym.load_instances -> obs (numpy with as_numpy); this handle keeps terminal observations, so render=False is refused."""
+        obs = self.env.load_instances(snap, idx=idx, rec=rec, render=render)
+        return None if obs is None else self._host(obs)
+
+    def copy_instances(self, src, dst, render=True):
+        """VecMemoryGym.copy_instances -> obs (numpy with as_numpy)."""
+        obs = self.env.copy_instances(src, dst, render=render)
+        return None if obs is None else self._host(obs)
+
     # gymnasium.vector.VectorEnv API surface used by trainers
     def step_async(self, actions):
         self._pending = actions

@@ -333,6 +333,49 @@ size_t mg_state_size(const mg_env* env);
 int mg_get_state(mg_env* env, void* host_buf, size_t size);
 int mg_set_state(mg_env* env, const void* host_buf, size_t size);
 
+/* INSTANCE RECORDS: single instances saved to and loaded from caller-owned DEVICE memory -- rewind an instance to a checkpoint of its own episode,
+ * branch K action sequences from one state (counterfactual probes: same state, different memory content), search and archive-and-return exploration,
+ * hand one hard state to many instances, move states around inside a batch.  (mg_get_state / mg_set_state cover the whole handle, are synchronous
+ * and go through host memory.)
+ *   mg_save_instances   record j <- instance idx_dev[j]                  (idx_dev == NULL: instance j), j = 0 .. count-1
+ *   mg_load_instances   instance idx_dev[j] <- record rec_of_dev[j]      (rec_of_dev == NULL: record j; idx_dev == NULL: instance j)
+ * DEFINITION: let record r be saved from instance s at some moment.  After a load of r into instance d, instance d gives from then on, for the same
+ * actions in the same order, bit for bit what instance s gave from the moment of the save: state and PCG64 stream, frames, reward, done and ground
+ * truth, episode records, same-call auto-resets, capacity ends, error bits, mg_expert_actions, mg_render_debug and the bound vector observation.  Every
+ * instance the load does not name keeps everything; a save changes nothing observable on any instance.  A copy inside the handle is a save followed by a
+ * load through the buffer, so overlapping source and destination sets are no special case.
+ * count is a host integer (it sizes the grid), 0 <= count; count == 0 does nothing.  rec_dev: 16-byte aligned, count * mg_instance_bytes bytes; the
+ * layout of a record is private.  idx_dev / rec_of_dev: int32 [count] on the device, read by the launches; the host never looks at them.  An entry
+ * idx_dev[j] < 0 is skipped: a fixed-size index array padded with -1 serves any subset without a host look, and a captured graph replays with other
+ * contents.  An entry idx_dev[j] >= num_envs, or rec_of_dev[j] outside 0 .. count-1, is skipped as well and raises error bit 512 (mg_poll_errors); it
+ * never becomes an out-of-bounds access.  One record may be loaded into many instances.  The instance indices of ONE load must be distinct: with
+ * duplicates it is unspecified which entry wins, but the instance ends up holding exactly one whole record (a claim launch in front of the copy decides).
+ * WHAT TRAVELS: everything the checkpoint holds per instance, and the frame descriptor row -- so mg_render after a load draws the loaded instance's
+ * frame as of the save.  The MortarMayhemB ids' bound vector observation row is carried in the record and written back by the load (bind before the
+ * save; a new binding is a new layout).  Endless-MysteryPath-v0: path segments still owed are generated before a save reads, stream-ordered (the launch
+ * a headless step uses); a record generated ahead of time belongs to the instance and travels with it.  WHAT DOES NOT: the words of a launch (hand-over,
+ * claim and ticket words, queues, counters) and the caller's set_of_dev entry (mg_bind_option_sets) -- THE CALLER OWNS IT AND COPIES IT: an instance
+ * loaded from a record runs under the option set its set_of_dev entry names, so copy the saved instance's entry along (the Python mirror does).
+ * VALIDITY: a record is valid for the handle it was saved from, under the geometry it was saved under -- not for another handle (exit generations and
+ * atlases are handle-local) and not across a rebuild of the geometry (a geometry option followed by a reset; mg_set_capacity; mg_set_state on the
+ * spotlight family; a new mg_bind_vector_obs binding).  mg_instance_layout returns a 64-bit value that is unique to the handle within the process and
+ * changes at every such rebuild: keep it next to the records and compare before loading.  mg_load_instances CANNOT check this -- the records carry no
+ * header -- and loading a stale record is undefined for the named instances.  mg_instance_bytes is fixed once the handle has been reset.
+ * obs_dev != NULL: the load draws the frames of the loaded instances, and only those, into their rows (the masked step's raster launch); other rows
+ * are untouched.  obs_dev == NULL draws nothing; mg_render later shows the loaded frames.
+ * LAUNCHES: both calls only enqueue on `stream`, nothing synchronises.  A save: (Endless-MysteryPath-v0: the owed-segment launch,) one row-copy launch
+ * -- a wave per record, each row moved with the widest access its size allows, rows longer than 16 KiB shared by several waves.  A load: a small claim
+ * launch, the row-copy launch, and with obs_dev a memset of the row mask and one raster launch.  The scratch a load needs (an int32 claim word and a
+ * uint8 row-mask entry per instance) is allocated AT THE HANDLE'S FIRST mg_load_instances; every later call allocates nothing, and both calls can be
+ * captured into a HIP graph (the index arrays are read at replay).  MG_STATE_VERSION is unchanged: no state is added.
+ * mg_debug_counter "instance_saves" / "instance_loads" count the calls with count > 0, on the host.
+ * Errors (-1): before the first mg_reset / mg_set_state; count < 0; a NULL or misaligned rec_dev; a geometry option set since the last reset. */
+size_t   mg_instance_bytes(const mg_env* env);   /* bytes of one record; a multiple of 16 */
+uint64_t mg_instance_layout(const mg_env* env);
+int mg_save_instances(mg_env* env, const int32_t* idx_dev, int32_t count, void* rec_dev, void* stream);
+int mg_load_instances(mg_env* env, const int32_t* idx_dev, const int32_t* rec_of_dev, int32_t count, const void* rec_dev,
+                      void* obs_dev, void* stream);
+
 /* Measurement hooks (bench.py's roofline leg): mg_set_profiling(env, N) makes every N-th mg_step (N = 1: every step,
  * 0: off) bracket its kernels with hipEvents recorded on the launch stream (a bracketed step costs ~15 us of stream
  * time, hence the sampling).  mg_get_profile(kind) synchronises, returns the summed elapsed milliseconds and the
@@ -353,6 +396,8 @@ int mg_get_profile(mg_env* env, int kind, double* total_ms, int64_t* launches);
  * 256  SearingSpotlights-v0: use_exit = False at the reset of an instance that has never had an exit (the reference raises
  *      AttributeError there, searing_spotlights.py:431-435; with an earlier exit it keeps drawing that one, and so does this
  *      library); no exit was drawn
+ * 512  mg_save_instances / mg_load_instances: an instance index >= num_envs, or a record index outside the call's records; the entry was
+ *      skipped, nothing else changed
  * 128  reserved (rounds <= 3: a frame workgroup of the mortar family's one-launch step gave up waiting for its descriptor.
  *      Since round 4 that launch cannot time out -- a frame wave that waits too long steps the instances itself,
  *      mg_mortar.hip mortar_step_raster_kernel -- and the bit is never raised) */
@@ -448,7 +493,8 @@ int mg_enable_peer_access(int device, int peer_device);
  * (mg_info_buffers.final_obs_dev, autoreset) on the generic path -- a step without auto-reset, a copy of the finished rows, a masked reset --
  * instead of inside the step's own launches, counted on the host.  "headless_steps" (every id): headless steps of this handle -- mg_step calls
  * with obs_dev == NULL and the steps mg_advance took through its loop form; "advance_fused_steps" (every id; only the mortar family has the
- * form): steps mg_advance took inside mortar_advance_kernel.  Both counted on the host.  Unknown name: -1.  Synchronous. */
+ * form): steps mg_advance took inside mortar_advance_kernel.  Both counted on the host.  "instance_saves" / "instance_loads" (every id):
+ * mg_save_instances / mg_load_instances calls of this handle with count > 0, counted on the host.  Unknown name: -1.  Synchronous. */
 int mg_debug_counter(mg_env* env, const char* name, int64_t* value);
 
 /* Test hook: copy the numpy-compatible PCG64 words of instance i to host:
