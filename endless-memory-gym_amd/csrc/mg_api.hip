@@ -37,6 +37,16 @@ struct mg_env {
         mg::DevArray<double> reward64, ep_reward;
         mg_info_buffers ib;
     } adv;
+    int64_t play_fused_steps = 0;      // mg_debug_counter: steps mg_play took inside a family's own launches (Family::play)
+    // mg_play: what the loop of its definition passes from launch to launch, allocated at the handle's first call (include/memgym.h)
+    struct Play {
+        bool ready = false;
+        mg::DevArray<uint8_t> alive, done;
+        mg::DevArray<int32_t> ep_length;
+        mg::DevArray<float> reward, aux[MG_INFO_SLOTS];
+        mg::DevArray<double> reward64, ep_reward;
+        mg_info_buffers ib;
+    } ply;
     // mg_save_instances / mg_load_instances: the handle's number in this process (mg_instance_layout), the host-side counters, and what a load passes
     // from its claim launch to the launches behind it, allocated at the handle's first load (include/memgym.h)
     uint64_t serial = 0;
@@ -495,6 +505,100 @@ int mg_advance(mg_env* env, int32_t steps, double eps, uint64_t seed, uint64_t s
     });
 }
 
+}  // extern "C"
+// One step of mg_play's loop form: advance_accumulate_kernel's additions in its order (a paused instance's rows are the zeros of the masked step: its sums
+// stay 0), then the step counts where the instance was alive, and MG_PLAY_EPISODE: an instance that has just finished is alive no longer.
+__global__ __launch_bounds__(256) void play_accumulate_kernel(int n, int first, int episode, mg_info_buffers ib, const uint8_t* __restrict__ done, uint8_t* alive,
+                                                              int32_t* played, mg_advance_out o) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const bool d = done[i] != 0;
+    if (o.reward_sum_dev) o.reward_sum_dev[i] = (first ? 0.0 : o.reward_sum_dev[i]) + ib.reward64_dev[i];
+    if (o.episodes_dev) o.episodes_dev[i] = (first ? 0 : o.episodes_dev[i]) + (d ? 1 : 0);
+    if (o.ep_reward_sum_dev && (first || d)) o.ep_reward_sum_dev[i] = (first ? 0.0 : o.ep_reward_sum_dev[i]) + (d ? ib.ep_reward_dev[i] : 0.0);
+    if (o.ep_length_sum_dev && (first || d)) o.ep_length_sum_dev[i] = (first ? (int64_t)0 : o.ep_length_sum_dev[i]) + (d ? (int64_t)ib.ep_length_dev[i] : (int64_t)0);
+#pragma unroll
+    for (int k = 0; k < MG_INFO_SLOTS; ++k)
+        if (o.aux_sum_dev[k] && ib.aux_dev[k] && (first || d)) o.aux_sum_dev[k][i] = (first ? 0.0 : o.aux_sum_dev[k][i]) + (d ? (double)ib.aux_dev[k][i] : 0.0);
+    const bool a = alive ? alive[i] != 0 : true;
+    if (played) played[i] = (first ? 0 : played[i]) + (a ? 1 : 0);
+    if (episode && d) alive[i] = 0;  // (episode: alive is the handle's scratch row, never NULL)
+}
+extern "C" {
+
+int mg_play(mg_env* env, const int32_t* tape_dev, int32_t steps, int mode, const uint8_t* active_dev, float* reward_trace_dev, uint8_t* done_trace_dev,
+            int32_t* steps_played_dev, float* gt_dev, const mg_advance_out* sums, void* stream) {
+    return guarded(env, [&] {
+        if (!env->started) throw std::runtime_error("mg_play: before the first mg_reset / mg_set_state");
+        if (steps < 1) throw std::runtime_error("mg_play: steps < 1");
+        if (!tape_dev) throw std::runtime_error("mg_play: tape_dev is NULL");
+        if (mode != MG_PLAY_THROUGH && mode != MG_PLAY_EPISODE) throw std::runtime_error("mg_play: mode is neither MG_PLAY_THROUGH nor MG_PLAY_EPISODE");
+        if (env->fam->geometry_dirty()) throw std::runtime_error("mg_play: options that change geometry need a reset before the next step");
+        mg_advance_out o;
+        memset(&o, 0, sizeof(o));
+        if (sums) {  // (as the caller's header laid it out: a shorter struct lacks the later slots)
+            const size_t sz = sums->struct_size;
+            if (sz < offsetof(mg_advance_out, aux_sum_dev) || sz > sizeof(o) + 16 * sizeof(void*) || sz % sizeof(void*) != 0)
+                throw std::runtime_error("mg_play: mg_advance_out.struct_size = " + std::to_string(sz) + " is not a layout of include/memgym.h; set it to sizeof(mg_advance_out)");
+            memcpy(&o, sums, sz < sizeof(o) ? sz : sizeof(o));
+        }
+        o.struct_size = sizeof(o);
+        hipStream_t st = (hipStream_t)stream;
+        mg::Family* f = env->fam;
+        const int n = env->num_envs;
+        mg_env::Play& P = env->ply;
+        if (!P.ready) {  // the handle's first call: the only one that allocates (and therefore not capturable)
+            if (mg::stream_capturing(st))
+                throw std::runtime_error("mg_play: the handle's first call allocates its scratch and cannot be captured; call it once eagerly");
+            P.alive.alloc(n);
+            P.reward.alloc(n);
+            P.done.alloc(n);
+            P.reward64.alloc(n);
+            P.ep_reward.alloc(n);
+            P.ep_length.alloc(n);
+            memset(&P.ib, 0, sizeof(P.ib));
+            P.ib.struct_size = sizeof(P.ib);
+            P.ib.reward64_dev = P.reward64.p;
+            P.ib.ep_reward_dev = P.ep_reward.p;
+            P.ib.ep_length_dev = P.ep_length.p;
+            for (int k = 0; k < MG_INFO_SLOTS && f->info_name(k); ++k) {
+                P.aux[k].alloc(n);
+                P.ib.aux_dev[k] = P.aux[k].p;
+            }
+            P.ready = true;
+        }
+        const int episode = mode == MG_PLAY_EPISODE ? 1 : 0;
+        float* gt = f->gt_dim() ? gt_dev : nullptr;
+        if (f->play(mg::PlayArgs{steps, episode, tape_dev, active_dev, reward_trace_dev, done_trace_dev, steps_played_dev, P.reward.p, P.done.p, P.alive.p, gt,
+                                 P.ib, o},
+                    st)) {
+            env->play_fused_steps += steps;
+            return;
+        }
+        // the loop of the definition.  The mask of step t: the caller's while it cannot change (MG_PLAY_THROUGH), else the handle's alive row
+        const uint8_t* mask = active_dev;
+        if (episode) {
+            if (active_dev) MG_HIP(hipMemcpyAsync(P.alive.p, active_dev, (size_t)n, hipMemcpyDeviceToDevice, st));
+            else MG_HIP(hipMemsetAsync(P.alive.p, 1, (size_t)n, st));
+            mask = P.alive.p;
+        }
+        const size_t row = (size_t)n * (size_t)f->action_dim();
+        const bool accumulate = sums || steps_played_dev || episode;
+        for (int t = 0; t < steps; ++t) {
+            float* r = reward_trace_dev ? reward_trace_dev + (size_t)t * (size_t)n : P.reward.p;
+            uint8_t* d = done_trace_dev ? done_trace_dev + (size_t)t * (size_t)n : P.done.p;
+            f->step(tape_dev + (size_t)t * row, mask, nullptr, r, d, gt, &P.ib, episode ? 0 : 1, st);
+            if (accumulate) {
+                hipLaunchKernelGGL(play_accumulate_kernel, dim3((n + 255) / 256), dim3(256), 0, st, n, t == 0 ? 1 : 0, episode, P.ib, (const uint8_t*)d,
+                                   episode ? P.alive.p : (uint8_t*)active_dev, steps_played_dev, o);
+                MG_HIP(hipGetLastError());
+            }
+        }
+        env->headless_steps += steps;
+        if (mask) env->masked_steps += steps;
+    });
+}
+
 // ---- instance records (include/memgym.h: mg_save_instances / mg_load_instances; the kernels: mg_instances.hpp) ----
 }  // extern "C"
 namespace {
@@ -806,6 +910,10 @@ int mg_debug_counter(mg_env* env, const char* name, int64_t* value) {
         }
         if (std::string(name) == "headless_steps" || std::string(name) == "advance_fused_steps") {  // every id: counted in this file
             *value = std::string(name) == "headless_steps" ? env->headless_steps : env->advance_fused_steps;
+            return;
+        }
+        if (std::string(name) == "play_fused_steps") {  // every id: counted in this file (only the mortar family has the form)
+            *value = env->play_fused_steps;
             return;
         }
         if (std::string(name) == "instance_saves" || std::string(name) == "instance_loads") {  // every id: counted in this file

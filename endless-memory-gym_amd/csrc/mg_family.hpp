@@ -228,6 +228,24 @@ struct AdvanceArgs {
     mg_advance_out out;
 };
 
+// mg_play (include/memgym.h) as it reaches a family that can run the whole loop inside its own launches: the caller's tape, mask, traces and sums, and
+// the handle's scratch rows (what the loop's mg_step_masked calls would be given; info as in AdvanceArgs, alive: the loop's mask from launch to launch).
+struct PlayArgs {
+    int steps;
+    int episode;             // mode == MG_PLAY_EPISODE
+    const int32_t* tape;     // [steps][num_envs * action_dim]
+    const uint8_t* active;   // the caller's, or NULL
+    float* reward_trace;     // [steps][num_envs], or NULL
+    uint8_t* done_trace;     // [steps][num_envs], or NULL
+    int32_t* played;         // [num_envs], or NULL
+    float* reward;
+    uint8_t* done;
+    uint8_t* alive;
+    float* gt;  // the caller's, or NULL
+    mg_info_buffers info;
+    mg_advance_out out;
+};
+
 // What the C ABI (mg_api.hip) sees of an environment family, and the host-side plumbing the three families share: the error
 // word, the RNG streams, the "seeded" / "geometry changed" guards and the debug view's scratch frames.
 class Family {
@@ -270,6 +288,9 @@ class Family {
     // mg_advance: true = the family has run the loop of include/memgym.h's definition inside launches of its own (the mortar family:
     // mortar_advance_kernel); false = it has no such form (or the lab build switched it off) and nothing happened: mg_api.hip runs the loop.
     virtual bool advance(const AdvanceArgs& /*v*/, hipStream_t /*s*/) { return false; }
+    // mg_play: true = the family has run the loop of include/memgym.h's definition inside launches of its own (the mortar family:
+    // mortar_play_kernel); false = it has no such form (or the lab build switched it off) and nothing happened: mg_api.hip runs the loop.
+    virtual bool play(const PlayArgs& /*v*/, hipStream_t /*s*/) { return false; }
     // rasterise the CURRENT frame descriptors of the instances with only[i] != 0 into `obs` (others untouched)
     virtual void raster_only(void* obs, const uint8_t* only, hipStream_t s) = 0;
     // true: step(..., autoreset = 1) with info->final_obs_dev set keeps the terminal observations ITSELF (the frame workgroup of a finishing

@@ -15,6 +15,7 @@
 //   mg_mortar_one_launch.hpp  mortar_step_raster_kernel: the step as one launch, its claim / hand-over word, RESCUE_AFTER_TICKS
 //   mg_mortar_expert.hpp      mortar_expert_kernel: the scripted teacher of the five ids (mg_expert_actions), a launch of its own
 //   mg_mortar_advance.hpp     mortar_advance_kernel: K steps under the teacher without a frame (mg_advance), teacher + step + sums per lane in one launch
+//   mg_mortar_play.hpp        mortar_play_kernel: K steps of a caller-supplied action tape without a frame (mg_play), step + traces + sums per lane in one launch
 //
 // The launches of a step as shipped:
 //   ONE launch for handles with one option set, in every observation format (mortar_step_raster_kernel: the step's workgroups lead the raster's grid and a frame waits for its own
@@ -37,6 +38,7 @@
 #include "mg_mortar_one_launch.hpp"
 #include "mg_mortar_expert.hpp"
 #include "mg_mortar_advance.hpp"
+#include "mg_mortar_play.hpp"
 
 namespace mg {
 using namespace v1;  // raster generation 1 (see mg_raster_v1.hpp)
@@ -324,6 +326,27 @@ class MortarFamily : public Family {
             const MortarAdvanceArgs aa{k, t0 == 0 ? 1 : 0, v.eps, v.seed, v.step0 + (uint64_t)t0, v.actions, v.out};
             with_bool(sets_.per_set(), [&](auto PS) {
                 launch_checked(mortar_advance_kernel<decltype(PS)::value>, dim3((n_ + 255) / 256), dim3(256), 0, s, sa, aa);
+            });
+        }
+        return true;
+    }
+
+    // mg_play inside ONE launch per ADVANCE_MAX_STEPS steps (mg_mortar_play.hpp); lab build, MEMGYM_MORTAR_PLAY_FUSE=0: the loop form of mg_api.hip -- headless
+    // (masked) step and accumulate launch per step -- for A/B measurements (tools/play_bench.py flips it between calls of one process: read at every call)
+    bool play(const PlayArgs& v, hipStream_t s) override {
+        if (!lab_flag("MEMGYM_MORTAR_PLAY_FUSE", true)) return false;
+        if (dirty_) throw std::runtime_error("options that change geometry need a reset before the next step");
+        sets_.upload(s);
+        const int row = n_ * action_dim();
+        for (int t0 = 0; t0 < v.steps; t0 += ADVANCE_MAX_STEPS) {
+            const int k = v.steps - t0 < ADVANCE_MAX_STEPS ? v.steps - t0 : ADVANCE_MAX_STEPS;
+            const MortarStepArgs sa{P_, n_, io(), v.tape + (size_t)t0 * (size_t)row, v.reward, v.done, gt_dim() ? v.gt : nullptr, v.info, v.episode ? 0 : 1,
+                                    handover_.p, nullptr};
+            const MortarPlayArgs pa{k, t0 == 0 ? 1 : 0, t0 + k == v.steps ? 1 : 0, v.episode, row, v.active, v.alive,
+                                    v.reward_trace ? v.reward_trace + (size_t)t0 * (size_t)n_ : nullptr,
+                                    v.done_trace ? v.done_trace + (size_t)t0 * (size_t)n_ : nullptr, v.played, v.out};
+            with_bool(sets_.per_set(), [&](auto PS) {
+                launch_checked(mortar_play_kernel<decltype(PS)::value>, dim3((n_ + 255) / 256), dim3(256), 0, s, sa, pa);
             });
         }
         return true;

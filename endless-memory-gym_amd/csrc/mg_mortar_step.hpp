@@ -160,7 +160,7 @@ __global__ __launch_bounds__(256) void mortar_reset_kernel(MortarParams P0, int 
 // ORDERED: every store of the lane in front of the hand-over word is complete before the word leaves (see there).
 template <bool FUSED, bool CLAIM = false, bool PS = false, bool FINAL = false, bool ORDERED = false>
 __device__ __forceinline__ void mortar_step_body(int i, const MortarStepArgs& a, uint32_t epoch, uint32_t* claim_word = nullptr,
-                                                 uint32_t ticket = 0u) {
+                                                 uint32_t ticket = 0u, const int32_t* actions_row = nullptr) {
     uint32_t claimed_by = 0u;
     if constexpr (CLAIM) {
         claimed_by = ticket + 1u;  // lanes other than the wave's first: any value but the ticket
@@ -169,7 +169,7 @@ __device__ __forceinline__ void mortar_step_body(int i, const MortarStepArgs& a,
     }
     const MortarIO& io = a.io;
     const MortarParams& P = PS ? io.sets[set_index(io.set_of, i)] : a.P;  // (PS: per-instance option sets)
-    const int32_t* const actions = a.actions;
+    const int32_t* const actions = actions_row ? actions_row : a.actions;  // (actions_row: mortar_play_kernel, row t of its tape)
     float* const reward_out = a.reward_out;
     uint8_t* const done_out = a.done_out;
     float* const gt = a.gt;

@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("MEMGYM_HIP_LIB", os.path.join(PKG_ROOT, "lib", "libme
 
 MG_INFO_SLOTS = 8
 MG_MAX_OPTION_SETS = 8
+MG_PLAY_THROUGH, MG_PLAY_EPISODE = 0, 1  # include/memgym.h: mg_play's modes
 
 
 class InfoBuffers(C.Structure):
@@ -96,6 +97,9 @@ def _load():
         L.mg_expert_actions.argtypes = [C.c_void_p, C.c_double, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
     if hasattr(L, "mg_advance"):  # (absent from the older builds tools/ A/B against through MEMGYM_HIP_LIB)
         L.mg_advance.argtypes = [C.c_void_p, C.c_int32, C.c_double, C.c_uint64, C.c_uint64, C.c_void_p, C.POINTER(AdvanceOut), C.c_void_p]
+    if hasattr(L, "mg_play"):  # (absent from the older builds tools/ A/B against through MEMGYM_HIP_LIB)
+        L.mg_play.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                              C.POINTER(AdvanceOut), C.c_void_p]
     if hasattr(L, "mg_save_instances"):  # (absent from the older builds tools/ A/B against through MEMGYM_HIP_LIB)
         L.mg_instance_bytes.argtypes = [C.c_void_p]
         L.mg_instance_bytes.restype = C.c_size_t

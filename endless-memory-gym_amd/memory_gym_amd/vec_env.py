@@ -318,6 +318,7 @@ class VecMemoryGym:
         self._stale = False    # step(render=False) / advance(render=False) since the last call that wrote every row: `obs` holds old bytes
         self._copy_snap = None  # copy_instances(): the scratch snapshot, kept from call to call
         self._adv = None       # advance(): the sums' tensors and the mg_advance_out over them, made at the first call
+        self._play = None      # play(): the sums' tensors, the mg_advance_out over them and the traces per K, made at the first call
         # `truncation` is always False in the reference; on_capacity="truncate": True where the episode ended on a capacity of this build
         self._truncated = self.capacity_u8.view(torch.bool) if self.capacity_u8 is not None else torch.zeros(N, dtype=torch.bool, device=dev)
         self._n_actions = self.num_envs * self.action_dim
@@ -593,6 +594,79 @@ class VecMemoryGym:
         if self._err.value & ~self._tolerated:
             self.check_errors()
         return (self.redraw() if render else None), (dict(self._adv[0]) if stats else None)
+
+    def _sum_tensors(self):
+        """the [N] tensors of advance()'s / play()'s stats and the mg_advance_out over them"""
+        N, dev = self.num_envs, self.device
+        t = {"reward": torch.zeros(N, dtype=torch.float64, device=dev), "episodes": torch.zeros(N, dtype=torch.int32, device=dev),
+             "episode_reward": torch.zeros(N, dtype=torch.float64, device=dev), "episode_length": torch.zeros(N, dtype=torch.int64, device=dev)}
+        out = _native.AdvanceOut()
+        out.struct_size = C.sizeof(_native.AdvanceOut)
+        out.reward_sum_dev, out.episodes_dev = t["reward"].data_ptr(), t["episodes"].data_ptr()
+        out.ep_reward_sum_dev, out.ep_length_sum_dev = t["episode_reward"].data_ptr(), t["episode_length"].data_ptr()
+        for k, nm in enumerate(self.info_names):
+            t[nm] = torch.zeros(N, dtype=torch.float64, device=dev)
+            out.aux_sum_dev[k] = t[nm].data_ptr()
+        return t, out
+
+    def play(self, actions, until_done=False, mask=None, render=True, stats=True, trace=False):
+        """K steps of YOUR OWN action sequences without a frame (include/memgym.h: mg_play) -- what advance() is for the scripted teacher: random
+        shooting from a saved state (save_instances / load_instances), replaying demonstrations, counterfactual probes, stored tapes of one episode
+        per seed.  actions: anything torch.as_tensor takes, of shape [K, N] (Discrete ids) or [K, N, 2] (MultiDiscrete ids); row t is what step()
+        takes at step t.  A wrong shape raises ValueError before anything is stepped.
+        until_done=False: state, random streams and error bits afterwards are those after `for t: step(actions[t], render=False)` with auto-reset,
+        whatever `autoreset` says.  until_done=True: every instance plays until ITS episode ends, is then left alone and is NOT reset -- the loop
+        `step(actions[t], render=False, mask=alive); alive &= ~done` of a handle with autoreset = False; a finished instance stays in its terminal
+        state (redraw() shows its terminal frame) until you reset it (reset(mask=...)) or load a record into it.
+        mask: as in step(mask=...), the instances that play at all; the others keep state, stream and frame.
+        -> (obs or None, stats).  render=True draws the frame each instance's last step left (redraw()); render=False leaves `obs` stale.
+        stats: the keys of advance() over THIS call's steps plus "steps" (int32 [N]: the steps each instance took); trace=True adds
+        "reward_trace" (float32 [K, N]) and "done_trace" (bool [K, N]), zero where an instance did not step.  The tensors are kept per handle
+        (the traces per K) and overwritten by the next call; stats=False, trace=False returns None in their place.  Nothing synchronises; the
+        handle's first call allocates scratch and is refused inside a capture (call it once eagerly, with the K and the trace setting the capture
+        will use, so that the stats tensors exist too); every later one is capturable (tape and mask are read at replay).  The five Mortar Mayhem ids run
+        the whole loop inside one launch per 1,024 steps; the other five take it launch by launch."""
+        a = actions
+        if not (isinstance(a, torch.Tensor) and a.dtype == torch.int32 and a.device == self.device and a.is_contiguous()):
+            a = a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a))
+            a = a.to(device=self.device, dtype=torch.int32).contiguous()
+        want = (self.num_envs,) if self.action_dim == 1 else (self.num_envs, 2)
+        if a.dim() != len(want) + 1 or tuple(a.shape[1:]) != want or a.shape[0] < 1:
+            raise ValueError("play(actions): the tape must have shape [K, %s] with K >= 1, got %s" % (", ".join(str(x) for x in want), tuple(a.shape)))
+        K = int(a.shape[0])
+        m = None
+        if mask is not None:
+            m = mask if isinstance(mask, torch.Tensor) else torch.as_tensor(mask)
+            if m.numel() != self.num_envs or m.dim() != 1:
+                raise ValueError("play(mask=...): the mask must have shape [%d], got %s" % (self.num_envs, tuple(m.shape)))
+            if m.dtype == torch.bool and m.device == self.device and m.is_contiguous():
+                m = m.view(torch.uint8)  # (the same bytes: True is 1)
+            elif not (m.dtype == torch.uint8 and m.device == self.device and m.is_contiguous()):
+                m = (m != 0).to(device=self.device, dtype=torch.uint8).contiguous()
+        if self._play is None:
+            t, out = self._sum_tensors()
+            t["steps"] = torch.zeros(self.num_envs, dtype=torch.int32, device=self.device)
+            self._play = (t, out, {})
+        sums, out, traces = self._play
+        if trace and K not in traces:
+            traces[K] = (torch.zeros((K, self.num_envs), dtype=torch.float32, device=self.device),
+                         torch.zeros((K, self.num_envs), dtype=torch.uint8, device=self.device))
+        rt, dt = traces[K] if trace else (None, None)
+        with torch.cuda.device(self.device):
+            _native.check(_native.LIB.mg_play(self._h, a.data_ptr(), K, _native.MG_PLAY_EPISODE if until_done else _native.MG_PLAY_THROUGH,
+                                              None if m is None else m.data_ptr(), None if rt is None else rt.data_ptr(),
+                                              None if dt is None else dt.data_ptr(), sums["steps"].data_ptr() if stats else None, self._p_gt,
+                                              C.byref(out) if stats else None, self._stream()), "mg_play")
+            if self.gt64 is not None:
+                _native.check(_native.LIB.mg_ground_truth64(self._h, self.gt64.data_ptr(), self._stream()), "mg_ground_truth64")
+        self._stale = True
+        _native.LIB.mg_peek_errors(self._h, self._p_err)  # host-mapped word: no synchronisation
+        if self._err.value & ~self._tolerated:
+            self.check_errors()
+        st = dict(sums) if stats else ({} if trace else None)
+        if trace:
+            st["reward_trace"], st["done_trace"] = rt, dt.view(torch.bool)
+        return (self.redraw() if render else None), st
 
     def expert_actions(self, eps=0.0, seed=0, step=None, out=None):
         """The scripted teacher (include/memgym.h: mg_expert_actions): for every instance the action the CPU oracle's expert hook gives

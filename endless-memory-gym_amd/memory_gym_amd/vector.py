@@ -107,6 +107,12 @@ class GymnasiumVectorEnv(_Base):
         obs, st = self.env.advance(steps, eps=eps, seed=seed, step=step, render=render, stats=stats)
         return (None if obs is None else self._host(obs)), (None if st is None else self._host(st))
 
+    def play(self, actions, until_done=False, mask=None, render=True, stats=True, trace=False):
+        """K steps of caller-supplied action sequences without a frame (VecMemoryGym.play) -> (obs or None, stats); numpy with as_numpy.
+        Episodes that end inside the call are NOT reported as `final_observation` / `final_info`: they are counted and summed in `stats`."""
+        obs, st = self.env.play(actions, until_done=until_done, mask=mask, render=render, stats=stats, trace=trace)
+        return (None if obs is None else self._host(obs)), (None if st is None else self._host(st))
+
     def save_instances(self, idx=None, out=None):
         """VecMemoryGym.save_instances: single instances to device memory -> InstanceSnapshot."""
         return self.env.save_instances(idx=idx, out=out)

@@ -290,6 +290,46 @@ typedef struct mg_advance_out {      /* all device arrays [num_envs], any may be
 int mg_advance(mg_env* env, int32_t steps, double eps, uint64_t seed, uint64_t step0,
                float* gt_dev, const mg_advance_out* out, void* stream);
 
+/* `steps` steps of a CALLER-SUPPLIED action tape WITHOUT A FRAME: what mg_advance is for the library's teacher, for the caller's own action sequences --
+ * planning by random shooting from a saved state (mg_save_instances / mg_load_instances), replaying recorded demonstrations, counterfactual probes,
+ * evaluating stored tapes of one episode per seed.
+ *   tape_dev          int32 [steps][num_envs] (Discrete ids) or [steps][num_envs][2] (MultiDiscrete ids): step-major, row t is what mg_step takes as actions_dev
+ *   mode              MG_PLAY_THROUGH: auto-reset, an instance that ends an episode goes on into the next one, like mg_advance
+ *                     MG_PLAY_EPISODE: every instance plays until ITS episode ends, is then left alone and is NOT reset
+ *   active_dev        uint8 [num_envs] or NULL (= everybody): the instances that play at all; read by the launches, never by the host
+ *   reward_trace_dev  float32 [steps][num_envs] or NULL      done_trace_dev  uint8 [steps][num_envs] or NULL
+ *   steps_played_dev  int32 [num_envs] or NULL: the steps each instance took in this call
+ *   sums              mg_advance_out, with the struct-size rules of mg_advance; OVERWRITTEN with this call's sums; or NULL
+ *   gt_dev            as in mg_step_masked: rows of the instances that stepped hold the ground truth after their last step; or NULL
+ * DEFINITION: state, PCG64 streams, frame descriptors, ground truth, error bits, traces and sums afterwards equal bit for bit those after
+ *     alive[i] = active_dev ? active_dev[i] != 0 : 1;  played[i] = 0
+ *     for t in 0 .. steps-1:
+ *         mg_step_masked(env, tape_dev + t * row, M, NULL, R_t, D_t, gt_dev, info, mode == MG_PLAY_THROUGH, stream)
+ *                 M = alive; M = NULL (the plain headless mg_step) when active_dev == NULL and mode == MG_PLAY_THROUGH
+ *         sums += step t's rows: the additions of mg_advance, in the same order
+ *         played[i] += alive[i]
+ *         if mode == MG_PLAY_EPISODE: alive[i] &= !D_t[i]
+ * where R_t / D_t are row t of the traces (scratch where a trace is NULL) and `info` the handle's scratch rows (reward64, the episode record, the named
+ * aux slots).  What follows from mg_step_masked's own definition: an instance that is not alive keeps its state, its stream and its descriptor; its
+ * trace entries are 0 and its tape entries are not interpreted; an instance that never was alive has sums and steps_played of 0.  In MG_PLAY_EPISODE a
+ * finished instance stays in the terminal state mg_step with autoreset == 0 leaves: mg_render shows its terminal frame, and the caller resets it (a
+ * masked mg_reset) or loads a record into it before it is stepped again.  mg_render draws, for every instance, the frame its last step left.
+ * Nothing synchronises.  The scratch (an alive byte, one reward / done row and the episode-record rows: about 40 bytes per instance) is allocated AT THE
+ * HANDLE'S FIRST mg_play, which therefore cannot be captured; every later call allocates nothing and can be captured into a HIP graph -- tape and mask are
+ * read from memory at replay, steps and mode are the captured values.  MG_STATE_VERSION is unchanged: no state is added.  Per-instance option sets,
+ * mg_set_capacity and every observation format work as they do for the calls of the definition.
+ * The five Mortar Mayhem ids run the loop INSIDE one launch (mortar_play_kernel: a lane per instance reads its tape entry, steps, stores its trace
+ * entries and keeps sums and step count in registers; a MG_PLAY_EPISODE lane leaves the loop at its own end; at most 1,024 steps per launch, a longer call
+ * is split); mg_debug_counter "play_fused_steps" counts the steps of such calls, which are no "headless_steps".  The other five ids take the loop above on
+ * the host -- the headless (masked) step and one small accumulate launch per step -- and count as "headless_steps" / "masked_steps".
+ * Errors (-1): before the first mg_reset / mg_set_state; steps < 1; tape_dev NULL; a mode other than the two; a bad sums->struct_size; a geometry
+ * option set since the last reset. */
+#define MG_PLAY_THROUGH 0
+#define MG_PLAY_EPISODE 1
+int mg_play(mg_env* env, const int32_t* tape_dev, int32_t steps, int mode, const uint8_t* active_dev,
+            float* reward_trace_dev, uint8_t* done_trace_dev, int32_t* steps_played_dev,
+            float* gt_dev, const mg_advance_out* sums, void* stream);
+
 /* The single-instance fast path (BASELINE config C1: gym.make(id), one instance, numpy in / numpy out -- the reference's own loop,
  * /root/reference/bench.py:12-30).  For a handle with num_envs == 1, mg_single_open allocates every per-call buffer in pinned,
  * device-mapped HOST memory and returns the host addresses: the kernels read the action from it and store observation, reward,
@@ -493,7 +533,9 @@ int mg_enable_peer_access(int device, int peer_device);
  * (mg_info_buffers.final_obs_dev, autoreset) on the generic path -- a step without auto-reset, a copy of the finished rows, a masked reset --
  * instead of inside the step's own launches, counted on the host.  "headless_steps" (every id): headless steps of this handle -- mg_step calls
  * with obs_dev == NULL and the steps mg_advance took through its loop form; "advance_fused_steps" (every id; only the mortar family has the
- * form): steps mg_advance took inside mortar_advance_kernel.  Both counted on the host.  "instance_saves" / "instance_loads" (every id):
+ * form): steps mg_advance took inside mortar_advance_kernel.  Both counted on the host.  "play_fused_steps" (every id; only the mortar family
+ * has the form): steps mg_play took inside mortar_play_kernel; the steps of its loop form count as "headless_steps" and, where a mask applied,
+ * "masked_steps".  "instance_saves" / "instance_loads" (every id):
  * mg_save_instances / mg_load_instances calls of this handle with count > 0, counted on the host.  Unknown name: -1.  Synchronous. */
 int mg_debug_counter(mg_env* env, const char* name, int64_t* value);
 
