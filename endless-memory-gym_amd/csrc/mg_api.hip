@@ -7,6 +7,7 @@
 
 #include "mg_expert.hpp"
 #include "mg_family.hpp"
+#include "mg_frame_records.hpp"
 #include "mg_instances.hpp"
 #include "mg_lab.hpp"
 
@@ -51,6 +52,7 @@ struct mg_env {
     // from its claim launch to the launches behind it, allocated at the handle's first load (include/memgym.h)
     uint64_t serial = 0;
     int64_t instance_saves = 0, instance_loads = 0;
+    int64_t frame_saves = 0, frame_draws = 0;  // mg_debug_counter: mg_save_frames / mg_draw_frames calls with count > 0
     struct Instances {
         bool ready = false;
         mg::DevArray<int32_t> claim;  // [num_envs] the entry of the current load that holds the instance
@@ -669,6 +671,65 @@ int mg_load_instances(mg_env* env, const int32_t* idx_dev, const int32_t* rec_of
     });
 }
 
+}  // extern "C"
+// mg_save_frames: record j <- descriptor row of instance idx[j] (idx == NULL: instance j).  A lane moves one 16-byte vector; a descriptor is 1, 4 or 8 of
+// them.  An entry < 0 is skipped, one >= num_envs is skipped and flagged (once, by the lane of its first vector); a skipped entry's record is not written.
+__global__ __launch_bounds__(256) void frame_rows_save_kernel(const row_vec16* __restrict__ descs, int vec_per_row, const int32_t* __restrict__ idx, int count,
+                                                              int num_envs, row_vec16* __restrict__ rec, int* err) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t j = t / vec_per_row;
+    if (j >= count) return;
+    const int q = (int)(t - j * vec_per_row);
+    const int i = idx ? idx[j] : (int)j;
+    if (i < 0) return;
+    if (i >= num_envs) {
+        if (q == 0) __hip_atomic_fetch_or(err, mg::ERR_FRAME_INDEX, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        return;
+    }
+    rec[j * vec_per_row + q] = descs[(int64_t)i * vec_per_row + q];
+}
+extern "C" {
+
+// ---- frame records (include/memgym.h: mg_save_frames / mg_draw_frames; mg_frame_records.hpp and the gather forms of the two raster skeletons) ----
+size_t mg_frame_record_bytes(const mg_env* env) {
+    if (!env || !env->fam) return 0;
+    return env->fam->frame_rows().second;
+}
+
+uint64_t mg_frame_layout(const mg_env* env) {
+    if (!env || !env->fam) return 0;
+    return mg::frame_layout_value(env->serial, env->fam->geometry_generation(), env->fam->frame_generation());
+}
+
+int mg_save_frames(mg_env* env, const int32_t* idx_dev, int32_t count, void* rec_dev, void* stream) {
+    return guarded(env, [&] {
+        const std::string who = "mg_save_frames: ";
+        if (!env->started) throw std::runtime_error(who + "before the first mg_reset / mg_set_state");
+        if (const char* no = mg::frame_save_refusal(count, rec_dev)) throw std::runtime_error(who + no);
+        if (env->fam->geometry_dirty()) throw std::runtime_error(who + "options that change geometry need a reset first");
+        if (count == 0) return;
+        const std::pair<const void*, size_t> rows = env->fam->frame_rows();
+        const int vec_per_row = (int)(rows.second / 16);
+        const int64_t lanes = (int64_t)count * vec_per_row;
+        hipLaunchKernelGGL(frame_rows_save_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const row_vec16*)rows.first,
+                           vec_per_row, idx_dev, count, env->num_envs, (row_vec16*)rec_dev, env->fam->error_word());
+        MG_HIP(hipGetLastError());
+        ++env->frame_saves;
+    });
+}
+
+int mg_draw_frames(mg_env* env, const void* rec_dev, int64_t n_records, const int32_t* pick_dev, int64_t count, int format, void* obs_dev, void* stream) {
+    return guarded(env, [&] {
+        const std::string who = "mg_draw_frames: ";
+        if (!env->started) throw std::runtime_error(who + "before the first mg_reset / mg_set_state");
+        if (const char* no = mg::frame_draw_refusal(rec_dev, n_records, pick_dev != nullptr, count, format, obs_dev)) throw std::runtime_error(who + no);
+        if (env->fam->geometry_dirty()) throw std::runtime_error(who + "options that change geometry need a reset first");
+        if (count == 0) return;
+        env->fam->draw_records(rec_dev, (int)n_records, pick_dev, (int)count, format, obs_dev, (hipStream_t)stream);
+        ++env->frame_draws;
+    });
+}
+
 int mg_ground_truth64(mg_env* env, double* gt64_dev, void* stream) {
     return guarded(env, [&] {
         if (!env->fam->gt_dim()) return;
@@ -918,6 +979,10 @@ int mg_debug_counter(mg_env* env, const char* name, int64_t* value) {
         }
         if (std::string(name) == "instance_saves" || std::string(name) == "instance_loads") {  // every id: counted in this file
             *value = std::string(name) == "instance_saves" ? env->instance_saves : env->instance_loads;
+            return;
+        }
+        if (std::string(name) == "frame_saves" || std::string(name) == "frame_draws") {  // every id: counted in this file
+            *value = std::string(name) == "frame_saves" ? env->frame_saves : env->frame_draws;
             return;
         }
         if (std::string(name) == "masked_steps") {  // every id: counted in this file

@@ -293,6 +293,12 @@ class Family {
     virtual bool play(const PlayArgs& /*v*/, hipStream_t /*s*/) { return false; }
     // rasterise the CURRENT frame descriptors of the instances with only[i] != 0 into `obs` (others untouched)
     virtual void raster_only(void* obs, const uint8_t* only, hipStream_t s) = 0;
+    // mg_save_frames / mg_draw_frames (include/memgym.h; mg_frame_records.hpp).  frame_rows(): the frame descriptor array raster_only() draws from, as
+    // (device pointer, bytes per instance: sizeof the family's Desc).  draw_records(): row j of `obs` <- the frame of records[pick[j]] (pick == NULL:
+    // records[j]), j < count, in format `fmt` -- the gather form of the family's raster launch with the composer raster_only() picks and the handle's
+    // atlas; nothing of the handle is written.  The arguments have passed frame_draw_refusal().
+    virtual std::pair<const void*, size_t> frame_rows() = 0;
+    virtual void draw_records(const void* records, int n_records, const int32_t* pick, int count, int fmt, void* obs, hipStream_t s) = 0;
     // true: step(..., autoreset = 1) with info->final_obs_dev set keeps the terminal observations ITSELF (the frame workgroup of a finishing
     // instance draws the terminal frame into final_obs_dev, then the reset frame into obs); false: mg_step takes the generic path (a step
     // without auto-reset, the terminal rows copied, a masked reset).  Asked once per call, on the stream of the call.
@@ -309,6 +315,7 @@ class Family {
     virtual void before_instance_save(hipStream_t /*s*/) {}
     bool geometry_dirty() const { return dirty_; }                   // a geometry option was set since the last reset
     uint64_t geometry_generation() const { return geom_gen_; }       // rebuilds of the geometry so far (mg_instance_layout)
+    uint64_t frame_generation() const { return frame_gen_; }         // what else makes a stored frame descriptor draw differently (mg_frame_layout)
     // called by mg_set_state after the blobs were restored: the instances now carry seeded RNG streams
     virtual void on_state_loaded() { seeded_ = true; }
     // called before anything looks at the state from outside (mg_get_state, mg_debug_rng, mg_render_debug): work a family has
@@ -386,6 +393,8 @@ class Family {
     bool dirty_ = true;    // a geometry option changed: the next reset rebuilds atlases and constants first
     bool seeded_ = false;  // some reset carried seeds (or a state was loaded)
     uint64_t geom_gen_ = 0;  // counts what makes earlier instance records invalid: every rebuild(), mg_set_capacity, a new vector-observation binding
+    uint64_t frame_gen_ = 0;  // counts what makes earlier FRAME records invalid without a rebuild: a change of the composer raster_only() picks, of the atlas or of a
+                              // template (the spotlight family's ordered_holes going from 0 to 1; host-side bookkeeping, no part of the state)
 };
 
 Family* make_mortar(int variant, int num_envs);

@@ -34,6 +34,7 @@
 #include "mg_stamps.hpp"
 #include "mg_mortar_types.hpp"
 #include "mg_mortar_compose.hpp"
+#include "mg_raster_gather_v1.hpp"
 #include "mg_mortar_step.hpp"
 #include "mg_mortar_one_launch.hpp"
 #include "mg_mortar_expert.hpp"
@@ -483,6 +484,11 @@ class MortarFamily : public Family {
 
     void raster_only(void* obs, const uint8_t* only, hipStream_t s) override {
         launch_raster<MortarComposer>(desc_.p, atlas_->dev(), obs, obs_format, n_, s, only);
+        check_launch();
+    }
+    std::pair<const void*, size_t> frame_rows() override { return {desc_.p, sizeof(MortarDesc)}; }
+    void draw_records(const void* records, int n_records, const int32_t* pick, int count, int fmt, void* obs, hipStream_t s) override {
+        launch_raster_gather<MortarComposer>((const MortarDesc*)records, atlas_->dev(), obs, fmt, n_records, pick, count, err_.dev, s);
         check_launch();
     }
     // (the one-launch step keeps terminal observations itself: the conditions under which step() takes that launch; lab

@@ -38,6 +38,7 @@
 #include "mg_stamps.hpp"
 #include "mg_mystery_types.hpp"
 #include "mg_mystery_compose.hpp"
+#include "mg_raster_gather_v1.hpp"
 #include "mg_mystery_path.hpp"
 #include "mg_mystery_finite.hpp"
 #include "mg_mystery_endless.hpp"
@@ -180,6 +181,15 @@ class MysteryFamily : public Family {
     void raster_only(void* obs, const uint8_t* only, hipStream_t s) override {
         if (big_sprites_) launch_raster<MysteryBigComposer>(desc_.p, atlas_->dev(), obs, obs_format, n_, s, only);
         else launch_raster<MysteryComposer>(desc_.p, atlas_->dev(), obs, obs_format, n_, s, only);
+        check_launch();
+    }
+    // (Endless: the descriptor rows are complete once the step's launches have run -- a queued instance's row is rewritten by the wave that serves its entry,
+    // emp_serve_entry -- so a save reads them as mg_render does, behind nothing but the stream's order; owed segments are no part of a descriptor)
+    std::pair<const void*, size_t> frame_rows() override { return {desc_.p, sizeof(MysteryDesc)}; }
+    void draw_records(const void* records, int n_records, const int32_t* pick, int count, int fmt, void* obs, hipStream_t s) override {
+        const MysteryDesc* rec = (const MysteryDesc*)records;
+        if (big_sprites_) launch_raster_gather<MysteryBigComposer>(rec, atlas_->dev(), obs, fmt, n_records, pick, count, err_.dev, s);
+        else launch_raster_gather<MysteryComposer>(rec, atlas_->dev(), obs, fmt, n_records, pick, count, err_.dev, s);
         check_launch();
     }
 

@@ -1,0 +1,50 @@
+// mg_raster_gather_v1.hpp -- the GATHER form of raster generation 1 (mg_raster_v1.hpp; mortar, Mystery Path): mg_draw_frames (include/memgym.h).
+// The dense kernel draws frame i of the handle from descriptor i; this one draws OUTPUT ROW j from the caller's record pick[j] (pick == NULL: record j),
+// for any number of rows.  Same persistent workgroups, same composers, same stream-out (store_frame, plain stores); what is new per frame is one
+// workgroup-uniform load of the pick in front of the descriptor and its range check.  A kernel of its own: the dense launches are the measured ones
+// and stay as they are.
+#pragma once
+#include "mg_frame_records.hpp"
+#include "mg_raster_v1.hpp"
+
+namespace mg {
+namespace v1 {
+
+// records: n_records descriptors as mg_save_frames left them (no kernel writes them while this one runs); pick: `count` record indices or NULL.
+// A pick outside 0 .. n_records-1 leaves its row untouched and raises ERR_FRAME_INDEX; a record the composer skips (a masked reset's "leave the frame
+// untouched") leaves its row untouched as well.  Row offsets are 64-bit (store_frame multiplies as size_t); j and the pick are 32-bit.
+template <class Composer, int FMT>
+__global__ __launch_bounds__(256, 7) void raster_gather_kernel(const typename Composer::Desc* __restrict__ records, RasterAtlas A, void* __restrict__ obs,
+                                                            int n_records, const int32_t* __restrict__ pick, int count, int* err) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const RasterCtx R = make_ctx(smem, A);
+    const int tid = threadIdx.x;
+    for (int j = blockIdx.x; j < count; j += gridDim.x) {
+        const int r = pick ? __builtin_amdgcn_readfirstlane(pick[j]) : j;  // workgroup-uniform: the descriptor pointer stays uniform (scalar loads)
+        if ((unsigned)r >= (unsigned)n_records) {
+            if (tid == 0) __hip_atomic_fetch_or(err, ERR_FRAME_INDEX, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            continue;
+        }
+        const typename Composer::Desc* d = records + r;
+        if (Composer::skip(d)) continue;
+        Composer::compose(d, R);
+        __syncthreads();
+        store_frame<FMT, false>(smem, obs, j, tid);
+        __syncthreads();  // the LDS frame is reused by the next iteration
+    }
+}
+
+// grid and LDS request: launch_raster's for a launch of `count` frames
+template <class Composer>
+inline void launch_raster_gather(const typename Composer::Desc* records, const RasterAtlas& atlas, void* obs, int fmt, int n_records, const int32_t* pick,
+                                 int count, int* err, hipStream_t s) {
+    const int forced_lds = lab_raster_lds(RASTER_LDS);
+    const int lds = forced_lds ? forced_lds : RASTER_LDS;
+    const dim3 grid(frames_grid(count));
+    with_obs_format(fmt, [&](auto F) {
+        launch(raster_gather_kernel<Composer, decltype(F)::value>, grid, dim3(256), lds, s, records, atlas, obs, n_records, pick, count, err);
+    });
+}
+
+}  // namespace v1
+}  // namespace mg

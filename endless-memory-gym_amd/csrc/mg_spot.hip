@@ -39,6 +39,7 @@
 #include "mg_option_sets.hpp"
 #include "mg_spot_types.hpp"
 #include "mg_spot_compose.hpp"
+#include "mg_raster_gather.hpp"
 #include "mg_spot_sampler.hpp"
 #include "mg_spot_logic.hpp"
 #include "mg_spot_serve.hpp"
@@ -207,6 +208,7 @@ class SpotFamily : public Family {
             P.black_background = A.flag();
             if (P.black_background && !P_.ordered_holes) {  // from now on spotlights may carry a border (sticky, kept in the state)
                 P_.ordered_holes = 1;
+                ++frame_gen_;  // (the border composer draws from now on: mg_frame_layout)
                 const int one = 1;
                 MG_HIP(hipMemcpy(flags_.p, &one, sizeof(int), hipMemcpyHostToDevice));
             }
@@ -390,6 +392,7 @@ class SpotFamily : public Family {
         seeded_ = true;
         int f = 0;
         MG_HIP(hipMemcpy(&f, flags_.p, sizeof(int), hipMemcpyDeviceToHost));
+        if (f && !P_.ordered_holes) ++frame_gen_;  // (as in set_option_set: the border composer draws from now on)
         if (f) P_.ordered_holes = 1;
         if (!P_.endless) {  // the exit generations the restored instances refer to; the atlas follows
             std::vector<double> hist(1 + EXIT_GENS, 0.0);
@@ -551,6 +554,13 @@ class SpotFamily : public Family {
 
     void raster_only(void* obs, const uint8_t* only, hipStream_t s) override {
         with_bool(P_.ordered_holes, [&](auto BO) { launch_raster<SpotComposerT<decltype(BO)::value>>(desc_.p, atlas_->dev(), obs, obs_format, n_, s, only); });
+        check_launch();
+    }
+    std::pair<const void*, size_t> frame_rows() override { return {desc_.p, sizeof(SpotDesc)}; }
+    void draw_records(const void* records, int n_records, const int32_t* pick, int count, int fmt, void* obs, hipStream_t s) override {
+        with_bool(P_.ordered_holes, [&](auto BO) {
+            launch_raster_gather<SpotComposerT<decltype(BO)::value>>((const SpotDesc*)records, atlas_->dev(), obs, fmt, n_records, pick, count, err_.dev, s);
+        });
         check_launch();
     }
 

@@ -107,6 +107,13 @@ def _load():
         L.mg_instance_layout.restype = C.c_uint64
         L.mg_save_instances.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
         L.mg_load_instances.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(L, "mg_save_frames"):  # (absent from the older builds tools/ A/B against through MEMGYM_HIP_LIB)
+        L.mg_frame_record_bytes.argtypes = [C.c_void_p]
+        L.mg_frame_record_bytes.restype = C.c_size_t
+        L.mg_frame_layout.argtypes = [C.c_void_p]
+        L.mg_frame_layout.restype = C.c_uint64
+        L.mg_save_frames.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+        L.mg_draw_frames.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]
     L.mg_enable_peer_access.argtypes = [C.c_int, C.c_int]
     L.mg_debug_rng.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
     L.mg_debug_set_rng.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]

@@ -194,8 +194,70 @@ def check_instance_save(instance_bytes, num_envs, idx=None, out=None, device=Non
     return idx, k
 
 
+class FrameRecords:
+    """What VecMemoryGym.save_frames returns: `records`, a uint8 tensor [..., frame_record_bytes] on the handle's device (one row = the frame descriptor
+    of one instance at one moment: 16 / 64 / 128 bytes, its layout private), and `layout`, the value of mg_frame_layout when it was taken (unique to the
+    handle, new whenever a stored descriptor would draw differently: draw_frames refuses records whose layout is not the handle's current one).  A
+    trainer that fills a [T, N, bytes] store step by step (save_frames(out=store[t])) wraps the whole store: FrameRecords(store, env.frame_layout())."""
+    __slots__ = ("records", "layout")
+
+    def __init__(self, records, layout):
+        self.records, self.layout = records, int(layout)
+
+    @property
+    def count(self):
+        return int(self.records.numel() // self.records.shape[-1])
+
+
+def _frame_rows(what, name, t, record_bytes):
+    """A tensor of frame records -> its view [n, record_bytes]; ValueError unless it is a contiguous uint8 tensor whose last dimension is one record."""
+    if not (isinstance(t, torch.Tensor) and t.dtype == torch.uint8 and t.dim() >= 2 and t.shape[-1] == int(record_bytes) and t.is_contiguous()):
+        raise ValueError("%s: %s must be a contiguous uint8 tensor [..., %d]" % (what, name, int(record_bytes)))
+    return t.view(-1, int(record_bytes))
+
+
+def check_frame_save(record_bytes, num_envs, idx=None, out=None, device=None):
+    """The argument checks of save_frames, which need no handle: -> (idx as an int32 tensor or None, number of records, out's records as [k, bytes] or
+    None).  out: a FrameRecords or a plain uint8 tensor [k, record_bytes] -- e.g. the row block store[t] of a [T, N, bytes] store -- contiguous."""
+    what = "save_frames"
+    if idx is not None:
+        idx = _instance_index(what, "idx", idx, device)
+    k = num_envs if idx is None else idx.numel()
+    rows = None
+    if out is not None:
+        rows = _frame_rows(what, "out", out.records if isinstance(out, FrameRecords) else out, record_bytes)
+        if rows.shape[0] != k:
+            raise ValueError("%s: out holds %d records, the call saves %d" % (what, rows.shape[0], k))
+    return idx, k, rows
+
+
+def check_frame_draw(records, layout, record_bytes, pick=None, out=None, obs_format="u8_xyc", device=None):
+    """The argument checks of draw_frames, which need no handle: -> (records as [n, bytes], pick as an int32 tensor or None, count, (dtype, shape) of
+    one row).  ValueError for records of another handle or an earlier layout (FrameRecords only: a plain tensor carries none), of the wrong dtype /
+    width / stride, a pick that is no one-dimensional integer tensor, more rows than records without a pick, an unknown format, an `out` of the wrong
+    shape / dtype or one that is not contiguous."""
+    what = "draw_frames"
+    if isinstance(records, FrameRecords):
+        if records.layout != int(layout):
+            raise ValueError("%s: the records (layout 0x%x) were saved from another handle, or before something changed that they would draw differently "
+                             "(layout 0x%x now): frame records are valid for the handle and the atlas they were saved under" % (what, records.layout, int(layout)))
+        records = records.records
+    rows = _frame_rows(what, "records", records, record_bytes)
+    if obs_format not in VecMemoryGym.OBS_FORMATS:
+        raise ValueError("%s: obs_format must be one of %s" % (what, sorted(VecMemoryGym.OBS_FORMATS)))
+    _, dt, shape = VecMemoryGym.OBS_FORMATS[obs_format]
+    if pick is not None:
+        pick = _instance_index(what, "pick", pick, device)
+    count = rows.shape[0] if pick is None else pick.numel()
+    if count > 0 and rows.shape[0] < 1:
+        raise ValueError("%s: no records to draw from" % what)
+    if out is not None and not (isinstance(out, torch.Tensor) and out.dtype == dt and tuple(out.shape) == (count,) + shape and out.is_contiguous()):
+        raise ValueError("%s: out must be a contiguous %s tensor of shape %s" % (what, dt, (count,) + shape))
+    return rows, pick, count, (dt, shape)
+
+
 class VecMemoryGym:
-    metadata = {"render_modes": ["rgb_array", "debug_rgb_array"], "render_fps": 25}
+    metadata ={"render_modes": ["rgb_array", "debug_rgb_array"], "render_fps": 25}
 
     OBS_FORMATS = {"u8_xyc": (0, torch.uint8, (84, 84, 3)), "f32_chw": (1, torch.float32, (3, 84, 84)),
                    "f16_chw": (2, torch.float16, (3, 84, 84)), "bf16_chw": (3, torch.bfloat16, (3, 84, 84)),
@@ -723,6 +785,53 @@ class VecMemoryGym:
             return out
         return InstanceSnapshot(records, self.instance_layout, set_of)
 
+    # ------------------------------------------------------------------ frame records
+    @property
+    def frame_record_bytes(self):
+        return int(_native.LIB.mg_frame_record_bytes(self._h))
+
+    def frame_layout(self):
+        return int(_native.LIB.mg_frame_layout(self._h))
+
+    def save_frames(self, idx=None, out=None):
+        """Keep the CURRENT frames as their descriptors (include/memgym.h: mg_save_frames) -> FrameRecords over a uint8 tensor [k, frame_record_bytes]:
+        16 / 64 / 128 bytes per frame instead of 21,168 and more.  After step(render=False) the records hold the frames the step would have drawn.
+        idx: the instances, an integer tensor / list (None: all, in order); entries < 0 are skipped (their records keep their bytes).  out: a
+        FrameRecords or a uint8 tensor [k, frame_record_bytes] to write into -- a row block store[t] of a larger [T, N, bytes] store, so one store is
+        filled step by step.  One small launch on the current stream; nothing synchronises, nothing of the handle changes."""
+        self._require_started("save_frames")
+        nbytes = self.frame_record_bytes
+        idx, k, rows = check_frame_save(nbytes, self.num_envs, idx, out, self.device)
+        if rows is None:
+            out = rows = torch.empty((k, nbytes), dtype=torch.uint8, device=self.device)
+        if rows.device != self.device or rows.data_ptr() % 16:
+            raise ValueError("save_frames: out must be a 16-byte aligned tensor on %s" % (self.device,))
+        with torch.cuda.device(self.device):
+            _native.check(_native.LIB.mg_save_frames(self._h, None if idx is None else idx.data_ptr(), k, rows.data_ptr(), self._stream()), "mg_save_frames")
+        if isinstance(out, FrameRecords):
+            out.layout = self.frame_layout()
+            return out
+        return FrameRecords(out, self.frame_layout())
+
+    def draw_frames(self, records, pick=None, out=None, obs_format=None):
+        """Draw kept frames (include/memgym.h: mg_draw_frames): row j of the result is the frame of record pick[j] (pick=None: record j), in
+        `obs_format` (default: the handle's) -- bit for bit what `obs` showed when the record was saved, or what a handle of that format would have
+        shown.  records: a FrameRecords (its layout is checked: ValueError if stale, before anything is launched) or a plain uint8 tensor, viewed as
+        [n_records, frame_record_bytes].  pick: an integer tensor / list of any length, duplicates allowed; an entry outside the records leaves its row
+        untouched and raises error bit 512.  out: a contiguous tensor [count] + shape of the format to draw into (a network's input tensor).  One
+        raster launch on the current stream; nothing synchronises, nothing of the handle changes."""
+        self._require_started("draw_frames")
+        fmt = self.obs_format if obs_format is None else obs_format
+        rows, pick, count, (dt, shape) = check_frame_draw(records, self.frame_layout(), self.frame_record_bytes, pick, out, fmt, self.device)
+        if out is None:
+            out = torch.empty((count,) + shape, dtype=dt, device=self.device)
+        if rows.device != self.device or out.device != self.device or rows.data_ptr() % 16 or out.data_ptr() % 16:
+            raise ValueError("draw_frames: records and out must be 16-byte aligned tensors on %s" % (self.device,))
+        with torch.cuda.device(self.device):
+            _native.check(_native.LIB.mg_draw_frames(self._h, rows.data_ptr(), rows.shape[0], None if pick is None else pick.data_ptr(), count,
+                                                     self.OBS_FORMATS[fmt][0], out.data_ptr(), self._stream()), "mg_draw_frames")
+        return out
+
     def _scatter_rows(self, dst, tgt, rows):
         """dst[tgt[j]] = rows[j]; tgt[j] == len(dst) names nobody (a skipped entry).  No host look."""
         ext = torch.cat([dst, dst[:1]])
@@ -938,7 +1047,7 @@ class VecMemoryGym:
                   32: "Endless Mortar Mayhem command list reached its 512-entry capacity (the episode was ended)",
                   64: "a deferred-reset queue overflowed (a previous fused launch did not drain it)",
                   256: "use_exit=False for an instance that never had an exit (the reference raises AttributeError at this reset)",
-                  512: "save_instances / load_instances: an instance or record index out of range (the entry was skipped)"}
+                  512: "save_instances / load_instances / save_frames / draw_frames: an instance or record index out of range (the entry was skipped)"}
 
     def check_errors(self):
         """Raise if a kernel flagged a capacity/failure condition since the last call (synchronises the device).

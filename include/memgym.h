@@ -416,6 +416,46 @@ int mg_save_instances(mg_env* env, const int32_t* idx_dev, int32_t count, void* 
 int mg_load_instances(mg_env* env, const int32_t* idx_dev, const int32_t* rec_of_dev, int32_t count, const void* rec_dev,
                       void* obs_dev, void* stream);
 
+/* FRAME RECORDS: keep a frame as its descriptor and draw it later.  Every frame this library writes is a pure function of the instance's frame
+ * descriptor -- the row the step kernels leave behind: 16 B (Mortar Mayhem ids), 64 B (Mystery Path ids), 128 B (Searing Spotlights ids) -- and the
+ * handle's atlas; the frame itself is 21,168 to 84,672 B.  A trainer steps headless or drawn, keeps each step's descriptor rows in a store of its own and
+ * at training time draws exactly the minibatch rows it wants, in the network's format, straight into its input tensor.
+ *   mg_save_frames   record j <- the CURRENT frame descriptor of instance idx_dev[j]   (idx_dev == NULL: instance j), j = 0 .. count-1
+ *   mg_draw_frames   row j of obs_dev <- the frame of record pick_dev[j]               (pick_dev == NULL: record j, and then count <= n_records)
+ * DEFINITION: let a record be saved from instance i after some call, and let that call have written row i of its observation buffer in format F.  Then
+ * mg_draw_frames(..., F, ...) writes that record's row with exactly those bytes; for any other format it writes the bytes a handle in that format would
+ * have shown.  After a headless step (obs_dev == NULL) the record draws the frame the step would have drawn.  Nothing of the handle's state, streams or
+ * descriptors changes in either call.
+ * mg_save_frames: the index conventions of mg_save_instances -- an entry < 0 is skipped, an entry >= num_envs is skipped and raises error bit 512; a
+ * skipped entry leaves its record untouched.  rec_dev: 16-byte aligned, count * mg_frame_record_bytes bytes; so a row block of a larger [T][N] store is
+ * filled step by step.  One small row-gather launch.  (Endless-MysteryPath-v0: the descriptor rows are complete once the step's launches have run, owed
+ * path segments are no part of them: nothing is flushed and nothing synchronises, exactly as for mg_render.)
+ * mg_draw_frames: count is independent of num_envs -- one frame, or millions; format is any MG_OBS_*, independent of the handle's own (records carry no
+ * format); obs_dev: 16-byte aligned, count rows of that format.  A pick outside 0 .. n_records-1 leaves its row untouched and raises bit 512.  A record
+ * whose descriptor says "leave the frame untouched" -- what a masked mg_reset leaves for the instances it did not reset -- leaves its row untouched, as
+ * mg_render does.  Duplicates in pick_dev are legal.  ONE launch: the gather form of the family's raster kernel (persistent workgroups walk the output
+ * rows, read the pick workgroup-uniformly, compose from the record with the composer mg_render uses, stream the row out; 64-bit row offsets) with the
+ * grid, LDS request and store flavour of a raster launch over `count` frames.
+ * Both calls only enqueue on `stream`, allocate nothing and can be captured into a HIP graph; indices, picks and records are read at replay.
+ * VALIDITY, as for instance records: a record belongs to the handle it was saved from and to the atlas it was saved under.  mg_frame_layout returns a
+ * 64-bit value that is unique to the handle within the process and changes whenever something changes that a stored descriptor would draw differently:
+ * everything that changes mg_instance_layout (a rebuild of the geometry -- this is also where the Mystery Path family chooses between its two composers
+ * by sprite size --, mg_set_capacity, mg_set_state on the spotlight family, a new vector-observation binding) and the spotlight family's switch to its
+ * border composer (black_background set for the first time, or a state loaded that has it).  The sticky hide_chessboard / black_background options
+ * themselves need no new layout: the background template is a field of the descriptor and travels in the record.  The library CANNOT check this -- the
+ * records carry no header: keep the value next to the records and compare before drawing (the Python mirror does); drawing a stale record is undefined
+ * for its row.  mg_frame_record_bytes is sizeof the family's descriptor: 16 / 64 / 128.
+ * OUT OF SCOPE: terminal-observation rows (final_obs_dev and the terminal descriptors behind them); the debug view (mg_render_debug); the MortarMayhemB
+ * ids' vector observation; descriptor traces out of mg_play / mg_advance (their in-launch forms keep no descriptor per step).
+ * mg_debug_counter "frame_saves" / "frame_draws" count the calls with count > 0, on the host.  MG_STATE_VERSION is unchanged: no state is added.
+ * Errors (-1): before the first mg_reset / mg_set_state; a geometry option set since the last reset; a NULL or misaligned rec_dev / obs_dev; count < 0;
+ * n_records < 1 with count > 0; an unknown format; pick_dev == NULL with count > n_records; n_records or count > INT32_MAX. */
+size_t   mg_frame_record_bytes(const mg_env* env);   /* 16 / 64 / 128: sizeof the family's frame descriptor */
+uint64_t mg_frame_layout(const mg_env* env);
+int mg_save_frames(mg_env* env, const int32_t* idx_dev, int32_t count, void* rec_dev, void* stream);
+int mg_draw_frames(mg_env* env, const void* rec_dev, int64_t n_records, const int32_t* pick_dev, int64_t count, int format, void* obs_dev,
+                   void* stream);
+
 /* Measurement hooks (bench.py's roofline leg): mg_set_profiling(env, N) makes every N-th mg_step (N = 1: every step,
  * 0: off) bracket its kernels with hipEvents recorded on the launch stream (a bracketed step costs ~15 us of stream
  * time, hence the sampling).  mg_get_profile(kind) synchronises, returns the summed elapsed milliseconds and the
@@ -436,8 +476,8 @@ int mg_get_profile(mg_env* env, int kind, double* total_ms, int64_t* launches);
  * 256  SearingSpotlights-v0: use_exit = False at the reset of an instance that has never had an exit (the reference raises
  *      AttributeError there, searing_spotlights.py:431-435; with an earlier exit it keeps drawing that one, and so does this
  *      library); no exit was drawn
- * 512  mg_save_instances / mg_load_instances: an instance index >= num_envs, or a record index outside the call's records; the entry was
- *      skipped, nothing else changed
+ * 512  mg_save_instances / mg_load_instances / mg_save_frames / mg_draw_frames: an instance index >= num_envs, or a record index outside the
+ *      call's records; the entry was skipped, nothing else changed
  * 128  reserved (rounds <= 3: a frame workgroup of the mortar family's one-launch step gave up waiting for its descriptor.
  *      Since round 4 that launch cannot time out -- a frame wave that waits too long steps the instances itself,
  *      mg_mortar.hip mortar_step_raster_kernel -- and the bit is never raised) */
@@ -536,7 +576,8 @@ int mg_enable_peer_access(int device, int peer_device);
  * form): steps mg_advance took inside mortar_advance_kernel.  Both counted on the host.  "play_fused_steps" (every id; only the mortar family
  * has the form): steps mg_play took inside mortar_play_kernel; the steps of its loop form count as "headless_steps" and, where a mask applied,
  * "masked_steps".  "instance_saves" / "instance_loads" (every id):
- * mg_save_instances / mg_load_instances calls of this handle with count > 0, counted on the host.  Unknown name: -1.  Synchronous. */
+ * mg_save_instances / mg_load_instances calls of this handle with count > 0, counted on the host.  "frame_saves" / "frame_draws" (every id): the same
+ * for mg_save_frames / mg_draw_frames.  Unknown name: -1.  Synchronous. */
 int mg_debug_counter(mg_env* env, const char* name, int64_t* value);
 
 /* Test hook: copy the numpy-compatible PCG64 words of instance i to host:
