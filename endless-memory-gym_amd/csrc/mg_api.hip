@@ -39,6 +39,7 @@ struct mg_env {
         mg_info_buffers ib;
     } adv;
     int64_t play_fused_steps = 0;      // mg_debug_counter: steps mg_play took inside a family's own launches (Family::play)
+    int64_t traced_steps = 0, traced_fused_steps = 0;  // mg_debug_counter: steps of mg_advance_traced / mg_play_traced calls with a trace; those taken in-launch
     // mg_play: what the loop of its definition passes from launch to launch, allocated at the handle's first call (include/memgym.h)
     struct Play {
         bool ready = false;
@@ -450,61 +451,114 @@ __global__ __launch_bounds__(256) void advance_accumulate_kernel(int n, int firs
     for (int k = 0; k < MG_INFO_SLOTS; ++k)
         if (o.aux_sum_dev[k] && ib.aux_dev[k] && (first || d)) o.aux_sum_dev[k][i] = (first ? 0.0 : o.aux_sum_dev[k][i]) + (d ? (double)ib.aux_dev[k][i] : 0.0);
 }
+// mg_save_frames' row-gather launch (defined with the frame records below): the traced loop forms keep each step's descriptor rows with it
+__global__ __launch_bounds__(256) void frame_rows_save_kernel(const row_vec16* __restrict__ descs, int vec_per_row, const int32_t* __restrict__ idx, int count,
+                                                              int num_envs, row_vec16* __restrict__ rec, int* err);
+namespace {
+// mg_rollout_trace as the caller's header laid it out (include/memgym.h), checked like mg_advance_out: -> the rows, all NULL without a trace
+mg::TraceRows read_trace(const std::string& who, const mg_rollout_trace* trace, bool teacher) {
+    mg_rollout_trace t;
+    memset(&t, 0, sizeof(t));
+    if (trace) {
+        const size_t sz = trace->struct_size;
+        if (sz < sizeof(t) || sz > sizeof(t) + 16 * sizeof(void*) || sz % sizeof(void*) != 0)
+            throw std::runtime_error(who + ": mg_rollout_trace.struct_size = " + std::to_string(sz) + " is not a layout of include/memgym.h; set it to sizeof(mg_rollout_trace)");
+        memcpy(&t, trace, sizeof(t));
+    }
+    if ((uintptr_t)t.frames_dev & 15u) throw std::runtime_error(who + ": mg_rollout_trace.frames_dev is not 16-byte aligned");
+    if (!teacher && (t.actions_dev || t.labels_dev))
+        throw std::runtime_error(who + ": mg_rollout_trace.actions_dev / labels_dev are set: the tape is the caller's and there is no teacher (mg_advance_traced fills them)");
+    if (((uintptr_t)t.actions_dev | (uintptr_t)t.labels_dev) & 7u) throw std::runtime_error(who + ": mg_rollout_trace.actions_dev / labels_dev are not 8-byte aligned");
+    return mg::TraceRows{t.frames_dev, t.actions_dev, t.labels_dev, t.reward_dev, t.done_dev};
+}
+
+// row t of a frame trace <- the descriptor rows as they stand: mg_save_frames(env, NULL, num_envs, ...) without its checks and its counter
+void save_frame_row(mg_env* env, void* frames, int t, hipStream_t st) {
+    const std::pair<const void*, size_t> rows = env->fam->frame_rows();
+    const int n = env->num_envs, vec_per_row = (int)(rows.second / 16);
+    const int64_t lanes = (int64_t)n * vec_per_row;
+    hipLaunchKernelGGL(frame_rows_save_kernel, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st, (const row_vec16*)rows.first, vec_per_row,
+                       (const int32_t*)nullptr, n, n, (row_vec16*)((char*)frames + (size_t)t * (size_t)n * rows.second), env->fam->error_word());
+    MG_HIP(hipGetLastError());
+}
+
+// mg_advance and mg_advance_traced (trace == NULL: the untraced call, launch for launch what it was)
+void advance_call(mg_env* env, const std::string& who, int32_t steps, double eps, uint64_t seed, uint64_t step0, float* gt_dev, const mg_advance_out* out,
+                  const mg_rollout_trace* trace, void* stream) {
+    if (!env->started) throw std::runtime_error(who + ": before the first mg_reset / mg_set_state");
+    if (steps < 1) throw std::runtime_error(who + ": steps < 1");
+    if (!(eps >= 0.0 && eps <= 1.0)) throw std::runtime_error(who + ": eps outside [0, 1]");
+    mg_advance_out o;
+    memset(&o, 0, sizeof(o));
+    if (out) {  // (as the caller's header laid it out: a shorter struct lacks the later slots)
+        const size_t sz = out->struct_size;
+        if (sz < offsetof(mg_advance_out, aux_sum_dev) || sz > sizeof(o) + 16 * sizeof(void*) || sz % sizeof(void*) != 0)
+            throw std::runtime_error(who + ": mg_advance_out.struct_size = " + std::to_string(sz) + " is not a layout of include/memgym.h; set it to sizeof(mg_advance_out)");
+        memcpy(&o, out, sz < sizeof(o) ? sz : sizeof(o));
+    }
+    o.struct_size = sizeof(o);
+    const mg::TraceRows T = read_trace(who, trace, true);
+    const bool traced = trace != nullptr;
+    if (traced && env->fam->geometry_dirty()) throw std::runtime_error(who + ": options that change geometry need a reset before the next step");
+    hipStream_t st = (hipStream_t)stream;
+    mg::Family* f = env->fam;
+    const int n = env->num_envs;
+    mg_env::Advance& A = env->adv;
+    if (!A.ready) {  // the handle's first call: the only one that allocates (and therefore not capturable)
+        if (mg::stream_capturing(st))
+            throw std::runtime_error(who + ": the handle's first call allocates its scratch and cannot be captured; call it once eagerly");
+        A.actions.alloc((size_t)n * 2);
+        A.reward.alloc(n);
+        A.done.alloc(n);
+        A.reward64.alloc(n);
+        A.ep_reward.alloc(n);
+        A.ep_length.alloc(n);
+        memset(&A.ib, 0, sizeof(A.ib));
+        A.ib.struct_size = sizeof(A.ib);
+        A.ib.reward64_dev = A.reward64.p;
+        A.ib.ep_reward_dev = A.ep_reward.p;
+        A.ib.ep_length_dev = A.ep_length.p;
+        for (int k = 0; k < MG_INFO_SLOTS && f->info_name(k); ++k) {
+            A.aux[k].alloc(n);
+            A.ib.aux_dev[k] = A.aux[k].p;
+        }
+        A.ready = true;
+    }
+    float* gt = f->gt_dim() ? gt_dev : nullptr;
+    const mg::AdvanceArgs args{steps, eps, seed, step0, A.actions.p, A.reward.p, A.done.p, gt, A.ib, o};
+    if (traced ? f->advance_traced(args, T, st) : f->advance(args, st)) {
+        env->advance_fused_steps += steps;
+        if (traced) env->traced_steps += steps, env->traced_fused_steps += steps;
+        return;
+    }
+    const size_t row = (size_t)n * (size_t)f->action_dim();
+    for (int t = 0; t < steps; ++t) {  // the loop of the definition; the trace rows, where given, ARE its A, R and D
+        int32_t* a = T.actions ? T.actions + (size_t)t * row : A.actions.p;
+        float* r = T.reward ? T.reward + (size_t)t * (size_t)n : A.reward.p;
+        uint8_t* d = T.done ? T.done + (size_t)t * (size_t)n : A.done.p;
+        const uint64_t base = mg::expert_base(seed, step0 + (uint64_t)t);
+        f->expert_actions(mg::ExpertArgs{eps, base, a}, st);
+        if (T.labels) f->expert_actions(mg::ExpertArgs{0.0, base, T.labels + (size_t)t * row}, st);
+        f->step(a, nullptr, nullptr, r, d, gt, &A.ib, 1, st);
+        if (out) {
+            hipLaunchKernelGGL(advance_accumulate_kernel, dim3((n + 255) / 256), dim3(256), 0, st, n, t == 0 ? 1 : 0, A.ib, (const uint8_t*)d, o);
+            MG_HIP(hipGetLastError());
+        }
+        if (T.frames) save_frame_row(env, T.frames, t, st);
+    }
+    env->headless_steps += steps;
+    if (traced) env->traced_steps += steps;
+}
+}  // namespace
 extern "C" {
 
 int mg_advance(mg_env* env, int32_t steps, double eps, uint64_t seed, uint64_t step0, float* gt_dev, const mg_advance_out* out, void* stream) {
-    return guarded(env, [&] {
-        if (!env->started) throw std::runtime_error("mg_advance: before the first mg_reset / mg_set_state");
-        if (steps < 1) throw std::runtime_error("mg_advance: steps < 1");
-        if (!(eps >= 0.0 && eps <= 1.0)) throw std::runtime_error("mg_advance: eps outside [0, 1]");
-        mg_advance_out o;
-        memset(&o, 0, sizeof(o));
-        if (out) {  // (as the caller's header laid it out: a shorter struct lacks the later slots)
-            const size_t sz = out->struct_size;
-            if (sz < offsetof(mg_advance_out, aux_sum_dev) || sz > sizeof(o) + 16 * sizeof(void*) || sz % sizeof(void*) != 0)
-                throw std::runtime_error("mg_advance: mg_advance_out.struct_size = " + std::to_string(sz) + " is not a layout of include/memgym.h; set it to sizeof(mg_advance_out)");
-            memcpy(&o, out, sz < sizeof(o) ? sz : sizeof(o));
-        }
-        o.struct_size = sizeof(o);
-        hipStream_t st = (hipStream_t)stream;
-        mg::Family* f = env->fam;
-        const int n = env->num_envs;
-        mg_env::Advance& A = env->adv;
-        if (!A.ready) {  // the handle's first call: the only one that allocates (and therefore not capturable)
-            if (mg::stream_capturing(st))
-                throw std::runtime_error("mg_advance: the handle's first call allocates its scratch and cannot be captured; call it once eagerly");
-            A.actions.alloc((size_t)n * 2);
-            A.reward.alloc(n);
-            A.done.alloc(n);
-            A.reward64.alloc(n);
-            A.ep_reward.alloc(n);
-            A.ep_length.alloc(n);
-            memset(&A.ib, 0, sizeof(A.ib));
-            A.ib.struct_size = sizeof(A.ib);
-            A.ib.reward64_dev = A.reward64.p;
-            A.ib.ep_reward_dev = A.ep_reward.p;
-            A.ib.ep_length_dev = A.ep_length.p;
-            for (int k = 0; k < MG_INFO_SLOTS && f->info_name(k); ++k) {
-                A.aux[k].alloc(n);
-                A.ib.aux_dev[k] = A.aux[k].p;
-            }
-            A.ready = true;
-        }
-        float* gt = f->gt_dim() ? gt_dev : nullptr;
-        if (f->advance(mg::AdvanceArgs{steps, eps, seed, step0, A.actions.p, A.reward.p, A.done.p, gt, A.ib, o}, st)) {
-            env->advance_fused_steps += steps;
-            return;
-        }
-        for (int t = 0; t < steps; ++t) {  // the loop of the definition
-            f->expert_actions(mg::ExpertArgs{eps, mg::expert_base(seed, step0 + (uint64_t)t), A.actions.p}, st);
-            f->step(A.actions.p, nullptr, nullptr, A.reward.p, A.done.p, gt, &A.ib, 1, st);
-            if (out) {
-                hipLaunchKernelGGL(advance_accumulate_kernel, dim3((n + 255) / 256), dim3(256), 0, st, n, t == 0 ? 1 : 0, A.ib, (const uint8_t*)A.done.p, o);
-                MG_HIP(hipGetLastError());
-            }
-        }
-        env->headless_steps += steps;
-    });
+    return guarded(env, [&] { advance_call(env, "mg_advance", steps, eps, seed, step0, gt_dev, out, nullptr, stream); });
+}
+
+int mg_advance_traced(mg_env* env, int32_t steps, double eps, uint64_t seed, uint64_t step0, float* gt_dev, const mg_advance_out* out,
+                      const mg_rollout_trace* trace, void* stream) {
+    return guarded(env, [&] { advance_call(env, "mg_advance_traced", steps, eps, seed, step0, gt_dev, out, trace, stream); });
 }
 
 }  // extern "C"
@@ -526,78 +580,95 @@ __global__ __launch_bounds__(256) void play_accumulate_kernel(int n, int first, 
     if (played) played[i] = (first ? 0 : played[i]) + (a ? 1 : 0);
     if (episode && d) alive[i] = 0;  // (episode: alive is the handle's scratch row, never NULL)
 }
+namespace {
+// mg_play and mg_play_traced (frames_dev: the trace's frame rows; traced: the call came with a trace.  Without one: mg_play, launch for launch what it was)
+void play_call(mg_env* env, const std::string& who, const int32_t* tape_dev, int32_t steps, int mode, const uint8_t* active_dev, float* reward_trace_dev,
+               uint8_t* done_trace_dev, int32_t* steps_played_dev, float* gt_dev, const mg_advance_out* sums, void* frames_dev, bool traced, void* stream) {
+    if (!env->started) throw std::runtime_error(who + ": before the first mg_reset / mg_set_state");
+    if (steps < 1) throw std::runtime_error(who + ": steps < 1");
+    if (!tape_dev) throw std::runtime_error(who + ": tape_dev is NULL");
+    if (mode != MG_PLAY_THROUGH && mode != MG_PLAY_EPISODE) throw std::runtime_error(who + ": mode is neither MG_PLAY_THROUGH nor MG_PLAY_EPISODE");
+    if (env->fam->geometry_dirty()) throw std::runtime_error(who + ": options that change geometry need a reset before the next step");
+    mg_advance_out o;
+    memset(&o, 0, sizeof(o));
+    if (sums) {  // (as the caller's header laid it out: a shorter struct lacks the later slots)
+        const size_t sz = sums->struct_size;
+        if (sz < offsetof(mg_advance_out, aux_sum_dev) || sz > sizeof(o) + 16 * sizeof(void*) || sz % sizeof(void*) != 0)
+            throw std::runtime_error(who + ": mg_advance_out.struct_size = " + std::to_string(sz) + " is not a layout of include/memgym.h; set it to sizeof(mg_advance_out)");
+        memcpy(&o, sums, sz < sizeof(o) ? sz : sizeof(o));
+    }
+    o.struct_size = sizeof(o);
+    hipStream_t st = (hipStream_t)stream;
+    mg::Family* f = env->fam;
+    const int n = env->num_envs;
+    mg_env::Play& P = env->ply;
+    if (!P.ready) {  // the handle's first call: the only one that allocates (and therefore not capturable)
+        if (mg::stream_capturing(st))
+            throw std::runtime_error(who + ": the handle's first call allocates its scratch and cannot be captured; call it once eagerly");
+        P.alive.alloc(n);
+        P.reward.alloc(n);
+        P.done.alloc(n);
+        P.reward64.alloc(n);
+        P.ep_reward.alloc(n);
+        P.ep_length.alloc(n);
+        memset(&P.ib, 0, sizeof(P.ib));
+        P.ib.struct_size = sizeof(P.ib);
+        P.ib.reward64_dev = P.reward64.p;
+        P.ib.ep_reward_dev = P.ep_reward.p;
+        P.ib.ep_length_dev = P.ep_length.p;
+        for (int k = 0; k < MG_INFO_SLOTS && f->info_name(k); ++k) {
+            P.aux[k].alloc(n);
+            P.ib.aux_dev[k] = P.aux[k].p;
+        }
+        P.ready = true;
+    }
+    const int episode = mode == MG_PLAY_EPISODE ? 1 : 0;
+    float* gt = f->gt_dim() ? gt_dev : nullptr;
+    const mg::PlayArgs args{steps, episode, tape_dev, active_dev, reward_trace_dev, done_trace_dev, steps_played_dev, P.reward.p, P.done.p, P.alive.p, gt, P.ib, o};
+    if (traced ? f->play_traced(args, frames_dev, st) : f->play(args, st)) {
+        env->play_fused_steps += steps;
+        if (traced) env->traced_steps += steps, env->traced_fused_steps += steps;
+        return;
+    }
+    // the loop of the definition.  The mask of step t: the caller's while it cannot change (MG_PLAY_THROUGH), else the handle's alive row
+    const uint8_t* mask = active_dev;
+    if (episode) {
+        if (active_dev) MG_HIP(hipMemcpyAsync(P.alive.p, active_dev, (size_t)n, hipMemcpyDeviceToDevice, st));
+        else MG_HIP(hipMemsetAsync(P.alive.p, 1, (size_t)n, st));
+        mask = P.alive.p;
+    }
+    const size_t row = (size_t)n * (size_t)f->action_dim();
+    const bool accumulate = sums || steps_played_dev || episode;
+    for (int t = 0; t < steps; ++t) {
+        float* r = reward_trace_dev ? reward_trace_dev + (size_t)t * (size_t)n : P.reward.p;
+        uint8_t* d = done_trace_dev ? done_trace_dev + (size_t)t * (size_t)n : P.done.p;
+        f->step(tape_dev + (size_t)t * row, mask, nullptr, r, d, gt, &P.ib, episode ? 0 : 1, st);
+        if (accumulate) {
+            hipLaunchKernelGGL(play_accumulate_kernel, dim3((n + 255) / 256), dim3(256), 0, st, n, t == 0 ? 1 : 0, episode, P.ib, (const uint8_t*)d,
+                               episode ? P.alive.p : (uint8_t*)active_dev, steps_played_dev, o);
+            MG_HIP(hipGetLastError());
+        }
+        if (frames_dev) save_frame_row(env, frames_dev, t, st);  // (an instance the step left alone keeps its descriptor: its row repeats it)
+    }
+    env->headless_steps += steps;
+    if (mask) env->masked_steps += steps;
+    if (traced) env->traced_steps += steps;
+}
+}  // namespace
 extern "C" {
 
 int mg_play(mg_env* env, const int32_t* tape_dev, int32_t steps, int mode, const uint8_t* active_dev, float* reward_trace_dev, uint8_t* done_trace_dev,
             int32_t* steps_played_dev, float* gt_dev, const mg_advance_out* sums, void* stream) {
     return guarded(env, [&] {
-        if (!env->started) throw std::runtime_error("mg_play: before the first mg_reset / mg_set_state");
-        if (steps < 1) throw std::runtime_error("mg_play: steps < 1");
-        if (!tape_dev) throw std::runtime_error("mg_play: tape_dev is NULL");
-        if (mode != MG_PLAY_THROUGH && mode != MG_PLAY_EPISODE) throw std::runtime_error("mg_play: mode is neither MG_PLAY_THROUGH nor MG_PLAY_EPISODE");
-        if (env->fam->geometry_dirty()) throw std::runtime_error("mg_play: options that change geometry need a reset before the next step");
-        mg_advance_out o;
-        memset(&o, 0, sizeof(o));
-        if (sums) {  // (as the caller's header laid it out: a shorter struct lacks the later slots)
-            const size_t sz = sums->struct_size;
-            if (sz < offsetof(mg_advance_out, aux_sum_dev) || sz > sizeof(o) + 16 * sizeof(void*) || sz % sizeof(void*) != 0)
-                throw std::runtime_error("mg_play: mg_advance_out.struct_size = " + std::to_string(sz) + " is not a layout of include/memgym.h; set it to sizeof(mg_advance_out)");
-            memcpy(&o, sums, sz < sizeof(o) ? sz : sizeof(o));
-        }
-        o.struct_size = sizeof(o);
-        hipStream_t st = (hipStream_t)stream;
-        mg::Family* f = env->fam;
-        const int n = env->num_envs;
-        mg_env::Play& P = env->ply;
-        if (!P.ready) {  // the handle's first call: the only one that allocates (and therefore not capturable)
-            if (mg::stream_capturing(st))
-                throw std::runtime_error("mg_play: the handle's first call allocates its scratch and cannot be captured; call it once eagerly");
-            P.alive.alloc(n);
-            P.reward.alloc(n);
-            P.done.alloc(n);
-            P.reward64.alloc(n);
-            P.ep_reward.alloc(n);
-            P.ep_length.alloc(n);
-            memset(&P.ib, 0, sizeof(P.ib));
-            P.ib.struct_size = sizeof(P.ib);
-            P.ib.reward64_dev = P.reward64.p;
-            P.ib.ep_reward_dev = P.ep_reward.p;
-            P.ib.ep_length_dev = P.ep_length.p;
-            for (int k = 0; k < MG_INFO_SLOTS && f->info_name(k); ++k) {
-                P.aux[k].alloc(n);
-                P.ib.aux_dev[k] = P.aux[k].p;
-            }
-            P.ready = true;
-        }
-        const int episode = mode == MG_PLAY_EPISODE ? 1 : 0;
-        float* gt = f->gt_dim() ? gt_dev : nullptr;
-        if (f->play(mg::PlayArgs{steps, episode, tape_dev, active_dev, reward_trace_dev, done_trace_dev, steps_played_dev, P.reward.p, P.done.p, P.alive.p, gt,
-                                 P.ib, o},
-                    st)) {
-            env->play_fused_steps += steps;
-            return;
-        }
-        // the loop of the definition.  The mask of step t: the caller's while it cannot change (MG_PLAY_THROUGH), else the handle's alive row
-        const uint8_t* mask = active_dev;
-        if (episode) {
-            if (active_dev) MG_HIP(hipMemcpyAsync(P.alive.p, active_dev, (size_t)n, hipMemcpyDeviceToDevice, st));
-            else MG_HIP(hipMemsetAsync(P.alive.p, 1, (size_t)n, st));
-            mask = P.alive.p;
-        }
-        const size_t row = (size_t)n * (size_t)f->action_dim();
-        const bool accumulate = sums || steps_played_dev || episode;
-        for (int t = 0; t < steps; ++t) {
-            float* r = reward_trace_dev ? reward_trace_dev + (size_t)t * (size_t)n : P.reward.p;
-            uint8_t* d = done_trace_dev ? done_trace_dev + (size_t)t * (size_t)n : P.done.p;
-            f->step(tape_dev + (size_t)t * row, mask, nullptr, r, d, gt, &P.ib, episode ? 0 : 1, st);
-            if (accumulate) {
-                hipLaunchKernelGGL(play_accumulate_kernel, dim3((n + 255) / 256), dim3(256), 0, st, n, t == 0 ? 1 : 0, episode, P.ib, (const uint8_t*)d,
-                                   episode ? P.alive.p : (uint8_t*)active_dev, steps_played_dev, o);
-                MG_HIP(hipGetLastError());
-            }
-        }
-        env->headless_steps += steps;
-        if (mask) env->masked_steps += steps;
+        play_call(env, "mg_play", tape_dev, steps, mode, active_dev, reward_trace_dev, done_trace_dev, steps_played_dev, gt_dev, sums, nullptr, false, stream);
+    });
+}
+
+int mg_play_traced(mg_env* env, const int32_t* tape_dev, int32_t steps, int mode, const uint8_t* active_dev, int32_t* steps_played_dev, float* gt_dev,
+                   const mg_advance_out* sums, const mg_rollout_trace* trace, void* stream) {
+    return guarded(env, [&] {
+        const mg::TraceRows T = read_trace("mg_play_traced", trace, false);
+        play_call(env, "mg_play_traced", tape_dev, steps, mode, active_dev, T.reward, T.done, steps_played_dev, gt_dev, sums, T.frames, trace != nullptr, stream);
     });
 }
 
@@ -975,6 +1046,10 @@ int mg_debug_counter(mg_env* env, const char* name, int64_t* value) {
         }
         if (std::string(name) == "play_fused_steps") {  // every id: counted in this file (only the mortar family has the form)
             *value = env->play_fused_steps;
+            return;
+        }
+        if (std::string(name) == "traced_steps" || std::string(name) == "traced_fused_steps") {  // every id: counted in this file
+            *value = std::string(name) == "traced_steps" ? env->traced_steps : env->traced_fused_steps;
             return;
         }
         if (std::string(name) == "instance_saves" || std::string(name) == "instance_loads") {  // every id: counted in this file

@@ -246,6 +246,16 @@ struct PlayArgs {
     mg_advance_out out;
 };
 
+// mg_rollout_trace (include/memgym.h: mg_advance_traced / mg_play_traced) as it reaches a family: row 0 of each [steps][...] trace array, any may be NULL.
+// mg_play_traced has no actions / labels; its reward / done rows travel in PlayArgs::reward_trace / done_trace, as mg_play's do.
+struct TraceRows {
+    void* frames;      // [steps][num_envs] frame descriptors (frame_rows().second bytes each), 16-byte aligned
+    int32_t* actions;  // [steps][num_envs * action_dim]
+    int32_t* labels;   // [steps][num_envs * action_dim]
+    float* reward;     // [steps][num_envs]
+    uint8_t* done;     // [steps][num_envs]
+};
+
 // What the C ABI (mg_api.hip) sees of an environment family, and the host-side plumbing the three families share: the error
 // word, the RNG streams, the "seeded" / "geometry changed" guards and the debug view's scratch frames.
 class Family {
@@ -291,6 +301,10 @@ class Family {
     // mg_play: true = the family has run the loop of include/memgym.h's definition inside launches of its own (the mortar family:
     // mortar_play_kernel); false = it has no such form (or the lab build switched it off) and nothing happened: mg_api.hip runs the loop.
     virtual bool play(const PlayArgs& /*v*/, hipStream_t /*s*/) { return false; }
+    // mg_advance_traced / mg_play_traced with a trace: the same contract, the traced in-launch forms (the mortar family: mortar_advance_traced_kernel /
+    // mortar_play_traced_kernel, mg_mortar_trace.hpp).  `frames` of play_traced: TraceRows::frames, or NULL.
+    virtual bool advance_traced(const AdvanceArgs& /*v*/, const TraceRows& /*tr*/, hipStream_t /*s*/) { return false; }
+    virtual bool play_traced(const PlayArgs& /*v*/, void* /*frames*/, hipStream_t /*s*/) { return false; }
     // rasterise the CURRENT frame descriptors of the instances with only[i] != 0 into `obs` (others untouched)
     virtual void raster_only(void* obs, const uint8_t* only, hipStream_t s) = 0;
     // mg_save_frames / mg_draw_frames (include/memgym.h; mg_frame_records.hpp).  frame_rows(): the frame descriptor array raster_only() draws from, as

@@ -16,6 +16,8 @@
 //   mg_mortar_expert.hpp      mortar_expert_kernel: the scripted teacher of the five ids (mg_expert_actions), a launch of its own
 //   mg_mortar_advance.hpp     mortar_advance_kernel: K steps under the teacher without a frame (mg_advance), teacher + step + sums per lane in one launch
 //   mg_mortar_play.hpp        mortar_play_kernel: K steps of a caller-supplied action tape without a frame (mg_play), step + traces + sums per lane in one launch
+//   mg_mortar_trace.hpp       mortar_advance_traced_kernel / mortar_play_traced_kernel: the two above as kernels of their own that also keep every step's frame
+//                             descriptor, action, teacher's label, reward and done (mg_advance_traced / mg_play_traced)
 //
 // The launches of a step as shipped:
 //   ONE launch for handles with one option set, in every observation format (mortar_step_raster_kernel: the step's workgroups lead the raster's grid and a frame waits for its own
@@ -40,6 +42,7 @@
 #include "mg_mortar_expert.hpp"
 #include "mg_mortar_advance.hpp"
 #include "mg_mortar_play.hpp"
+#include "mg_mortar_trace.hpp"
 
 namespace mg {
 using namespace v1;  // raster generation 1 (see mg_raster_v1.hpp)
@@ -348,6 +351,46 @@ class MortarFamily : public Family {
                                     v.done_trace ? v.done_trace + (size_t)t0 * (size_t)n_ : nullptr, v.played, v.out};
             with_bool(sets_.per_set(), [&](auto PS) {
                 launch_checked(mortar_play_kernel<decltype(PS)::value>, dim3((n_ + 255) / 256), dim3(256), 0, s, sa, pa);
+            });
+        }
+        return true;
+    }
+
+    // mg_advance_traced / mg_play_traced inside ONE launch per ADVANCE_MAX_STEPS steps (mg_mortar_trace.hpp): the host offsets every trace row pointer by the
+    // steps the launches before took, in 64 bits.  The lab switches of the untraced forms govern these too (tools/rollout_trace_bench.py flips them).
+    bool advance_traced(const AdvanceArgs& v, const TraceRows& tr, hipStream_t s) override {
+        if (!lab_flag("MEMGYM_MORTAR_ADVANCE_FUSE", true)) return false;
+        if (dirty_) throw std::runtime_error("options that change geometry need a reset before the next step");
+        sets_.upload(s);
+        const MortarStepArgs sa{P_, n_, io(), v.actions, v.reward, v.done, gt_dim() ? v.gt : nullptr, v.info, 1, handover_.p, nullptr};
+        const size_t row = (size_t)n_ * (size_t)action_dim();
+        for (int t0 = 0; t0 < v.steps; t0 += ADVANCE_MAX_STEPS) {
+            const int k = v.steps - t0 < ADVANCE_MAX_STEPS ? v.steps - t0 : ADVANCE_MAX_STEPS;
+            const MortarAdvanceArgs aa{k, t0 == 0 ? 1 : 0, v.eps, v.seed, v.step0 + (uint64_t)t0, v.actions, v.out};
+            const size_t at = (size_t)t0 * (size_t)n_;
+            const MortarTraceRows rows{tr.frames ? (MortarDesc*)tr.frames + at : nullptr, tr.actions ? tr.actions + (size_t)t0 * row : nullptr,
+                                       tr.labels ? tr.labels + (size_t)t0 * row : nullptr, tr.reward ? tr.reward + at : nullptr, tr.done ? tr.done + at : nullptr};
+            with_bool(sets_.per_set(), [&](auto PS) {
+                launch_checked(mortar_advance_traced_kernel<decltype(PS)::value>, dim3((n_ + 255) / 256), dim3(256), 0, s, sa, aa, rows);
+            });
+        }
+        return true;
+    }
+    bool play_traced(const PlayArgs& v, void* frames, hipStream_t s) override {
+        if (!lab_flag("MEMGYM_MORTAR_PLAY_FUSE", true)) return false;
+        if (dirty_) throw std::runtime_error("options that change geometry need a reset before the next step");
+        sets_.upload(s);
+        const int row = n_ * action_dim();
+        for (int t0 = 0; t0 < v.steps; t0 += ADVANCE_MAX_STEPS) {
+            const int k = v.steps - t0 < ADVANCE_MAX_STEPS ? v.steps - t0 : ADVANCE_MAX_STEPS;
+            const size_t at = (size_t)t0 * (size_t)n_;
+            const MortarStepArgs sa{P_, n_, io(), v.tape + (size_t)t0 * (size_t)row, v.reward, v.done, gt_dim() ? v.gt : nullptr, v.info, v.episode ? 0 : 1,
+                                    handover_.p, nullptr};
+            const MortarPlayArgs pa{k, t0 == 0 ? 1 : 0, t0 + k == v.steps ? 1 : 0, v.episode, row, v.active, v.alive,
+                                    v.reward_trace ? v.reward_trace + at : nullptr, v.done_trace ? v.done_trace + at : nullptr, v.played, v.out};
+            MortarDesc* const fr = frames ? (MortarDesc*)frames + at : nullptr;
+            with_bool(sets_.per_set(), [&](auto PS) {
+                launch_checked(mortar_play_traced_kernel<decltype(PS)::value>, dim3((n_ + 255) / 256), dim3(256), 0, s, sa, pa, fr);
             });
         }
         return true;

@@ -33,6 +33,11 @@ class AdvanceOut(C.Structure):  # include/memgym.h: mg_advance_out (device array
                 ("ep_length_sum_dev", C.c_void_p), ("aux_sum_dev", C.c_void_p * MG_INFO_SLOTS)]
 
 
+class RolloutTraceRows(C.Structure):  # include/memgym.h: mg_rollout_trace (device arrays [steps][...], any may be NULL)
+    _fields_ = [("struct_size", C.c_size_t), ("frames_dev", C.c_void_p), ("actions_dev", C.c_void_p), ("labels_dev", C.c_void_p),
+                ("reward_dev", C.c_void_p), ("done_dev", C.c_void_p)]
+
+
 class ObsAllocInfo(C.Structure):
     _fields_ = [("zones", C.c_int), ("pieces", C.c_int), ("piece_bytes", C.c_size_t), ("searched_bytes", C.c_size_t),
                 ("probe_same_tbps", C.c_double), ("probe_cross_tbps", C.c_double), ("search_ms", C.c_double)]
@@ -100,6 +105,11 @@ def _load():
     if hasattr(L, "mg_play"):  # (absent from the older builds tools/ A/B against through MEMGYM_HIP_LIB)
         L.mg_play.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                               C.POINTER(AdvanceOut), C.c_void_p]
+    if hasattr(L, "mg_advance_traced"):  # (absent from the older builds tools/ A/B against through MEMGYM_HIP_LIB)
+        L.mg_advance_traced.argtypes = [C.c_void_p, C.c_int32, C.c_double, C.c_uint64, C.c_uint64, C.c_void_p, C.POINTER(AdvanceOut),
+                                        C.POINTER(RolloutTraceRows), C.c_void_p]
+        L.mg_play_traced.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(AdvanceOut),
+                                     C.POINTER(RolloutTraceRows), C.c_void_p]
     if hasattr(L, "mg_save_instances"):  # (absent from the older builds tools/ A/B against through MEMGYM_HIP_LIB)
         L.mg_instance_bytes.argtypes = [C.c_void_p]
         L.mg_instance_bytes.restype = C.c_size_t

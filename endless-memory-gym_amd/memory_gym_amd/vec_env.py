@@ -256,6 +256,77 @@ def check_frame_draw(records, layout, record_bytes, pick=None, out=None, obs_for
     return rows, pick, count, (dt, shape)
 
 
+MAX_DRAW_RECORDS = (1 << 31) - 1  # include/memgym.h: mg_draw_frames refuses n_records > INT32_MAX
+
+
+class RolloutTrace:
+    """What VecMemoryGym.new_rollout returns and advance_traced(ro) / play(trace=ro) fill (include/memgym.h: mg_advance_traced / mg_play_traced): K steps
+    of N instances kept as
+        frames   uint8   [K + 1, N, frame_record_bytes]   the frame records, and `frame_layout`, the value of mg_frame_layout they were filled under
+        actions  int32   [K, N] or [K, N, 2]              the action played at step t (advance only; play leaves it alone: the tape is the caller's)
+        labels   int32   same shape, or None              the teacher's answer at eps = 0 in the state the action was played in (new_rollout(labels=True))
+        reward   float32 [K, N]                           done   bool [K, N]
+    (any of them may be None: not kept -- e.g. RolloutTrace(frames, 0, None, None, None, None) keeps the frame records alone)
+    in the gymnasium convention: frames[t] is the observation actions[t] / labels[t] belong to, frames[t + 1] the result of step t (the new episode's
+    first frame where the step auto-reset the instance; for an instance that did not step, the frame it keeps).  draw() turns picks of it into frames."""
+    __slots__ = ("frames", "frame_layout", "actions", "labels", "reward", "done")
+
+    def __init__(self, frames, frame_layout, actions, labels, reward, done):
+        self.frames, self.frame_layout, self.actions, self.labels, self.reward, self.done = frames, int(frame_layout), actions, labels, reward, done
+
+    @property
+    def steps(self):
+        return int(self.frames.shape[0]) - 1 if self.frames is not None else int(next(t for t in (self.reward, self.done, self.actions) if t is not None).shape[0])
+
+    @property
+    def num_envs(self):
+        return int(next(t for t in (self.frames, self.reward, self.done, self.actions) if t is not None).shape[1])
+
+    def draw(self, env, t, i, out=None, obs_format=None):
+        """Frames of the trace: row j of the result is frames[t[j], i[j]] drawn in `obs_format` (default: the handle's) -- draw_frames over the flattened
+        store with pick = t * N + i.  t, i: integers, or integer tensors / lists of one length (t in 0 .. K, i in 0 .. N - 1).  ValueError, before anything
+        is launched: a trace filled under another handle or an earlier frame layout, t and i of different lengths, a store of more records than
+        mg_draw_frames accepts, and whatever draw_frames refuses about `out`."""
+        what = "RolloutTrace.draw"
+        if not (isinstance(self.frames, torch.Tensor) and self.frames.dim() == 3):
+            raise ValueError("%s: frames must be a uint8 tensor [K + 1, N, frame_record_bytes] (this trace keeps no frames?)" % what)
+        n = int(self.frames.shape[1])
+        if int(self.frames.shape[0]) * n > MAX_DRAW_RECORDS:
+            raise ValueError("%s: the store holds %d x %d records, draw_frames takes at most %d: draw from slices of `frames`"
+                             % (what, int(self.frames.shape[0]), n, MAX_DRAW_RECORDS))
+        dev = self.frames.device
+        t, i = (_instance_index(what, nm, [v] if isinstance(v, (int, np.integer)) else v, dev) for nm, v in (("t", t), ("i", i)))
+        if t.numel() != i.numel():
+            raise ValueError("%s: t and i must have one length, got %d and %d" % (what, t.numel(), i.numel()))
+        return env.draw_frames(FrameRecords(self.frames, self.frame_layout), pick=t * n + i, out=out, obs_format=obs_format)
+
+
+def check_rollout_trace(ro, steps, num_envs, action_dim, record_bytes, teacher, device=None):
+    """The argument checks of advance_traced(ro) / play(trace=ro), which need no handle: ValueError unless `ro` is a RolloutTrace whose tensors have the
+    shapes and dtypes of RolloutTrace's docstring for K = steps and N = num_envs, are contiguous, lie on `device` (if given) and are aligned for the
+    launches' vector stores (frames to 16 bytes, actions / labels to 8).  teacher=False (play): actions and labels are not looked at."""
+    what = "advance_traced" if teacher else "play(trace=...)"
+    if not isinstance(ro, RolloutTrace):
+        raise ValueError("%s: need the RolloutTrace new_rollout returned" % what)
+    K, N = int(steps), int(num_envs)
+    acts = (K, N) if action_dim == 1 else (K, N, 2)
+    want = [("frames", ro.frames, torch.uint8, (K + 1, N, int(record_bytes)), 16), ("reward", ro.reward, torch.float32, (K, N), 4), ("done", ro.done, torch.bool, (K, N), 1)]
+    if teacher:
+        want.append(("actions", ro.actions, torch.int32, acts, 8))
+        if ro.labels is not None:
+            want.append(("labels", ro.labels, torch.int32, acts, 8))
+    for name, t, dt, shape, align in want:
+        if t is None:  # not kept (include/memgym.h: every array may be NULL)
+            continue
+        if not (isinstance(t, torch.Tensor) and t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous()):
+            raise ValueError("%s: trace.%s must be a contiguous %s tensor of shape %s (a trace of %d steps of %d instances), got %s"
+                             % (what, name, dt, shape, K, N, "%s %s" % (t.dtype, tuple(t.shape)) if isinstance(t, torch.Tensor) else type(t).__name__))
+        if device is not None and t.device != device:
+            raise ValueError("%s: trace.%s is on %s, the handle on %s" % (what, name, t.device, device))
+        if t.data_ptr() % align:
+            raise ValueError("%s: trace.%s must be %d-byte aligned" % (what, name, align))
+
+
 class VecMemoryGym:
     metadata ={"render_modes": ["rgb_array", "debug_rgb_array"], "render_fps": 25}
 
@@ -617,6 +688,31 @@ class VecMemoryGym:
         self._swapped = self._stale = False
         return self._obs()
 
+    def new_rollout(self, steps, labels=False):
+        """A RolloutTrace for `steps` steps of this handle (zeros; frames [steps + 1, N, frame_record_bytes]) to pass to advance_traced() /
+        play(trace=...), as often as you like.  labels=True adds the tensor for the teacher's answers (advance only)."""
+        K, N, dev = int(steps), self.num_envs, self.device
+        if K < 1:
+            raise ValueError("new_rollout: steps must be >= 1, got %d" % K)
+        acts = (K, N) if self.action_dim == 1 else (K, N, 2)
+        return RolloutTrace(torch.zeros((K + 1, N, self.frame_record_bytes), dtype=torch.uint8, device=dev), 0,
+                            torch.zeros(acts, dtype=torch.int32, device=dev), torch.zeros(acts, dtype=torch.int32, device=dev) if labels else None,
+                            torch.zeros((K, N), dtype=torch.float32, device=dev), torch.zeros((K, N), dtype=torch.bool, device=dev))
+
+    def _trace_rows(self, ro, teacher):
+        """frames[0] <- the current frames (save_frames); -> the mg_rollout_trace over frames[1:] and the other tensors of a checked RolloutTrace"""
+        ptr = lambda t: None if t is None else t.data_ptr()
+        rows = _native.RolloutTraceRows()
+        rows.struct_size = C.sizeof(_native.RolloutTraceRows)
+        if ro.frames is not None:
+            self.save_frames(out=ro.frames[0])
+            ro.frame_layout = self.frame_layout()
+            rows.frames_dev = ro.frames[1:].data_ptr()
+        rows.reward_dev, rows.done_dev = ptr(ro.reward), ptr(ro.done)
+        if teacher:
+            rows.actions_dev, rows.labels_dev = ptr(ro.actions), ptr(ro.labels)
+        return rows
+
     def advance(self, steps, eps=0.0, seed=0, step=None, render=True, stats=True):
         """`steps` steps under the scripted teacher without a frame (include/memgym.h: mg_advance): state, random streams and error
         bits afterwards are those after `for t: step(expert_actions(eps, seed, step + t), render=False)` with auto-reset, whatever
@@ -629,8 +725,27 @@ class VecMemoryGym:
         step=None continues the call numbering of expert_actions() and advances it by `steps`.  Episodes that end inside the call are
         counted, not shown: there are no terminal observations here, on any handle.  Nothing synchronises; the handle's first call
         allocates scratch, every later one is capturable (the arguments are then the captured values).  The five Mortar Mayhem ids
-        run the whole loop inside one launch per 1,024 steps; the other five take it launch by launch."""
-        steps = int(steps)
+        run the whole loop inside one launch per 1,024 steps; the other five take it launch by launch.
+        advance_traced() is this call keeping every step in a RolloutTrace."""
+        return self._advance(int(steps), eps, seed, step, render, stats, None)
+
+    def advance_traced(self, trace, eps=0.0, seed=0, step=None, render=True, stats=True):
+        """advance(trace.steps, ...) that KEEPS the rollout in `trace`, a RolloutTrace (new_rollout) (include/memgym.h: mg_advance_traced): trace.frames[0]
+        the frames before the call, and per step t the action played (actions[t]), the teacher's answer at eps = 0 where the trace has labels (labels[t]),
+        reward[t], done[t] and the frame record after the step (frames[t + 1]); trace.draw() draws any pick of them later.  State, streams, stats and
+        the return value are those of advance() with the same arguments.  A trace of the wrong N / dtype / device / alignment raises ValueError
+        before anything is launched.  (A method of its own: advance()'s parameter list is kept as it is.)"""
+        self._require_started("advance_traced")
+        if not isinstance(trace, RolloutTrace):
+            raise ValueError("advance_traced: need the RolloutTrace new_rollout returned")
+        try:
+            steps = trace.steps
+        except (AttributeError, IndexError, StopIteration):
+            raise ValueError("advance_traced: the trace's tensors do not say how many steps it holds") from None
+        check_rollout_trace(trace, steps, self.num_envs, self.action_dim, self.frame_record_bytes, True, self.device)
+        return self._advance(steps, eps, seed, step, render, stats, trace)
+
+    def _advance(self, steps, eps, seed, step, render, stats, trace):
         if self._adv is None and stats:
             N, dev = self.num_envs, self.device
             t = {"reward": torch.zeros(N, dtype=torch.float64, device=dev), "episodes": torch.zeros(N, dtype=torch.int32, device=dev),
@@ -645,8 +760,13 @@ class VecMemoryGym:
             self._adv = (t, out)
         mask = (1 << 64) - 1
         with torch.cuda.device(self.device):
-            _native.check(_native.LIB.mg_advance(self._h, steps, float(eps), int(seed) & mask, int(self._expert_calls if step is None else step) & mask,
-                                                 self._p_gt, C.byref(self._adv[1]) if stats else None, self._stream()), "mg_advance")
+            if trace is not None:
+                rows = self._trace_rows(trace, True)
+                _native.check(_native.LIB.mg_advance_traced(self._h, steps, float(eps), int(seed) & mask, int(self._expert_calls if step is None else step) & mask,
+                                                            self._p_gt, C.byref(self._adv[1]) if stats else None, C.byref(rows), self._stream()), "mg_advance_traced")
+            else:
+                _native.check(_native.LIB.mg_advance(self._h, steps, float(eps), int(seed) & mask, int(self._expert_calls if step is None else step) & mask,
+                                                     self._p_gt, C.byref(self._adv[1]) if stats else None, self._stream()), "mg_advance")
             if self.gt64 is not None:
                 _native.check(_native.LIB.mg_ground_truth64(self._h, self.gt64.data_ptr(), self._stream()), "mg_ground_truth64")
         if step is None:
@@ -687,7 +807,12 @@ class VecMemoryGym:
         (the traces per K) and overwritten by the next call; stats=False, trace=False returns None in their place.  Nothing synchronises; the
         handle's first call allocates scratch and is refused inside a capture (call it once eagerly, with the K and the trace setting the capture
         will use, so that the stats tensors exist too); every later one is capturable (tape and mask are read at replay).  The five Mortar Mayhem ids run
-        the whole loop inside one launch per 1,024 steps; the other five take it launch by launch."""
+        the whole loop inside one launch per 1,024 steps; the other five take it launch by launch.
+        trace=<a RolloutTrace of K steps> (new_rollout) KEEPS the rollout instead (include/memgym.h: mg_play_traced): trace.frames[0] the frames before
+        the call, and per step t trace.reward[t], trace.done[t] and the frame record after the step, trace.frames[t + 1] -- for an instance that did
+        not step (paused by `mask`, or finished under until_done) the record of the frame it keeps, reward 0, done False.  trace.actions is not written:
+        the tape is yours.  stats then holds the sums and "steps" alone.  A trace of the wrong K / N / dtype / device / alignment raises ValueError before
+        anything is launched."""
         a = actions
         if not (isinstance(a, torch.Tensor) and a.dtype == torch.int32 and a.device == self.device and a.is_contiguous()):
             a = a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a))
@@ -705,6 +830,11 @@ class VecMemoryGym:
                 m = m.view(torch.uint8)  # (the same bytes: True is 1)
             elif not (m.dtype == torch.uint8 and m.device == self.device and m.is_contiguous()):
                 m = (m != 0).to(device=self.device, dtype=torch.uint8).contiguous()
+        ro = trace if not isinstance(trace, bool) and trace is not None else None
+        if ro is not None:
+            self._require_started("play(trace=...)")
+            check_rollout_trace(ro, K, self.num_envs, self.action_dim, self.frame_record_bytes, False, self.device)
+            trace = False
         if self._play is None:
             t, out = self._sum_tensors()
             t["steps"] = torch.zeros(self.num_envs, dtype=torch.int32, device=self.device)
@@ -715,10 +845,16 @@ class VecMemoryGym:
                          torch.zeros((K, self.num_envs), dtype=torch.uint8, device=self.device))
         rt, dt = traces[K] if trace else (None, None)
         with torch.cuda.device(self.device):
-            _native.check(_native.LIB.mg_play(self._h, a.data_ptr(), K, _native.MG_PLAY_EPISODE if until_done else _native.MG_PLAY_THROUGH,
-                                              None if m is None else m.data_ptr(), None if rt is None else rt.data_ptr(),
-                                              None if dt is None else dt.data_ptr(), sums["steps"].data_ptr() if stats else None, self._p_gt,
-                                              C.byref(out) if stats else None, self._stream()), "mg_play")
+            if ro is not None:
+                rows = self._trace_rows(ro, False)
+                _native.check(_native.LIB.mg_play_traced(self._h, a.data_ptr(), K, _native.MG_PLAY_EPISODE if until_done else _native.MG_PLAY_THROUGH,
+                                                         None if m is None else m.data_ptr(), sums["steps"].data_ptr() if stats else None, self._p_gt,
+                                                         C.byref(out) if stats else None, C.byref(rows), self._stream()), "mg_play_traced")
+            else:
+                _native.check(_native.LIB.mg_play(self._h, a.data_ptr(), K, _native.MG_PLAY_EPISODE if until_done else _native.MG_PLAY_THROUGH,
+                                                  None if m is None else m.data_ptr(), None if rt is None else rt.data_ptr(),
+                                                  None if dt is None else dt.data_ptr(), sums["steps"].data_ptr() if stats else None, self._p_gt,
+                                                  C.byref(out) if stats else None, self._stream()), "mg_play")
             if self.gt64 is not None:
                 _native.check(_native.LIB.mg_ground_truth64(self._h, self.gt64.data_ptr(), self._stream()), "mg_ground_truth64")
         self._stale = True

@@ -101,15 +101,26 @@ class GymnasiumVectorEnv(_Base):
         """The scripted teacher's actions in the current states (VecMemoryGym.expert_actions): what step() takes; numpy with as_numpy."""
         return self._host(self.env.expert_actions(eps=eps, seed=seed, step=step, out=out))
 
+    def new_rollout(self, steps, labels=False):
+        """VecMemoryGym.new_rollout -> RolloutTrace (device tensors, whatever as_numpy says: a trace is drawn from on the device)."""
+        return self.env.new_rollout(steps, labels=labels)
+
     def advance(self, steps, eps=0.0, seed=0, step=None, render=True, stats=True):
         """`steps` steps under the scripted teacher without a frame (VecMemoryGym.advance) -> (obs or None, stats); numpy with as_numpy.
         Episodes that end inside the call are NOT reported as `final_observation` / `final_info`: they are counted and summed in `stats`."""
         obs, st = self.env.advance(steps, eps=eps, seed=seed, step=step, render=render, stats=stats)
         return (None if obs is None else self._host(obs)), (None if st is None else self._host(st))
 
+    def advance_traced(self, trace, eps=0.0, seed=0, step=None, render=True, stats=True):
+        """VecMemoryGym.advance_traced: advance(trace.steps, ...) that keeps every step's frame record, action, label, reward and done in `trace`, a
+        RolloutTrace (new_rollout) -> (obs or None, stats); numpy with as_numpy."""
+        obs, st = self.env.advance_traced(trace, eps=eps, seed=seed, step=step, render=render, stats=stats)
+        return (None if obs is None else self._host(obs)), (None if st is None else self._host(st))
+
     def play(self, actions, until_done=False, mask=None, render=True, stats=True, trace=False):
         """K steps of caller-supplied action sequences without a frame (VecMemoryGym.play) -> (obs or None, stats); numpy with as_numpy.
-        Episodes that end inside the call are NOT reported as `final_observation` / `final_info`: they are counted and summed in `stats`."""
+        Episodes that end inside the call are NOT reported as `final_observation` / `final_info`: they are counted and summed in `stats`.
+        trace: False / True as in VecMemoryGym.play, or a RolloutTrace (new_rollout) that keeps every step's frame record, reward and done."""
         obs, st = self.env.play(actions, until_done=until_done, mask=mask, render=render, stats=stats, trace=trace)
         return (None if obs is None else self._host(obs)), (None if st is None else self._host(st))
 

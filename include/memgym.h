@@ -330,6 +330,47 @@ int mg_play(mg_env* env, const int32_t* tape_dev, int32_t steps, int mode, const
             float* reward_trace_dev, uint8_t* done_trace_dev, int32_t* steps_played_dev,
             float* gt_dev, const mg_advance_out* sums, void* stream);
 
+/* ROLLOUT TRACES: mg_advance / mg_play that KEEP EVERY STEP -- the frame record, the action played, the teacher's label, reward and done -- so that K steps
+ * under the teacher (or under the caller's tape) leave a complete rollout behind and mg_draw_frames later draws only the minibatch rows training asks for.
+ * All trace arrays are step-major, row t belongs to step t of the call; every array may be NULL (not kept).
+ * DEFINITION: state, PCG64 streams, frame descriptors, ground truth, error bits and sums after either call are exactly those of mg_advance / mg_play with the
+ * same arguments, and row t of the traces is what the definition loop of that call produces at step t:
+ *   mg_advance_traced   actions row t = what mg_expert_actions(env, eps, seed, step0 + t, ...) wrote before the step;
+ *                       labels  row t = what mg_expert_actions(env, 0.0, seed, step0 + t, ...) gives in the same state (the teacher's answer: DAgger labels);
+ *   both                reward / done row t = the R / D of step t;
+ *                       frames row t = what mg_save_frames(env, NULL, num_envs, frames + t * num_envs * mg_frame_record_bytes, stream) stores right after step t:
+ *                       the frame the step would have drawn -- the new episode's first frame where the step auto-reset the instance.
+ * What follows for MG_PLAY_EPISODE and for instances outside active_dev: an instance that does not step keeps its descriptor, so its frames rows repeat the
+ * descriptor it has -- the terminal one after its own done, the one from before the call if it never was alive -- and its reward / done entries are 0.
+ * trace == NULL is legal and makes the call its untraced sibling (mg_play_traced then keeps no reward / done rows either).  Frame traces have the validity of
+ * frame records: keep mg_frame_layout next to them.  The frame BEFORE the call's first step is not part of the trace: mg_save_frames it first (the Python
+ * mirror does, into row 0 of a [steps + 1] store).
+ * The scratch is the siblings' (allocated at the handle's first mg_advance / mg_advance_traced, respectively mg_play / mg_play_traced, which cannot be captured);
+ * every later call allocates nothing and can be captured into a HIP graph: the trace pointers are then the captured values, their contents are written at
+ * replay.  MG_STATE_VERSION is unchanged: no state is added.
+ * The five Mortar Mayhem ids run the loop INSIDE one launch per 1,024 steps (mortar_advance_traced_kernel / mortar_play_traced_kernel: the lane stores its action
+ * straight into the trace row, evaluates the teacher a second time for the label, and stores the 16-byte descriptor its step has just left as one vector store;
+ * all trace offsets are 64-bit); the other five ids take the loop on the host with the trace rows as the loop's own A / R / D rows, one more teacher launch for
+ * the labels and one mg_save_frames launch per step.  mg_debug_counter "traced_steps" counts the steps of calls with a trace, "traced_fused_steps" those taken
+ * in-launch; they also count as the siblings' "advance_fused_steps" / "play_fused_steps" / "headless_steps" / "masked_steps".
+ * STILL OUT OF SCOPE: the terminal frames of episodes that end inside a call (the reset frame replaces them, as in mg_advance); the MortarMayhemB ids' vector
+ * observation per step; the debug view.
+ * Errors (-1): everything the sibling refuses; a mg_rollout_trace.struct_size that is no layout of this header; a frames_dev that is not 16-byte aligned;
+ * actions_dev / labels_dev that are not 8-byte aligned; actions_dev or labels_dev set in mg_play_traced (the tape is the caller's, there is no teacher). */
+typedef struct mg_rollout_trace {   /* every array may be NULL */
+    size_t   struct_size;           /* in: sizeof(mg_rollout_trace) of the caller's header; checked like mg_advance_out's */
+    void*    frames_dev;   /* [steps][num_envs] records of mg_frame_record_bytes each; 16-byte aligned */
+    int32_t* actions_dev;  /* [steps][num_envs * action_dim]: the action played at step t  (mg_advance_traced only) */
+    int32_t* labels_dev;   /* same shape: the teacher's answer at eps = 0 in the state before step t (mg_advance_traced only) */
+    float*   reward_dev;   /* [steps][num_envs] */
+    uint8_t* done_dev;     /* [steps][num_envs] */
+} mg_rollout_trace;
+int mg_advance_traced(mg_env* env, int32_t steps, double eps, uint64_t seed, uint64_t step0, float* gt_dev,
+                      const mg_advance_out* out, const mg_rollout_trace* trace, void* stream);
+int mg_play_traced(mg_env* env, const int32_t* tape_dev, int32_t steps, int mode, const uint8_t* active_dev,
+                   int32_t* steps_played_dev, float* gt_dev, const mg_advance_out* sums,
+                   const mg_rollout_trace* trace, void* stream);
+
 /* The single-instance fast path (BASELINE config C1: gym.make(id), one instance, numpy in / numpy out -- the reference's own loop,
  * /root/reference/bench.py:12-30).  For a handle with num_envs == 1, mg_single_open allocates every per-call buffer in pinned,
  * device-mapped HOST memory and returns the host addresses: the kernels read the action from it and store observation, reward,
@@ -446,7 +487,7 @@ int mg_load_instances(mg_env* env, const int32_t* idx_dev, const int32_t* rec_of
  * records carry no header: keep the value next to the records and compare before drawing (the Python mirror does); drawing a stale record is undefined
  * for its row.  mg_frame_record_bytes is sizeof the family's descriptor: 16 / 64 / 128.
  * OUT OF SCOPE: terminal-observation rows (final_obs_dev and the terminal descriptors behind them); the debug view (mg_render_debug); the MortarMayhemB
- * ids' vector observation; descriptor traces out of mg_play / mg_advance (their in-launch forms keep no descriptor per step).
+ * ids' vector observation.  (Descriptor traces out of mg_play / mg_advance: mg_play_traced / mg_advance_traced, above.)
  * mg_debug_counter "frame_saves" / "frame_draws" count the calls with count > 0, on the host.  MG_STATE_VERSION is unchanged: no state is added.
  * Errors (-1): before the first mg_reset / mg_set_state; a geometry option set since the last reset; a NULL or misaligned rec_dev / obs_dev; count < 0;
  * n_records < 1 with count > 0; an unknown format; pick_dev == NULL with count > n_records; n_records or count > INT32_MAX. */
@@ -577,7 +618,9 @@ int mg_enable_peer_access(int device, int peer_device);
  * has the form): steps mg_play took inside mortar_play_kernel; the steps of its loop form count as "headless_steps" and, where a mask applied,
  * "masked_steps".  "instance_saves" / "instance_loads" (every id):
  * mg_save_instances / mg_load_instances calls of this handle with count > 0, counted on the host.  "frame_saves" / "frame_draws" (every id): the same
- * for mg_save_frames / mg_draw_frames.  Unknown name: -1.  Synchronous. */
+ * for mg_save_frames / mg_draw_frames.  "traced_steps" / "traced_fused_steps" (every id; only the mortar family has the in-launch form): steps of
+ * mg_advance_traced / mg_play_traced calls that came with a trace, and those of them taken inside mortar_advance_traced_kernel / mortar_play_traced_kernel.
+ * Unknown name: -1.  Synchronous. */
 int mg_debug_counter(mg_env* env, const char* name, int64_t* value);
 
 /* Test hook: copy the numpy-compatible PCG64 words of instance i to host:
