@@ -28,6 +28,7 @@ struct mg_env {
     int64_t final_obs_generic_steps = 0;  // mg_debug_counter: mg_step calls that kept terminal observations on the generic path (see mg_step)
     int64_t masked_steps = 0;          // mg_debug_counter: mg_step_masked calls with active_dev != NULL
     int64_t headless_steps = 0;        // mg_debug_counter: mg_step calls with obs_dev == NULL, and the steps of mg_advance's loop form
+    int64_t final_frame_steps = 0;     // mg_debug_counter: mg_step / mg_step_masked calls with mg_info_buffers.final_frames_dev
     int64_t advance_fused_steps = 0;   // mg_debug_counter: steps mg_advance took inside a family's own launches (Family::advance)
     // mg_advance: what the loop of its definition passes from launch to launch, allocated at the handle's first call (include/memgym.h)
     struct Advance {
@@ -36,7 +37,7 @@ struct mg_env {
         mg::DevArray<float> reward, aux[MG_INFO_SLOTS];
         mg::DevArray<uint8_t> done;
         mg::DevArray<double> reward64, ep_reward;
-        mg_info_buffers ib;
+        mg_info_dev ib;
     } adv;
     int64_t play_fused_steps = 0;      // mg_debug_counter: steps mg_play took inside a family's own launches (Family::play)
     int64_t traced_steps = 0, traced_fused_steps = 0;  // mg_debug_counter: steps of mg_advance_traced / mg_play_traced calls with a trace; those taken in-launch
@@ -47,7 +48,7 @@ struct mg_env {
         mg::DevArray<int32_t> ep_length;
         mg::DevArray<float> reward, aux[MG_INFO_SLOTS];
         mg::DevArray<double> reward64, ep_reward;
-        mg_info_buffers ib;
+        mg_info_dev ib;
     } ply;
     // mg_save_instances / mg_load_instances: the handle's number in this process (mg_instance_layout), the host-side counters, and what a load passes
     // from its claim launch to the launches behind it, allocated at the handle's first load (include/memgym.h)
@@ -77,24 +78,6 @@ struct mg_env {
 };
 
 namespace {
-// mg_info_buffers as the caller's header laid it out (include/memgym.h: struct_size)
-constexpr size_t INFO_SIZE_MIN = offsetof(mg_info_buffers, final_obs_dev);  // the episode-record pointers every layout has
-mg_info_buffers read_info(const mg_info_buffers* info) {
-    mg_info_buffers ib;
-    memset(&ib, 0, sizeof(ib));
-    if (!info) return ib;
-    const size_t sz = info->struct_size;
-    // A caller built against the header of round 2 (no struct_size member) has a device POINTER in this place: 8-aligned and huge.
-    // Nothing larger than this build's struct plus room for a few future members is a layout of include/memgym.h.
-    constexpr size_t INFO_SIZE_MAX = sizeof(mg_info_buffers) + 16 * sizeof(void*);
-    if (sz < INFO_SIZE_MIN || sz > INFO_SIZE_MAX || sz % sizeof(void*) != 0)
-        throw std::runtime_error("mg_step: mg_info_buffers.struct_size = " + std::to_string(sz) + " is not a layout of include/memgym.h (" +
-                                 std::to_string(sizeof(mg_info_buffers)) + " in this build); set it to sizeof(mg_info_buffers)");
-    memcpy(&ib, info, sz < sizeof(ib) ? sz : sizeof(ib));  // a shorter (older) struct: the fields it lacks stay NULL
-    ib.struct_size = sizeof(ib);
-    return ib;
-}
-
 struct StateHeader {
     char magic[8];
     uint32_t version, num_envs;
@@ -382,12 +365,17 @@ namespace {
 void step_call(mg_env* env, const char* who, const int32_t* actions_dev, const uint8_t* active_dev, void* obs_dev, float* reward_dev, uint8_t* done_dev,
                float* gt_dev, const mg_info_buffers* info, int autoreset, hipStream_t st) {
     if (!actions_dev || !reward_dev || !done_dev) throw std::runtime_error(std::string(who) + ": NULL buffer");
-    const mg_info_buffers ib = read_info(info);
+    const mg::InfoArgs ia = mg::read_info(info);
+    if (const char* no = mg::final_frames_refusal(ia, !obs_dev)) throw std::runtime_error(std::string(who) + ": " + no);
+    const mg_info_dev& ib = ia.dev;
     mg::Family* f = env->fam;
-    if (!obs_dev) {  // a headless step: the family's plain arrangement without its raster launch
-        if (ib.final_obs_dev) throw std::runtime_error(std::string(who) + ": obs_dev is NULL (a headless step) together with final_obs_dev: terminal observations are frames");
-        f->step(actions_dev, active_dev, nullptr, reward_dev, done_dev, gt_dev, &ib, autoreset, st);
-        ++env->headless_steps;
+    if (!obs_dev || ia.final_frames) {  // a headless step: the family's plain arrangement without its raster launch
+        // (with final_frames_dev: the RECORDS form of its step kernel keeps the terminal frames' descriptors; a drawn call is that arrangement and the
+        // family's dense raster launch behind it -- the plain arrangement, include/memgym.h)
+        f->step(actions_dev, active_dev, nullptr, reward_dev, done_dev, gt_dev, &ib, autoreset, st, ia.final_frames);
+        if (ia.final_frames) ++env->final_frame_steps;
+        if (!obs_dev) ++env->headless_steps;
+        else f->raster_only(obs_dev, active_dev, st);
         if (active_dev) ++env->masked_steps;
         if (ib.gt64_dev) f->ground_truth64(ib.gt64_dev, st, active_dev);
         return;
@@ -439,7 +427,7 @@ int mg_expert_actions(mg_env* env, double eps, uint64_t seed, uint64_t step, int
 }  // extern "C"
 // One step of mg_advance's loop form into the call's sums (the three families share it): row i of the step's reward64 / done / episode
 // record, added to -- at the call's first step: stored as -- sum i.  The same additions in the same order as mortar_advance_kernel's.
-__global__ __launch_bounds__(256) void advance_accumulate_kernel(int n, int first, mg_info_buffers ib, const uint8_t* __restrict__ done, mg_advance_out o) {
+__global__ __launch_bounds__(256) void advance_accumulate_kernel(int n, int first, mg_info_dev ib, const uint8_t* __restrict__ done, mg_advance_out o) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const bool d = done[i] != 0;
@@ -564,7 +552,7 @@ int mg_advance_traced(mg_env* env, int32_t steps, double eps, uint64_t seed, uin
 }  // extern "C"
 // One step of mg_play's loop form: advance_accumulate_kernel's additions in its order (a paused instance's rows are the zeros of the masked step: its sums
 // stay 0), then the step counts where the instance was alive, and MG_PLAY_EPISODE: an instance that has just finished is alive no longer.
-__global__ __launch_bounds__(256) void play_accumulate_kernel(int n, int first, int episode, mg_info_buffers ib, const uint8_t* __restrict__ done, uint8_t* alive,
+__global__ __launch_bounds__(256) void play_accumulate_kernel(int n, int first, int episode, mg_info_dev ib, const uint8_t* __restrict__ done, uint8_t* alive,
                                                               int32_t* played, mg_advance_out o) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -898,7 +886,7 @@ int mg_single_step(mg_env* env, int32_t a0, int32_t a1, void* stream) {
         int32_t* act = (int32_t*)(S.host + S.o_action);
         act[0] = a0;
         act[1] = a1;
-        mg_info_buffers ib;
+        mg_info_dev ib;
         memset(&ib, 0, sizeof(ib));
         ib.struct_size = sizeof(ib);
         ib.ep_reward_dev = (double*)(S.dev + S.o_ep_reward);
@@ -1062,6 +1050,10 @@ int mg_debug_counter(mg_env* env, const char* name, int64_t* value) {
         }
         if (std::string(name) == "masked_steps") {  // every id: counted in this file
             *value = env->masked_steps;
+            return;
+        }
+        if (std::string(name) == "final_frame_steps") {  // every id: counted in this file
+            *value = env->final_frame_steps;
             return;
         }
         if (!env->fam->debug_counter(name, value)) throw std::runtime_error(std::string("mg_debug_counter: no counter named ") + name + " for " + env->id);

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/memgym.h"
+#include "mg_info.hpp"
 #include "mg_lab.hpp"
 #include "mg_launch.hpp"
 #include "mg_device.hpp"
@@ -65,7 +66,7 @@ __device__ __forceinline__ void queue_leave(int* left, int participants, int* co
 }
 // mg_step_masked, an instance whose active flag is 0, from its own lane of the MASKED form of a step kernel: the step's outputs that stay usable as
 // masks and sums without another look at the flags are zeroed -- plain stores -- and nothing else of the instance is read or written.
-__device__ __forceinline__ void masked_out(int i, float* reward_out, uint8_t* done_out, const mg_info_buffers& info) {
+__device__ __forceinline__ void masked_out(int i, float* reward_out, uint8_t* done_out, const mg_info_dev& info) {
     reward_out[i] = 0.0f;
     done_out[i] = 0;
     if (info.reward64_dev) info.reward64_dev[i] = 0.0;
@@ -224,7 +225,7 @@ struct AdvanceArgs {
     float* reward;
     uint8_t* done;
     float* gt;  // the caller's, or NULL
-    mg_info_buffers info;
+    mg_info_dev info;
     mg_advance_out out;
 };
 
@@ -242,7 +243,7 @@ struct PlayArgs {
     uint8_t* done;
     uint8_t* alive;
     float* gt;  // the caller's, or NULL
-    mg_info_buffers info;
+    mg_info_dev info;
     mg_advance_out out;
 };
 
@@ -293,8 +294,11 @@ class Family {
     // frames, the descriptors included, is what a drawn step of the same handle leaves (info->final_obs_dev is NULL then: mg_step refuses the pair)
     // active != NULL: a MASKED step (include/memgym.h: mg_step_masked) -- the arrangement of a headless step with the MASKED form of its step kernel, which
     // leaves the instances with active[i] == 0 alone but for their zeroed reward / done, then, with obs, masked_frames(): the active instances' frames
+    // final_frames != NULL: TERMINAL FRAME RECORDS (include/memgym.h: mg_info_buffers.final_frames_dev) -- obs is NULL (mg_api.hip draws behind the call), the
+    // RECORDS form of the (masked) step kernel stores the descriptor of the frame an instance ended on, as it is before any reset, to row i of
+    // final_frames (frame_rows().second bytes each), in the same number of launches; rows of instances that did not finish are not written
     virtual void step(const int32_t* actions, const uint8_t* active, void* obs, float* reward, uint8_t* done, float* gt,
-                      const mg_info_buffers* info, int autoreset, hipStream_t s) = 0;
+                      const mg_info_dev* info, int autoreset, hipStream_t s, void* final_frames = nullptr) = 0;
     // mg_advance: true = the family has run the loop of include/memgym.h's definition inside launches of its own (the mortar family:
     // mortar_advance_kernel); false = it has no such form (or the lab build switched it off) and nothing happened: mg_api.hip runs the loop.
     virtual bool advance(const AdvanceArgs& /*v*/, hipStream_t /*s*/) { return false; }
@@ -364,9 +368,9 @@ class Family {
         if (!seeds && !seeded_) throw std::runtime_error("reset(seed=None) before any seeded reset");
     }
     // head of every step(): the caller's info buffers, all null where it passed none
-    mg_info_buffers begin_step(const mg_info_buffers* info) const {
+    mg_info_dev begin_step(const mg_info_dev* info) const {
         if (dirty_) throw std::runtime_error("options that change geometry need a reset before the next step");
-        mg_info_buffers ib;
+        mg_info_dev ib;
         memset(&ib, 0, sizeof(ib));
         if (info) ib = *info;
         return ib;

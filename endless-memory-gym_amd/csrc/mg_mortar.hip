@@ -259,14 +259,14 @@ class MortarFamily : public Family {
                      [&] { raster(obs, s); });
     }
 
-    void step(const int32_t* actions, const uint8_t* active, void* obs, float* reward, uint8_t* done, float* gt, const mg_info_buffers* info,
-              int autoreset, hipStream_t s) override {
+    void step(const int32_t* actions, const uint8_t* active, void* obs, float* reward, uint8_t* done, float* gt, const mg_info_dev* info,
+              int autoreset, hipStream_t s, void* final_frames) override {
         struct Consume {  // want_done_flag() holds for this call only, whichever way it ends
             uint32_t*& flag;
             ~Consume() { flag = nullptr; }
         } consume{flag_dev_};
         flag_stored_ = false;
-        const mg_info_buffers ib = begin_step(info);
+        const mg_info_dev ib = begin_step(info);
         sets_.upload(s);
         const MortarStepArgs sa{P_, n_, io(), actions, reward, done, gt_dim() ? gt : nullptr, ib, autoreset, handover_.p, nullptr};
         // one launch: mortar_step_raster_kernel (handles with ONE option set: the per-set step code reads its parameters from memory)
@@ -306,7 +306,12 @@ class MortarFamily : public Family {
         prof.begin(0, s);
         const int sb = step_block(256);
         with_bool(sets_.per_set(), [&](auto PS) {
-            if (active) launch(mortar_step_masked_kernel<decltype(PS)::value>, dim3((n_ + sb - 1) / sb), dim3(sb), 0, s, sa, active);
+            if (final_frames) {  // (terminal frame records: the RECORDS forms of the same two kernels)
+                with_bool(active != nullptr, [&](auto MASKED) {
+                    launch(mortar_step_records_kernel<decltype(PS)::value, decltype(MASKED)::value>, dim3((n_ + sb - 1) / sb), dim3(sb), 0, s, sa, active,
+                           (MortarDesc*)final_frames);
+                });
+            } else if (active) launch(mortar_step_masked_kernel<decltype(PS)::value>, dim3((n_ + sb - 1) / sb), dim3(sb), 0, s, sa, active);
             else launch(mortar_step_kernel<decltype(PS)::value>, dim3((n_ + sb - 1) / sb), dim3(sb), 0, s, sa);
         });
         end_logic(s);

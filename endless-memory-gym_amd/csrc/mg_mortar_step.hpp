@@ -158,9 +158,11 @@ __global__ __launch_bounds__(256) void mortar_reset_kernel(MortarParams P0, int 
 // publishes the descriptor of its TERMINAL frame in a.tdesc[i] (a word of the same layout) before it resets, and says so in the reset frame's
 // hand-over word (ring_on, a field only the debug view uses otherwise): the frame workgroup draws the terminal frame into final_obs_dev first.
 // ORDERED: every store of the lane in front of the hand-over word is complete before the word leaves (see there).
-template <bool FUSED, bool CLAIM = false, bool PS = false, bool FINAL = false, bool ORDERED = false>
+// RECORDS (mg_info_buffers.final_frames_dev, the two-launch / headless forms): an instance that finishes stores the descriptor of its TERMINAL frame -- the
+// one the else branch at the end builds, before any reset -- to final_frames[i] as one 16-byte store; the rows of the others are not written.
+template <bool FUSED, bool CLAIM = false, bool PS = false, bool FINAL = false, bool ORDERED = false, bool RECORDS = false>
 __device__ __forceinline__ void mortar_step_body(int i, const MortarStepArgs& a, uint32_t epoch, uint32_t* claim_word = nullptr,
-                                                 uint32_t ticket = 0u, const int32_t* actions_row = nullptr) {
+                                                 uint32_t ticket = 0u, const int32_t* actions_row = nullptr, MortarDesc* final_frames = nullptr) {
     uint32_t claimed_by = 0u;
     if constexpr (CLAIM) {
         claimed_by = ticket + 1u;  // lanes other than the wave's first: any value but the ticket
@@ -173,7 +175,7 @@ __device__ __forceinline__ void mortar_step_body(int i, const MortarStepArgs& a,
     float* const reward_out = a.reward_out;
     uint8_t* const done_out = a.done_out;
     float* const gt = a.gt;
-    const mg_info_buffers& info = a.info;
+    const mg_info_dev& info = a.info;
     const int autoreset = a.autoreset;
     // the action is requested together with the state record (read where it is used -- behind a test of the state -- it was
     // a second memory round trip at the head of the kernel)
@@ -375,6 +377,18 @@ __device__ __forceinline__ void mortar_step_body(int i, const MortarStepArgs& a,
     MortarDesc d;
     memset(&d, 0, sizeof(d));
     d.glyph_x0 = (int16_t)P.glyph_x0;
+    if constexpr (RECORDS) {
+        if (done) {  // the terminal frame (the else branch below, which an auto-reset replaces), kept as its descriptor
+            MortarDesc td = d;
+            const int tcx = s.disp_is_agent ? s.ax : s.disp_x, tcy = s.disp_is_agent ? s.ay : s.disp_y;
+            td.sx = (int16_t)(tcx - P.sprite_dim / 2);
+            td.sy = (int16_t)(tcy - P.sprite_dim / 2);
+            td.sprite = s.disp_sprite;
+            td.glyph = glyph;
+            td.tmpl = (uint16_t)((s.tiles_on && P.visual_feedback) ? 1 + s.tx * P.N + s.ty : 0);
+            final_frames[i] = td;
+        }
+    }
     if (done && autoreset) {
         if constexpr (FINAL) {  // the terminal frame (the else branch below) as a hand-over word of its own, epoch 0: read only behind ring_on
             const int tcx = s.disp_is_agent ? s.ax : s.disp_x, tcy = s.disp_is_agent ? s.ay : s.disp_y;
@@ -426,6 +440,16 @@ __global__ __launch_bounds__(256) void mortar_step_masked_kernel(MortarStepArgs 
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.n) return;
     if (active[i]) mortar_step_body<false, false, PS>(i, a, 0u);
+    else masked_out(i, a.reward_out, a.done_out, a.info);
+}
+
+// The RECORDS forms of the two kernels above (mg_info_buffers.final_frames_dev): the lane of an instance that finishes keeps the terminal frame's descriptor in
+// the caller's row.  The row pointer is an argument of these forms alone: MortarStepArgs is what it was for every other kernel.
+template <bool PS, bool MASKED>
+__global__ __launch_bounds__(256) void mortar_step_records_kernel(MortarStepArgs a, const uint8_t* __restrict__ active, MortarDesc* __restrict__ final_frames) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.n) return;
+    if (!MASKED || active[i]) mortar_step_body<false, false, PS, false, false, true>(i, a, 0u, nullptr, 0u, nullptr, final_frames);
     else masked_out(i, a.reward_out, a.done_out, a.info);
 }
 }  // namespace mg

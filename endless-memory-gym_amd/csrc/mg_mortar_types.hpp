@@ -86,7 +86,7 @@ struct MortarStepArgs {
     float* reward_out;
     uint8_t* done_out;
     float* gt;
-    mg_info_buffers info;
+    mg_info_dev info;
     int autoreset;
     uint64_t* handover;  // one-launch step: [N] hand-over words (mg_mortar_handover.hpp), step lane -> frame workgroup of the same launch
     uint64_t* tdesc;     // FINAL form of the one-launch step (terminal observations kept): [N] words of the terminal frames (same layout, epoch 0)

@@ -407,14 +407,23 @@ class MysteryFiniteFamily final : public MysteryFamily {
         draw_reset_frames(mask, obs, s);
     }
 
-    void step(const int32_t* actions, const uint8_t* active, void* obs, float* reward, uint8_t* done, float* gt, const mg_info_buffers* info,
-              int autoreset, hipStream_t s) override {
-        const mg_info_buffers ib = begin_step(info);
+    void step(const int32_t* actions, const uint8_t* active, void* obs, float* reward, uint8_t* done, float* gt, const mg_info_dev* info,
+              int autoreset, hipStream_t s, void* final_frames) override {
+        const mg_info_dev ib = begin_step(info);
         prof.begin(0, s);
         // (per-instance option sets: only this kernel has a <PS> form -- the raster launch's path service reads nothing of the options)
         // (a headless step, obs == NULL: the paths are generated in the step kernel -- there is no raster launch to serve them)
         const int defer = (obs && !active && autoreset && !big_sprites_) ? defer_mode() : 0;
         sets_.upload(s);
+        if (final_frames) {  // terminal frame records (obs == NULL): the RECORDS form of the step kernel, masked or not, with the paths generated in it
+            with_bool(sets_.per_set(), [&](auto PS) {
+                with_bool(active != nullptr, [&](auto MASKED) {
+                    launch(mystery_step_records_kernel<decltype(PS)::value, decltype(MASKED)::value>, dim3(blocks()), dim3(256), WS_BYTES, s, P_, io(), actions, active,
+                           reward, done, ib, autoreset, lpw(), (MysteryDesc*)final_frames);
+                });
+            });
+            return plain_frames(obs, s, active);
+        }
         if (active) {  // a masked step: the MASKED form of the step kernel with the paths generated in it, then the active instances' frames
             with_bool(sets_.per_set(), [&](auto PS) {
                 launch(mystery_step_masked_kernel<decltype(PS)::value>, dim3(blocks()), dim3(256), WS_BYTES, s, P_, io(), actions, active, reward, done, ib, autoreset, lpw());
@@ -542,7 +551,7 @@ class MysteryEndlessFamily final : public MysteryFamily {
         if (dirty_) rebuild();
         require_seeded(seeds);
         if (seeds) seeded_ = true;
-        mg_info_buffers none;
+        mg_info_dev none;
         memset(&none, 0, sizeof(none));
         // a masked reset(seed=None) of a handle whose steps run the fused arrangement: reset like the auto-reset step resets (lazy
         // segments, records ahead of time: emp_masked_reset_kernel); lab MEMGYM_EMP_MASKED_FAST=0: through the queue server like any other
@@ -567,9 +576,9 @@ class MysteryEndlessFamily final : public MysteryFamily {
         draw_reset_frames(mask, obs, s);
     }
 
-    void step(const int32_t* actions, const uint8_t* active, void* obs, float* reward, uint8_t* done, float* gt, const mg_info_buffers* info,
-              int autoreset, hipStream_t s) override {
-        const mg_info_buffers ib = begin_step(info);
+    void step(const int32_t* actions, const uint8_t* active, void* obs, float* reward, uint8_t* done, float* gt, const mg_info_dev* info,
+              int autoreset, hipStream_t s, void* final_frames) override {
+        const mg_info_dev ib = begin_step(info);
         prof.begin(0, s);
         // lazy initial segments need the fused launch (its frame workgroups carry the background jobs); any other path
         // first generates what earlier fused steps left owed
@@ -592,6 +601,19 @@ class MysteryEndlessFamily final : public MysteryFamily {
         const bool keep_final = autoreset && ib.final_obs_dev && fused && keeps_final_obs(s);
         // (three of the four <PS, FINAL> forms exist: terminal observations are kept by handles with one option set only)
         auto step_launch = [&](auto kernel) { launch(kernel, dim3((n_ + sb - 1) / sb), dim3(sb), 0, s, P_, io(), actions, reward, done, gt, ib, autoreset); };
+        if (final_frames) {  // terminal frame records (obs == NULL, never fused): the RECORDS forms of the step kernel and of the queue server, whose tdesc is the caller's rows
+            MysteryIO rio = io();
+            rio.tdesc = (MysteryDesc*)final_frames;
+            with_bool(sets_.per_set(), [&](auto PS) {
+                with_bool(active != nullptr, [&](auto MASKED) {
+                    launch(emp_step_records_kernel<decltype(PS)::value, decltype(MASKED)::value>, dim3((n_ + sb - 1) / sb), dim3(sb), 0, s, P_, rio, actions, active,
+                           reward, done, gt, ib, autoreset);
+                });
+                launch(emp_serve_records_kernel<decltype(PS)::value>, dim3(servers(false)), dim3(256), WS_BYTES, s, P_, rio, reward, done, gt, ib, autoreset);
+            });
+            plain_frames(obs, s, active);
+            return;
+        }
         if (active) {
             with_bool(sets_.per_set(), [&](auto PS) {
                 launch(emp_step_masked_kernel<decltype(PS)::value>, dim3((n_ + sb - 1) / sb), dim3(sb), 0, s, P_, io(), actions, active, reward, done, gt, ib, autoreset);
@@ -714,7 +736,7 @@ class MysteryEndlessFamily final : public MysteryFamily {
         return want < cap ? want : cap;
     }
     // the queue server as a launch of its own: `all` = every instance (a full reset), else the queued ones
-    void serve(bool all, const int64_t* seeds, float* reward, uint8_t* done, float* gt, const mg_info_buffers& ib, int autoreset, hipStream_t s) {
+    void serve(bool all, const int64_t* seeds, float* reward, uint8_t* done, float* gt, const mg_info_dev& ib, int autoreset, hipStream_t s) {
         with_bool(sets_.per_set(), [&](auto PS) {
             launch(emp_serve_kernel<decltype(PS)::value>, dim3(servers(all)), dim3(256), WS_BYTES, s, P_, io(), seeds, all ? 1 : 0, reward, done, gt, ib, autoreset);
         });

@@ -433,7 +433,7 @@ static __device__ unsigned long long g_lab_step_clock[12 * 4096];
 // such an instance -- one copy of emp_fill_desc either way, and for FINAL = false the code of rounds 3-5 (a loop of exactly one pass).
 template <bool OWN_RESET, bool WHOLE_DESC = false, bool FINAL = false>
 __device__ bool emp_step_b(const MysteryParams& P, const MysteryIO& io, int i, MysteryCore& s, int nx, int ny, float* reward_out,
-                           uint8_t* done_out, float* gt, const mg_info_buffers& info, int autoreset, MysteryDesc& d, bool cap = false) {
+                           uint8_t* done_out, float* gt, const mg_info_dev& info, int autoreset, MysteryDesc& d, bool cap = false) {
     typedef uint32_t q4 __attribute__((ext_vector_type(4)));
     double reward = 0.0;
     bool done = cap;  // cap: the segment store is full and the reference would append now (emp_step_a) -- the episode ends here
@@ -659,7 +659,7 @@ __device__ bool emp_step_b(const MysteryParams& P, const MysteryIO& io, int i, M
 // and / or "reset" (three segments), state, stream and frame descriptor written back.
 template <bool FINAL = false>
 __device__ void emp_serve_entry(const MysteryParams& P, const MysteryIO& io, const PathWS& W, int entry, const int64_t* seeds, float* reward_out,
-                                uint8_t* done_out, float* gt, const mg_info_buffers& info, int autoreset, MysteryDesc* d_out = nullptr) {
+                                uint8_t* done_out, float* gt, const mg_info_dev& info, int autoreset, MysteryDesc* d_out = nullptr) {
     const bool me = (threadIdx.x & 63) == 0;
     const int i = entry & EMP_Q_INST;
     float* gti = gt ? gt + 3 * i : nullptr;

@@ -14,7 +14,7 @@ namespace mg {
 
 template <bool PS, bool FINAL = false>
 __global__ __launch_bounds__(256) void emp_step_kernel(MysteryParams P0, MysteryIO io, const int32_t* actions, float* reward_out,
-                                                       uint8_t* done_out, float* gt, mg_info_buffers info, int autoreset) {
+                                                       uint8_t* done_out, float* gt, mg_info_dev info, int autoreset) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= P0.n) return;
     // (fewer instance-carrying lanes per wave -- 32 / 16 / 8, as the finite variants' kernel has them -- measured slower: 34-40 us
@@ -71,7 +71,7 @@ __global__ __launch_bounds__(256) void emp_step_kernel(MysteryParams P0, Mystery
 // with the body moved into a function the compiler schedules the existing forms differently, and those stay the code they were.)
 template <bool PS>
 __global__ __launch_bounds__(256) void emp_step_masked_kernel(MysteryParams P0, MysteryIO io, const int32_t* actions, const uint8_t* __restrict__ active,
-                                                              float* reward_out, uint8_t* done_out, float* gt, mg_info_buffers info, int autoreset) {
+                                                              float* reward_out, uint8_t* done_out, float* gt, mg_info_dev info, int autoreset) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= P0.n) return;
     if (!active[i]) return masked_out(i, reward_out, done_out, info);
@@ -90,6 +90,41 @@ __global__ __launch_bounds__(256) void emp_step_masked_kernel(MysteryParams P0, 
     if (emp_step_b<!PS, true, false>(P, io, i, s, nx, ny, reward_out, done_out, gt ? gt + 3 * i : nullptr, info, autoreset, d, (ra & EMP_CAP) != 0)) {
         queue_push(io.queue, &io.qctr[QC_COUNT], P.n, i, io.err);
         d.valid = DESC_QUEUED;
+    }
+    io.core[i] = s;
+    io.desc[i] = d;
+}
+
+// The RECORDS form (mg_info_buffers.final_frames_dev) of the step kernel as a headless or masked step launches it -- the plain arrangement, P.lazy == 0.  The rows are
+// io.tdesc: the host hands this form (and emp_serve_records_kernel behind it) an io whose tdesc IS the caller's buffer, so that the FINAL tail of emp_step_b -- the
+// terminal descriptor first, before anybody resets the instance -- stores straight into the caller's row.  That tail keeps the row only for an instance that is reset
+// in this call; with autoreset == 0 the descriptor the step leaves IS the terminal one, and the lane stores it where its own done flag says so.  An instance whose step
+// needs a new segment first finishes in the queue server: its row is written there.
+template <bool PS, bool MASKED>
+__global__ __launch_bounds__(256) void emp_step_records_kernel(MysteryParams P0, MysteryIO io, const int32_t* actions, const uint8_t* __restrict__ active,
+                                                               float* reward_out, uint8_t* done_out, float* gt, mg_info_dev info, int autoreset) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= P0.n) return;
+    if (MASKED && !active[i]) return masked_out(i, reward_out, done_out, info);
+    const MysteryParams& P = PS ? io.sets[set_index(io.set_of, i)] : P0;
+    const int act = actions[i];
+    MysteryCore s = load_core(&io.core[i]);
+    int nx = 0, ny = 0;
+    const int ra = emp_step_a(P, i, s, act, nx, ny, io.err);
+    if (ra & EMP_DUE) {  // the agent entered the last-but-one segment: the rest of its step needs the new one (emp_serve_records_kernel)
+        queue_push(io.queue, &io.qctr[QC_COUNT], P.n, i | EMP_Q_SEGMENT, io.err);
+        io.core[i] = s;
+        io.desc[i].valid = DESC_QUEUED;  // (the rest of the descriptor is last step's)
+        return;
+    }
+    MysteryDesc d;
+    // (OWN_RESET = false: this form only ever runs the plain arrangement, where no instance resets itself from a record made ahead of time -- without that
+    // code and its batch of loads the kernel needs 188 VGPRs, with it 262)
+    if (emp_step_b<false, true, true>(P, io, i, s, nx, ny, reward_out, done_out, gt ? gt + 3 * i : nullptr, info, autoreset, d, (ra & EMP_CAP) != 0)) {
+        queue_push(io.queue, &io.qctr[QC_COUNT], P.n, i, io.err);
+        d.valid = DESC_QUEUED;
+    } else if (!autoreset && done_out[i]) {
+        io.tdesc[i] = d;
     }
     io.core[i] = s;
     io.desc[i] = d;
@@ -199,7 +234,7 @@ __global__ __launch_bounds__(64) void emp_reset_lanes_kernel(MysteryParams P, My
 // all != 0: mg_reset of every instance (entry k = instance k, seeds may be given); otherwise the queue is drained
 template <bool PS>
 __global__ __launch_bounds__(256) void emp_serve_kernel(MysteryParams P, MysteryIO io, const int64_t* seeds, int all, float* reward_out,
-                                                        uint8_t* done_out, float* gt, mg_info_buffers info, int autoreset) {
+                                                        uint8_t* done_out, float* gt, mg_info_dev info, int autoreset) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     path_ws_init(smem);
     const PathWS W{smem, io.jump, io.stats};
@@ -213,6 +248,34 @@ __global__ __launch_bounds__(256) void emp_serve_kernel(MysteryParams P, Mystery
         const int entry = all ? idx : bcast(io.queue[idx], 0);
         emp_serve_entry(PS ? io.sets[set_index(io.set_of, entry & EMP_Q_INST)] : P, io, W, entry, seeds, reward_out, done_out, gt, info, autoreset);
         if (me) {
+            idx = waves + atomicAdd(&io.qctr[QC_HEAD], 1);
+        }
+        idx = bcast(idx, 0);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) queue_leave(&io.qctr[QC_LEFT], (int)gridDim.x, &io.qctr[QC_COUNT], &io.qctr[QC_HEAD]);
+}
+
+// The RECORDS form of the queue server behind emp_step_records_kernel (never `all`: a step's queue): the FINAL form of emp_serve_entry keeps the terminal descriptor of
+// an instance that finishes HERE -- its step needed a new segment first -- in io.tdesc, the caller's rows (see emp_step_records_kernel); with autoreset == 0 the entry's
+// own descriptor is the terminal one.
+template <bool PS>
+__global__ __launch_bounds__(256) void emp_serve_records_kernel(MysteryParams P, MysteryIO io, float* reward_out, uint8_t* done_out, float* gt, mg_info_dev info,
+                                                                int autoreset) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    path_ws_init(smem);
+    const PathWS W{smem, io.jump, io.stats};
+    const bool me = (threadIdx.x & 63) == 0;
+    const int count = queue_count(&io.qctr[QC_COUNT], P.n);
+    const int waves = gridDim.x * (blockDim.x >> 6);
+    int idx = bcast((int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)), 0);
+    while (idx < count) {
+        const int entry = bcast(io.queue[idx], 0);
+        const int i = entry & EMP_Q_INST;
+        MysteryDesc d;
+        emp_serve_entry<true>(PS ? io.sets[set_index(io.set_of, i)] : P, io, W, entry, nullptr, reward_out, done_out, gt, info, autoreset, &d);
+        if (me) {
+            if (!autoreset && (entry & EMP_Q_SEGMENT) && done_out[i]) io.tdesc[i] = d;
             idx = waves + atomicAdd(&io.qctr[QC_HEAD], 1);
         }
         idx = bcast(idx, 0);
@@ -275,7 +338,7 @@ static_assert(LW_BYTES <= v1::RASTER_LDS, "the lane generator's workspace must f
 template <int FMT, bool EMP_NT, bool FINAL = false>
 __global__ __launch_bounds__(256, MG_LAB_EMP_LB) void emp_raster_serve_kernel(const MysteryDesc* __restrict__ descs, RasterAtlas A, void* __restrict__ obs, int n,
                                                                   MysteryParams P, MysteryIO io, float* reward_out, uint8_t* done_out,
-                                                                  float* gt, mg_info_buffers info, int autoreset, int svc, int bgw, int turn) {
+                                                                  float* gt, mg_info_dev info, int autoreset, int svc, int bgw, int turn) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     __shared__ MysteryDesc sdesc[4];
     __shared__ int served[4];

@@ -294,9 +294,9 @@ class SpotFamily : public Family {
         }, [&] { raster(obs, s); });
     }
 
-    void step(const int32_t* actions, const uint8_t* active, void* obs, float* reward, uint8_t* done, float* gt, const mg_info_buffers* info,
-              int autoreset, hipStream_t s) override {
-        const mg_info_buffers ib = begin_step(info);
+    void step(const int32_t* actions, const uint8_t* active, void* obs, float* reward, uint8_t* done, float* gt, const mg_info_dev* info,
+              int autoreset, hipStream_t s, void* final_frames) override {
+        const mg_info_dev ib = begin_step(info);
         sets_.upload(s);
         prof.begin(0, s);
         // (resets served inside the raster launch: handles with ONE option set -- the service code takes its parameters from the launch's arguments)
@@ -311,7 +311,12 @@ class SpotFamily : public Family {
         const dim3 sg((n_ * SLOTS + sb - 1) / sb);
         with_bool(P_.endless, [&](auto EN) {
             with_bool(sets_.per_set(), [&](auto PS) {
-                if (active) launch(spot_step_masked_kernel<decltype(EN)::value, decltype(PS)::value>, sg, dim3(sb), 0, s, sa, active);
+                if (final_frames) {  // (terminal frame records, obs == NULL: the RECORDS forms of the same two kernels; never deferred)
+                    with_bool(active != nullptr, [&](auto MASKED) {
+                        launch(spot_step_records_kernel<decltype(EN)::value, decltype(PS)::value, decltype(MASKED)::value>, sg, dim3(sb), 0, s, sa, active,
+                               (SpotDesc*)final_frames);
+                    });
+                } else if (active) launch(spot_step_masked_kernel<decltype(EN)::value, decltype(PS)::value>, sg, dim3(sb), 0, s, sa, active);
                 else launch(spot_step_kernel<decltype(EN)::value, decltype(PS)::value>, sg, dim3(sb), 0, s, sa);
             });
         });

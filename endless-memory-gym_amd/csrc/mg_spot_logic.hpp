@@ -331,8 +331,14 @@ static __device__ unsigned long long g_lab_spot_clock[10 * 65536];
 #define SPOT_CLOCK_AFTER(slot, ...) do { } while (0)
 #define SPOT_CLOCK_FLAG(f) do { } while (0)
 #endif
-template <bool EN, bool PS>
-__device__ __forceinline__ void spot_step_body(int i, const LaneCtx& L, const SpotStepArgs& a, int* disc_lds, SpotCore* core_lds, const Trig& T) {
+// RECORDS (mg_info_buffers.final_frames_dev; the step kernels proper, never deferred): the 16 lanes of an instance that finishes keep the descriptor of its TERMINAL
+// frame in final_frames[i], composed BEFORE the in-kernel reset touches the state.  The row is written word for word as io.desc[i] stands after the same step
+// without a reset (what mg_save_frames would store): the head by the leader (store_desc_head and the two unused words), the hole words by the slot lanes -- hole
+// `rank` by the lane that has just computed it, the words behind this step's n_holes (stale holes of earlier frames; the composers do not read them) by lanes
+// n_holes .. 15 from a load issued with the step's other loads.  The 16 + 4 stores of a group go to disjoint words of one 128-byte line: nothing orders them.
+template <bool EN, bool PS, bool RECORDS = false>
+__device__ __forceinline__ void spot_step_body(int i, const LaneCtx& L, const SpotStepArgs& a, int* disc_lds, SpotCore* core_lds, const Trig& T,
+                                               SpotDesc* final_frames = nullptr) {
     const int ls = L.ls;
 #ifdef MG_LAB_SPOT_CLOCK
     unsigned long long clk[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -346,7 +352,7 @@ __device__ __forceinline__ void spot_step_body(int i, const LaneCtx& L, const Sp
     float* const reward_out = a.reward_out;
     uint8_t* const done_out = a.done_out;
     float* const gt = a.gt;
-    const mg_info_buffers& info = a.info;
+    const mg_info_dev& info = a.info;
     const int autoreset = a.autoreset, defer = a.defer;
     const int group_shift = L.gshift;  // bit position of this instance's 16 lanes in a wave ballot
     const bool leader = ls == 0;
@@ -368,6 +374,9 @@ __device__ __forceinline__ void spot_step_body(int i, const LaneCtx& L, const Sp
     mine.speed = io.sp_speed[k];
     mine.ang = io.sp_ang[k];
     mine.r = io.sp_r[k];
+    uint32_t rec_stale = 0u, rec_hole = 0u;
+    int rec_rank = -1;
+    if constexpr (RECORDS) rec_stale = io.desc[i].holes[ls];
     g.pin();
 
     // CharacterController.step(action, walkable_rect = (0, 4, 84, 80))
@@ -464,6 +473,10 @@ __device__ __forceinline__ void spot_step_body(int i, const LaneCtx& L, const Sp
             }
         }
         io.desc[i].holes[rank] = pack_hole((int)cx, (int)cy, radius) | ((uint32_t)(p_r >> 7) << 31);
+        if constexpr (RECORDS) {
+            rec_hole = pack_hole((int)cx, (int)cy, radius) | ((uint32_t)(p_r >> 7) << 31);
+            rec_rank = rank;
+        }
         t += mine.speed;
         if (t >= 1.0) t = 1.0;  // = done: removed from the list by the next step
         io.sp_t[k] = t;
@@ -599,6 +612,49 @@ __device__ __forceinline__ void spot_step_body(int i, const LaneCtx& L, const Sp
     // frame; state, stream and the descriptor head (its n_holes are the reset frame's stale holes) are stored as after
     // any other step, exactly what a masked mg_reset(seed = None) would find.
     const bool reset_me = done && autoreset;
+    if constexpr (RECORDS) {
+        if (__builtin_expect(done, 0)) {  // the terminal frame: the else branch below, which an in-kernel reset replaces -- its descriptor alone, none of its stores
+            SpotDesc* const rec = final_frames + i;
+            if (rec_rank >= 0) rec->holes[rec_rank] = rec_hole;
+            if (ls >= nh) rec->holes[ls] = rec_stale;
+            if (leader) {
+                SpotDesc td;
+                memset(&td, 0, sizeof(td));
+                td.valid = 1;
+                td.bg = bg_template(s.pad, s.bg_red);
+                td.sprite = s.rot8;
+                td.sx = (int16_t)(ax - P.sprite_half);
+                td.sy = (int16_t)(ay - P.sprite_half);
+                td.alpha = s.alpha;
+                td.n_holes = (uint8_t)nh;
+                td.exit_stamp = 0xFF;
+                if constexpr (EN) {
+                    td.n_coins = P.coin_enabled ? 1 : 0;
+                    td.coin_above = (uint8_t)(((P.coins_visible || s.coin_t < P.coin_show_duration) ? LAYER_COIN_ABOVE : 0) | P.layer_flags);
+                    td.coins[0] = coin_word(P, s.coin_x, s.coin_y);
+                } else {
+                    td.n_coins = s.n_coins;
+                    td.coin_above = (uint8_t)((P.coins_visible ? LAYER_COIN_ABOVE : 0) | P.layer_flags);
+#pragma unroll
+                    for (int q = 0; q < MAX_COINS; ++q) {
+                        if (q < s.n_coins) {
+                            int cx = (int)(int16_t)(coin_pos[q] & 0xFFFF), cy = (int)(coin_pos[q] >> 16);
+                            td.coins[q] = coin_word(P, cx, cy);
+                        }
+                    }
+                    const int eg = exit_gen_of(s.pad), half = (int)((P.exit_halves >> (8 * eg)) & 0xFFu);
+                    td.exit_stamp = (s.pad & PAD_HAS_EXIT) ? (uint8_t)(ST_EXIT0 + 2 * eg + (s.exit_open ? 1 : 0)) : 0xFF;
+                    td.exit_x = (int16_t)(s.exit_x - half);
+                    td.exit_y = (int16_t)(s.exit_y - half);
+                }
+                SpotCore tb = s;
+                tb.last_pos = shown_last_pos;
+                fill_topbar<EN>(P, tb, td, false, shown0, shown1);
+                store_desc_head(rec, td);
+                reinterpret_cast<uint2*>(rec)[3] = make_uint2(0u, 0u);  // (w6, w7: unused, zero in every descriptor row)
+            }
+        }
+    }
     SPOT_CLOCK(5);
     if (defer && reset_me && leader) queue_push(io.queue, &io.qctr[SQ_COUNT], P.n, i, io.err);
     if (__builtin_expect(reset_me && !defer, 0)) {  // cold: keep the reset code out of the hot instruction stream

@@ -58,6 +58,19 @@ __global__ __launch_bounds__(256) void spot_step_masked_kernel(SpotStepArgs a, c
     else if ((gid & 15) == 0) masked_out(i, a.reward_out, a.done_out, a.info);
 }
 
+// The RECORDS forms of the two kernels above (mg_info_buffers.final_frames_dev): the 16 lanes of an instance that finishes keep the terminal frame's descriptor in the
+// caller's row (spot_step_body<.., RECORDS>).  The row pointer is an argument of these forms alone: SpotStepArgs is what it was for every other kernel.
+template <bool EN, bool PS, bool MASKED>
+__global__ __launch_bounds__(256) void spot_step_records_kernel(SpotStepArgs a, const uint8_t* __restrict__ active, SpotDesc* __restrict__ final_frames) {
+    __shared__ int disc_lds[(256 / 16) * DISC_INTS];
+    __shared__ SpotCore core_lds[256 / 16];
+    const int gid = blockIdx.x * blockDim.x + threadIdx.x;
+    const int i = gid >> 4;
+    if (i >= a.P.n) return;
+    if (!MASKED || active[i]) spot_step_body<EN, PS, true>(i, lane_ctx((int)threadIdx.x), a, disc_lds, core_lds, Trig{a.P.cos_tab, a.P.sin_tab}, final_frames);
+    else if ((gid & 15) == 0) masked_out(i, a.reward_out, a.done_out, a.info);
+}
+
 // The step's raster launch with the put-off resets served inside it: the first workgroups take the queue entries, eight
 // each (the 16 lanes of a quarter wave reset one instance, like spot_reset_kernel; waves 2 and 3 wait), then draw those
 // eight frames; all other workgroups walk the frames of the instances that were not queued (SpotDesc::valid == 1).  The

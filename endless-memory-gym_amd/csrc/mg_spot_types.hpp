@@ -169,7 +169,7 @@ struct SpotStepArgs {
     float* reward_out;
     uint8_t* done_out;
     float* gt;
-    mg_info_buffers info;
+    mg_info_dev info;
     int autoreset, defer;
 };
 

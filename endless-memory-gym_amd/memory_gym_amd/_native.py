@@ -20,7 +20,8 @@ MG_PLAY_THROUGH, MG_PLAY_EPISODE = 0, 1  # include/memgym.h: mg_play's modes
 
 class InfoBuffers(C.Structure):
     _fields_ = [("struct_size", C.c_size_t), ("ep_reward_dev", C.c_void_p), ("ep_length_dev", C.c_void_p), ("aux_dev", C.c_void_p * MG_INFO_SLOTS),
-                ("final_obs_dev", C.c_void_p), ("reward64_dev", C.c_void_p), ("gt64_dev", C.c_void_p), ("capacity_dev", C.c_void_p)]
+                ("final_obs_dev", C.c_void_p), ("reward64_dev", C.c_void_p), ("gt64_dev", C.c_void_p), ("capacity_dev", C.c_void_p),
+                ("final_frames_dev", C.c_void_p)]  # (a library older than the member reads struct_size bytes and ignores what it does not know)
 
 
 class SingleIO(C.Structure):  # include/memgym.h: mg_single_io (host addresses of pinned, device-mapped buffers)

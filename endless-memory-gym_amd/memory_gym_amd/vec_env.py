@@ -335,11 +335,13 @@ class VecMemoryGym:
                    "u8_chw": (4, torch.uint8, (3, 84, 84))}
 
     def __init__(self, env_id, num_envs=1, device=None, render_mode=None, obs_format="u8_xyc", final_observation=False,
-                 obs_buffer=None, obs_placement=None, ground_truth64=False, on_capacity="raise", capacity=None):
+                 obs_buffer=None, obs_placement=None, ground_truth64=False, on_capacity="raise", capacity=None, final_frames=False):
         if env_id not in DEFAULTS:
             raise ValueError("unknown env id %r" % (env_id,))
         if obs_format not in self.OBS_FORMATS:
             raise ValueError("obs_format must be one of %s" % sorted(self.OBS_FORMATS))
+        if final_observation and final_frames:
+            raise ValueError("final_observation=True together with final_frames=True: terminal frames are kept as frames or as records, pick one")
         if not torch.cuda.is_available():
             raise RuntimeError("memory_gym_amd needs a ROCm GPU (MI355X); no CPU fallback exists")
         self.env_id = env_id
@@ -439,6 +441,12 @@ class VecMemoryGym:
         self.on_capacity = on_capacity
         self.capacity_u8 = torch.zeros(N, dtype=torch.uint8, device=dev) if on_capacity == "truncate" else None
         self._info.capacity_dev = self.capacity_u8.data_ptr() if self.capacity_u8 is not None else None
+        # final_frames=True: the same convention WITHOUT frames (include/memgym.h: mg_info_buffers.final_frames_dev) -- the frame an episode ended on is
+        # kept as its frame record, 16 / 64 / 128 bytes, so step(render=False) stays legal; draw_frames(info["final_frames"], pick=...) draws the rows
+        self.final_frames = None
+        if final_frames:
+            self.final_frames = FrameRecords(torch.zeros((N, self.frame_record_bytes), dtype=torch.uint8, device=dev), self.frame_layout())
+            self._info.final_frames_dev = self.final_frames.records.data_ptr()
         self._tolerated = self.CAPACITY_BITS if on_capacity == "truncate" else 0
         self.reset_params = process_reset_params(env_id, None)
         self._applied = dict(DEFAULTS[env_id])
@@ -620,7 +628,10 @@ class VecMemoryGym:
         """Env.step for every instance.  render=False is the HEADLESS step (include/memgym.h: mg_step with obs_dev == NULL): everything but
         the frames -- state, random streams, rewards, dones, infos -- is what the drawn step gives, the first element of the returned tuple
         is None and `obs` keeps its old bytes until redraw(), the next drawn step or a reset.  Terminal observations are frames: a handle
-        made with final_observation=True refuses render=False (ValueError) before anything is stepped.
+        made with final_observation=True refuses render=False (ValueError) before anything is stepped.  A handle made with final_frames=True keeps
+        the frame an episode ended on as a frame RECORD instead (include/memgym.h: mg_info_buffers.final_frames_dev) and steps headless like any other:
+        with auto-reset on, info["final_frames"] is `final_frames` (a FrameRecords [N, frame_record_bytes]), its rows valid where info["done_mask"] is
+        set -- draw_frames(info["final_frames"], pick=idx, obs_format=...) draws them, in any format, whenever training wants them.
         mask: step a SUBSET (include/memgym.h: mg_step_masked) -- a bool or uint8 tensor [N] on the device, or anything torch.as_tensor
         takes; instance i steps iff mask[i] != 0, and its results are those of a handle in which it alone had been stepped by step() with
         the same actions in the same order.  The other instances are left alone: state, random stream and their row of `obs`, of the
@@ -661,6 +672,10 @@ class VecMemoryGym:
         info = dict(self._info_dict)
         if self.final_obs is not None and self.autoreset:  # rows valid where done_mask is set
             info["final_observation"] = self.final_obs
+        if self.final_frames is not None:
+            self.final_frames.layout = self.frame_layout()  # (the rows written by this call are records of the handle as it is now)
+            if self.autoreset:  # rows valid where done_mask is set
+                info["final_frames"] = self.final_frames
         return (self._obs() if render else None), self.reward, self._done_bool, self._truncated, info
 
     def _launch_step(self, a, render=True, m=None):

@@ -27,12 +27,16 @@ except Exception:  # gymnasium is not a dependency of the hot path
 
 
 class GymnasiumVectorEnv(_Base):
-    def __init__(self, env_id, num_envs, device=None, obs_format="u8_xyc", as_numpy=False, on_capacity="raise", capacity=None):
+    def __init__(self, env_id, num_envs, device=None, obs_format="u8_xyc", as_numpy=False, on_capacity="raise", capacity=None, final_frames=False):
         # as_numpy: gymnasium's host-side layout with the reference's dtypes -- rewards and info["ground_truth"] as float64
         # on_capacity="truncate": a sub-environment whose episode this build ended on one of its capacities (VecMemoryGym) comes back with
         # terminations[i] = False and truncations[i] = True, like a time limit; its final_observation / final_info are set as for any end
-        self.env = VecMemoryGym(env_id, num_envs=num_envs, device=device, obs_format=obs_format, final_observation=True,
-                                ground_truth64=bool(as_numpy), on_capacity=on_capacity, capacity=capacity)
+        # final_frames=True: the same convention WITHOUT FRAMES -- step() is the headless step (obs is None; redraw() draws the current frames), and the frame
+        # an episode ended on comes back as its frame record: infos["final_frames"] (a FrameRecords [N, bytes]) with the mask infos["_final_frames"];
+        # final_observations(infos) draws exactly the finished rows when the trainer wants them (the bootstrap value of a truncated episode)
+        self.final_frames = bool(final_frames)
+        self.env = VecMemoryGym(env_id, num_envs=num_envs, device=device, obs_format=obs_format, final_observation=not self.final_frames,
+                                ground_truth64=bool(as_numpy), on_capacity=on_capacity, capacity=capacity, final_frames=self.final_frames)
         self.as_numpy = bool(as_numpy)
         done = False
         if _Base is not object:  # gymnasium 0.29: VectorEnv.__init__(num_envs, observation_space, action_space) batches the spaces
@@ -70,7 +74,7 @@ class GymnasiumVectorEnv(_Base):
         return self._host(obs), self._host(info)
 
     def step(self, actions):
-        obs, reward, done, trunc, info = self.env.step(actions)
+        obs, reward, done, trunc, info = self.env.step(actions, render=not self.final_frames)
         ep = {"reward": info["reward"], "length": info["length"]}
         for nm in self.env.info_names:
             ep[nm] = info[nm]
@@ -80,6 +84,21 @@ class GymnasiumVectorEnv(_Base):
         term = done if self.env.capacity_u8 is None else (done & ~trunc)  # gymnasium: an episode ends EITHER terminated or truncated
         if "capacity_exceeded" in info:
             infos["capacity_exceeded"] = info["capacity_exceeded"]
+        if self.final_frames:  # (records stay on the device whatever as_numpy says: they are drawn from there)
+            infos.update(final_frames=info["final_frames"], _final_frames=done)
+            if not self.as_numpy:
+                infos.update(final_info=ep, _final_info=done)
+                return obs, reward, term, trunc, infos
+            d = done.cpu().numpy()
+            out = self._host({k: v for k, v in infos.items() if k != "final_frames"})
+            out["final_frames"] = infos["final_frames"]
+            if d.any():
+                finfo = np.full(self.num_envs, None, dtype=object)
+                host_ep = {k: v.cpu().numpy() for k, v in ep.items()}
+                for i in np.nonzero(d)[0]:
+                    finfo[i] = {k: (int(v[i]) if k == "length" else float(v[i])) for k, v in host_ep.items()}
+                out.update(final_info=finfo, _final_info=d.copy())
+            return None, self.env.reward64.cpu().numpy(), term.cpu().numpy(), trunc.cpu().numpy(), out
         if not self.as_numpy:
             infos.update(final_observation=info["final_observation"], _final_observation=done, final_info=ep, _final_info=done)
             return obs, reward, term, trunc, infos
@@ -96,6 +115,24 @@ class GymnasiumVectorEnv(_Base):
                 finfo[i] = {k: (int(v[i]) if k == "length" else float(v[i])) for k, v in host_ep.items()}
             out.update(final_observation=fobs, _final_observation=d.copy(), final_info=finfo, _final_info=d.copy())
         return self._host(obs), self.env.reward64.cpu().numpy(), term.cpu().numpy(), trunc.cpu().numpy(), out  # (the reference's Python floats: doubles)
+
+    def final_observations(self, info, out=None, obs_format=None):
+        """The terminal observations of the sub-environments that finished in the step `info` came from, drawn from its frame records (final_frames=True):
+        -> (idx, frames) with idx the finished sub-environments in ascending order (int64 tensor) and frames[j] the observation episode idx[j] ended on, in
+        `obs_format` (default: the handle's) -- one gather-raster launch over exactly those rows (VecMemoryGym.draw_frames); numpy with as_numpy.  Looks at
+        the mask on the host (one synchronisation); out: a tensor [len(idx), ...] to draw into.  No finished sub-environment: (empty idx, None)."""
+        if "final_frames" not in info:
+            raise ValueError("final_observations: the info dict carries no frame records (GymnasiumVectorEnv(final_frames=True))")
+        mask = info["_final_frames"]
+        idx = torch.nonzero(torch.as_tensor(mask, device=self.env.device)).flatten()
+        if idx.numel() == 0:
+            return self._host(idx), None
+        frames = self.env.draw_frames(info["final_frames"], pick=idx.to(torch.int32), out=out, obs_format=obs_format)
+        return self._host(idx), self._host(frames)
+
+    def redraw(self):
+        """VecMemoryGym.redraw: the current observations after headless steps (numpy with as_numpy)."""
+        return self._host(self.env.redraw())
 
     def expert_actions(self, eps=0.0, seed=0, step=None, out=None):
         """The scripted teacher's actions in the current states (VecMemoryGym.expert_actions): what step() takes; numpy with as_numpy."""

@@ -67,6 +67,25 @@ typedef struct mg_info_buffers {
      * (a reset follows under autoreset); the sticky error bit (mg_poll_errors: 4, 8, 32, 1) is raised as before, so a caller that
      * ignores this array still hears about it.  With it a trainer treats the instance as truncated and goes on with the batch. */
     uint8_t* capacity_dev;
+    /* Optional: TERMINAL FRAME RECORDS -- the frame an episode ended on, kept as a frame record (FRAME RECORDS, below) instead of a frame:
+     * [num_envs] records of mg_frame_record_bytes each, 16-byte aligned.  DEFINITION: where mg_step / mg_step_masked returns done_dev[i] == 1, row i
+     * holds the frame descriptor of instance i as it was BEFORE ANY RESET OF THIS CALL: mg_draw_frames(env, final_frames_dev, num_envs, &i, 1, F, row,
+     * stream) writes exactly the bytes row i of final_obs_dev gets from a drawn mg_step of a twin handle in format F with the same history.  Where
+     * done_dev[i] == 0 -- instances outside active_dev included -- row i is NOT written.  autoreset 0 and 1; with 0 the row equals what mg_save_frames
+     * stores after the call.  Everything else the call leaves -- state, PCG64 streams, the descriptors mg_render / mg_save_frames read, reward, done,
+     * episode records, ground truth, error bits -- is bit for bit what the same call without this member leaves.  The rows have the validity of frame
+     * records: keep mg_frame_layout next to them.
+     * This is what lets a trainer in the gymnasium vector convention step HEADLESS: obs_dev == NULL with final_frames_dev is legal (with final_obs_dev
+     * it stays refused: terminal observations are frames), masked or not, one option set or several, every observation format, in the SAME NUMBER OF
+     * LAUNCHES as the headless step without the member -- the RECORDS form of the family's (masked) step kernel stores the row itself: the instance's
+     * lane (one 16-byte store: Mortar Mayhem ids; four: Mystery Path ids; Endless-MysteryPath-v0 also from its queue server's lane) or its 16-lane
+     * group (Searing Spotlights ids: the head from the first lane, a hole word from each).  With obs_dev != NULL the call is that headless arrangement
+     * followed by the family's dense raster launch (the one mg_render uses; filtered by active_dev in mg_step_masked): the PLAIN arrangement, not the
+     * fused one -- a drawn step that wants its terminal frames cheaply AND its frames fused passes final_obs_dev instead.  Nothing is allocated, no
+     * state is added (MG_STATE_VERSION is unchanged), the call can be captured into a HIP graph.  mg_debug_counter "final_frame_steps" counts the
+     * calls.  Refused (-1): final_frames_dev together with final_obs_dev (the caller picks one); a final_frames_dev that is not 16-byte aligned.
+     * mg_advance, mg_play and their traced siblings do not take it. */
+    void* final_frames_dev;
 } mg_info_buffers;
 
 /* gymnasium.make(id) + Env.__init__  (memory_gym/__init__.py:13-61; e.g. mortar_mayhem_grid.py:55-90).
@@ -209,6 +228,7 @@ int mg_render_debug(mg_env* env, uint8_t* rgb_dev, void* stream);
  * kernel with the resets / paths generated in it; Endless-MysteryPath-v0's step kernel and its queue server as a launch of its own
  * (whatever earlier fused steps left owed is generated first, and the next drawn step is fused again) -- a linear chain of launches,
  * capturable into a HIP graph.  Refused (-1): obs_dev == NULL together with info->final_obs_dev -- terminal observations are frames.
+ * (The frame an episode ended on leaves a headless step as a RECORD: info->final_frames_dev, see mg_info_buffers.)
  * mg_reset and mg_single_step keep requiring their buffers.  mg_debug_counter "headless_steps" counts these calls. */
 int mg_step(mg_env* env, const int32_t* actions_dev, void* obs_dev, float* reward_dev, uint8_t* done_dev,
             float* gt_dev, const mg_info_buffers* info, int autoreset, void* stream);
@@ -486,8 +506,10 @@ int mg_load_instances(mg_env* env, const int32_t* idx_dev, const int32_t* rec_of
  * themselves need no new layout: the background template is a field of the descriptor and travels in the record.  The library CANNOT check this -- the
  * records carry no header: keep the value next to the records and compare before drawing (the Python mirror does); drawing a stale record is undefined
  * for its row.  mg_frame_record_bytes is sizeof the family's descriptor: 16 / 64 / 128.
- * OUT OF SCOPE: terminal-observation rows (final_obs_dev and the terminal descriptors behind them); the debug view (mg_render_debug); the MortarMayhemB
- * ids' vector observation.  (Descriptor traces out of mg_play / mg_advance: mg_play_traced / mg_advance_traced, above.)
+ * OUT OF SCOPE: terminal-observation rows as FRAMES (final_obs_dev and the terminal descriptors the fused launches keep behind it: mg_save_frames never
+ * sees them -- the frame an episode ended on is kept as a record by mg_step itself, mg_info_buffers.final_frames_dev, and drawn by mg_draw_frames like any
+ * other); the debug view (mg_render_debug); the MortarMayhemB ids' vector observation.  (Descriptor traces out of mg_play / mg_advance: mg_play_traced /
+ * mg_advance_traced, above.)
  * mg_debug_counter "frame_saves" / "frame_draws" count the calls with count > 0, on the host.  MG_STATE_VERSION is unchanged: no state is added.
  * Errors (-1): before the first mg_reset / mg_set_state; a geometry option set since the last reset; a NULL or misaligned rec_dev / obs_dev; count < 0;
  * n_records < 1 with count > 0; an unknown format; pick_dev == NULL with count > n_records; n_records or count > INT32_MAX. */
