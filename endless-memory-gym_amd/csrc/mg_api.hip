@@ -55,6 +55,7 @@ struct mg_env {
     uint64_t serial = 0;
     int64_t instance_saves = 0, instance_loads = 0;
     int64_t frame_saves = 0, frame_draws = 0;  // mg_debug_counter: mg_save_frames / mg_draw_frames calls with count > 0
+    int64_t debug_frame_saves = 0, debug_frame_draws = 0;  // mg_debug_counter: mg_save_debug_frames / mg_draw_debug_frames calls with count > 0
     struct Instances {
         bool ready = false;
         mg::DevArray<int32_t> claim;  // [num_envs] the entry of the current load that holds the instance
@@ -789,6 +790,33 @@ int mg_draw_frames(mg_env* env, const void* rec_dev, int64_t n_records, const in
     });
 }
 
+// ---- debug-view records (include/memgym.h: mg_save_debug_frames / mg_draw_debug_frames; the picked *_debug_desc kernels of the three families, the debug
+// gather forms of the two raster skeletons, mg_debug_stream_out.hpp) ----
+int mg_save_debug_frames(mg_env* env, const int32_t* idx_dev, int32_t count, void* rec_dev, void* stream) {
+    return guarded(env, [&] {
+        const std::string who = "mg_save_debug_frames: ";
+        if (!env->started) throw std::runtime_error(who + "before the first mg_reset / mg_set_state");
+        if (const char* no = mg::frame_save_refusal(count, rec_dev)) throw std::runtime_error(who + no);
+        if (env->fam->geometry_dirty()) throw std::runtime_error(who + "options that change geometry need a reset first");
+        if (!idx_dev && count > env->num_envs) throw std::runtime_error(who + "idx_dev is NULL and count > num_envs");
+        if (count == 0) return;
+        env->fam->save_debug_records(idx_dev, count, rec_dev, (hipStream_t)stream);
+        ++env->debug_frame_saves;
+    });
+}
+
+int mg_draw_debug_frames(mg_env* env, const void* rec_dev, int64_t n_records, const int32_t* pick_dev, int64_t count, int size, void* rgb_dev, void* stream) {
+    return guarded(env, [&] {
+        const std::string who = "mg_draw_debug_frames: ";
+        if (!env->started) throw std::runtime_error(who + "before the first mg_reset / mg_set_state");
+        if (const char* no = mg::debug_draw_refusal(rec_dev, n_records, pick_dev != nullptr, count, size, rgb_dev)) throw std::runtime_error(who + no);
+        if (env->fam->geometry_dirty()) throw std::runtime_error(who + "options that change geometry need a reset first");
+        if (count == 0) return;
+        env->fam->draw_debug_records(rec_dev, (int)n_records, pick_dev, (int)count, size, rgb_dev, (hipStream_t)stream);
+        ++env->debug_frame_draws;
+    });
+}
+
 int mg_ground_truth64(mg_env* env, double* gt64_dev, void* stream) {
     return guarded(env, [&] {
         if (!env->fam->gt_dim()) return;
@@ -1046,6 +1074,10 @@ int mg_debug_counter(mg_env* env, const char* name, int64_t* value) {
         }
         if (std::string(name) == "frame_saves" || std::string(name) == "frame_draws") {  // every id: counted in this file
             *value = std::string(name) == "frame_saves" ? env->frame_saves : env->frame_draws;
+            return;
+        }
+        if (std::string(name) == "debug_frame_saves" || std::string(name) == "debug_frame_draws") {  // every id: counted in this file
+            *value = std::string(name) == "debug_frame_saves" ? env->debug_frame_saves : env->debug_frame_draws;
             return;
         }
         if (std::string(name) == "masked_steps") {  // every id: counted in this file

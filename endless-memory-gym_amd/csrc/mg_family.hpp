@@ -324,6 +324,13 @@ class Family {
     // render("debug_rgb_array") before its final x4 stretch: the debug surface of every instance (the reference's
     // _build_debug_surface, e.g. mortar_mayhem_grid.py:104-135) as uint8 [num_envs][84 x][84 y][3], the observation layout
     virtual void raster_debug(void* frames, hipStream_t s) = 0;
+    // mg_save_debug_frames / mg_draw_debug_frames (include/memgym.h).  save_debug_records(): record j <- the descriptor raster_debug() would fill for
+    // instance idx[j] (idx == NULL: instance j) from the current state, j < count -- the picked form of the family's *_debug_desc_kernel, one lane per
+    // entry, with mg_save_frames' index conventions; what a debug render changes (the mortar family's dbg_pops) changes for the named instances alone.
+    // Stream-ordered: work a family has put off is enqueued in front, nothing synchronises.  draw_debug_records(): row j of `rgb` <- the view of
+    // records[pick[j]] at `size` 84 or 336, the gather form of the family's raster launch with the composer raster_debug() picks.
+    virtual void save_debug_records(const int32_t* idx, int count, void* rec, hipStream_t s) = 0;
+    virtual void draw_debug_records(const void* records, int n_records, const int32_t* pick, int count, int size, void* rgb, hipStream_t s) = 0;
     // checkpoint: list of (device pointer, bytes) making up the state
     virtual std::vector<std::pair<void*, size_t>> state_blobs() = 0;
     // mg_save_instances / mg_load_instances (mg_instances.hpp): the arrays that ARE [num_envs][row], as (device pointer, bytes per instance) -- everything the

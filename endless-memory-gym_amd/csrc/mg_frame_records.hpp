@@ -52,4 +52,11 @@ inline const char* frame_draw_refusal(const void* rec_dev, int64_t n_records, bo
     return nullptr;
 }
 
+// The same for mg_draw_debug_frames: mg_draw_frames' refusals with a size, 84 or 336, in place of a format.
+inline const char* debug_draw_refusal(const void* rec_dev, int64_t n_records, bool has_pick, int64_t count, int size, const void* rgb_dev) {
+    if (size != 84 && size != 336) return "size is neither 84 nor 336";
+    if (!aligned16(rgb_dev)) return "rgb_dev is NULL or not 16-byte aligned";
+    return frame_draw_refusal(rec_dev, n_records, has_pick, count, MG_OBS_U8_XYC, rgb_dev);
+}
+
 }  // namespace mg

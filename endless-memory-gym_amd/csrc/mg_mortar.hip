@@ -109,6 +109,49 @@ __global__ __launch_bounds__(256) void mortar_debug_desc_kernel(MortarParams P0,
     out[i] = d;
 }
 
+// The same descriptor for ONE instance, for the picked form below (a body of its own: mortar_debug_desc_kernel stays the code it was).
+__device__ __forceinline__ MortarDesc mortar_debug_desc_one(const MortarParams& P, const MortarIO& io, int i) {
+    const MortarState s = io.state[i];
+    const uint8_t* cmds = io.cmds + (size_t)i * P.cmd_cap;
+    MortarDesc d = io.desc[i];
+    {   // the agent the debug view shows is the stored (rotated_agent_surface, rotated_agent_rect) pair, which no reset clears
+        // (mortar_mayhem_grid.py:115-118): stale from the previous episode until the first step; sprite 0 before any step
+        const bool have = s.disp_sprite != 0xFF;
+        const int cx = (have && !s.disp_is_agent) ? s.disp_x : s.ax, cy = (have && !s.disp_is_agent) ? s.disp_y : s.ay;
+        d.sx = (int16_t)(cx - P.sprite_dim / 2);
+        d.sy = (int16_t)(cy - P.sprite_dim / 2);
+        d.sprite = have ? s.disp_sprite : (uint8_t)0;
+        d.tmpl = (uint16_t)((s.tiles_on && P.visual_feedback) ? 1 + s.tx * P.N + s.ty : 0);
+        d.glyph_x0 = (int16_t)P.glyph_x0;
+    }
+    d.glyph = 0xFF;
+    if (s.vis_pos < s.vis_len) {
+        const int idx = (int)s.dbg_pops, period = s.show_dur + s.show_delay;
+        io.state[i].dbg_pops = s.dbg_pops + 1;
+        if (idx >= 0 && idx < (int)s.vis_len && period > 0) {
+            const int k = idx / period, w = idx % period;
+            d.glyph = (w < s.show_dur) ? cmds[s.vis_base + k] : (uint8_t)9;
+        }
+    }
+    const int r = P.tile / 2;  // pygame.draw.circle(surface, green, tile centre, tile_dim // 2, int(8 * SCALE))
+    d.ring_x = (int16_t)(P.arena_x0 + P.tile * s.tx + P.tile / 2 - r);
+    d.ring_y = (int16_t)(P.arena_x0 + P.tile * s.ty + P.tile / 2 - r);
+    d.ring_on = 1;
+    return d;
+}
+// mg_save_debug_frames: record j <- the debug descriptor of instance idx[j] (idx == NULL: instance j), one lane per entry; the named instances are the
+// ones whose display-schedule clone is popped.  An entry < 0 is skipped, one >= n is skipped and flagged; a skipped entry's record is not written.
+__global__ __launch_bounds__(256) void mortar_debug_desc_picked_kernel(MortarParams P0, int n, MortarIO io, const int32_t* __restrict__ idx, int count,
+                                                                       MortarDesc* rec) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= count) return;
+    const int i = idx ? idx[j] : j;
+    if (i < 0) return;
+    if (i >= n) return raise_error(io.err, ERR_FRAME_INDEX);
+    const MortarParams& P = io.set_of ? io.sets[set_index(io.set_of, i)] : P0;
+    rec[j] = mortar_debug_desc_one(P, io, i);
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // Host side
 // ---------------------------------------------------------------------------------------------------------
@@ -454,6 +497,15 @@ class MortarFamily : public Family {
         debug_frames<MortarDesc>(
             s, [&](MortarDesc* dbg) { launch(mortar_debug_desc_kernel, dim3((n_ + 255) / 256), dim3(256), 0, s, P_, n_, io(), dbg); },
             [&](MortarDesc* dbg) { launch_raster<MortarDebugComposer>(dbg, atlas_->dev(), frames, MG_OBS_U8_XYC, n_, s); });
+    }
+
+    void save_debug_records(const int32_t* idx, int count, void* rec, hipStream_t s) override {
+        sets_.upload(s);
+        launch_checked(mortar_debug_desc_picked_kernel, dim3((count + 255) / 256), dim3(256), 0, s, P_, n_, io(), idx, count, (MortarDesc*)rec);
+    }
+    void draw_debug_records(const void* records, int n_records, const int32_t* pick, int count, int size, void* rgb, hipStream_t s) override {
+        launch_raster_debug_gather<MortarDebugComposer>((const MortarDesc*)records, atlas_->dev(), rgb, size, n_records, pick, count, err_.dev, s);
+        check_launch();
     }
 
    private:

@@ -111,6 +111,59 @@ __global__ __launch_bounds__(256) void mystery_debug_desc_kernel(MysteryParams P
     out[i] = d;
 }
 
+// The same descriptor for ONE instance, for the picked form below (a body of its own: mystery_debug_desc_kernel stays the code it was).
+__device__ __forceinline__ MysteryDesc mystery_debug_desc_one(const MysteryParams& P, const MysteryIO& io, int i) {
+    const MysteryCore s = io.core[i];
+    MysteryDesc d = io.desc[i];
+    d.valid = 1;
+    d.tile_mask[0] = d.tile_mask[1] = 0;
+    if (!P.endless) {
+        mp_desc(P, s, d);  // from the state alone: a handle restored by mg_set_state has no frame descriptors before its first step
+        d.pad8[0] = 1;
+        const uint64_t ends = (1ull << (s.sx * G + s.sy)) | (1ull << (s.ex * G + s.ey));
+        d.tile_mask[0] = s.path_mask & ~ends;
+        d.tile_mask[1] = io.walls[i];
+        d.goal_on = d.origin_on = 1;
+        d.goal_x = s.ex; d.goal_y = s.ey;
+        d.origin_x = s.sx; d.origin_y = s.sy;
+        d.tile_x0 = 0;
+        d.cross_on = s.cross_on;  // the cross surface keeps its alpha: the observation's visibility
+    } else {
+        d.pad8[0] = 2;
+        const int x0 = floordiv_pos(s.camera_x, P.tile);
+        d.tile_x0 = x0 * P.tile - s.camera_x;
+        const int seg_lo = x0 / (G + 1) - 1, seg_hi = (x0 + 16) / (G + 1) + 1;
+        for (int seg = seg_lo < 0 ? 0 : seg_lo; seg <= seg_hi && seg < s.num_seg; ++seg) {
+            const uint8_t* sp = seg_ptr(io, i, seg);
+            const int cnt = sp[0];
+            for (int k = 1; k <= cnt; ++k) {
+                const int col = node_x(seg, sp[k]) - x0, y = node_y(sp[k]);
+                if (col >= 0 && col < 16) {
+                    const int cell = col * G + y;
+                    d.tile_mask[cell >> 6] |= 1ull << (cell & 63);
+                }
+            }
+        }
+        d.stamina_on = 1;  // blitted whatever show_stamina says
+        const int st = s.stamina < P.stamina_level ? s.stamina : P.stamina_level;
+        d.stamina_red = (uint8_t)(int)(SCREEN * (1 - ((double)st / P.stamina_level)));
+    }
+    return d;
+}
+// mg_save_debug_frames: record j <- the debug descriptor of instance idx[j] (idx == NULL: instance j), one lane per entry.  An entry < 0 is skipped, one
+// >= n is skipped and flagged; a skipped entry's record is not written.
+template <bool PS>
+__global__ __launch_bounds__(256) void mystery_debug_desc_picked_kernel(MysteryParams P0, MysteryIO io, const int32_t* __restrict__ idx, int count,
+                                                                        MysteryDesc* rec) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= count) return;
+    const int i = idx ? idx[j] : j;
+    if (i < 0) return;
+    if (i >= P0.n) return raise_error(io.err, ERR_FRAME_INDEX);
+    const MysteryParams& P = PS ? io.sets[set_index(io.set_of, i)] : P0;
+    rec[j] = mystery_debug_desc_one(P, io, i);
+}
+
 __global__ __launch_bounds__(256) void mystery_init_kernel(int n, MysteryCore* core) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -190,6 +243,20 @@ class MysteryFamily : public Family {
         const MysteryDesc* rec = (const MysteryDesc*)records;
         if (big_sprites_) launch_raster_gather<MysteryBigComposer>(rec, atlas_->dev(), obs, fmt, n_records, pick, count, err_.dev, s);
         else launch_raster_gather<MysteryComposer>(rec, atlas_->dev(), obs, fmt, n_records, pick, count, err_.dev, s);
+        check_launch();
+    }
+    // (Endless: the debug view reads the segment store -- owed segments are generated first, on the call's stream, as before an instance save)
+    void save_debug_records(const int32_t* idx, int count, void* rec, hipStream_t s) override {
+        before_instance_save(s);
+        sets_.upload(s);
+        with_bool(sets_.per_set(), [&](auto PS) {
+            launch_checked(mystery_debug_desc_picked_kernel<decltype(PS)::value>, dim3((count + 255) / 256), dim3(256), 0, s, P_, io(), idx, count, (MysteryDesc*)rec);
+        });
+    }
+    void draw_debug_records(const void* records, int n_records, const int32_t* pick, int count, int size, void* rgb, hipStream_t s) override {
+        const MysteryDesc* rec = (const MysteryDesc*)records;
+        if (big_sprites_) launch_raster_debug_gather<MysteryDebugBigComposer>(rec, atlas_->dev(), rgb, size, n_records, pick, count, err_.dev, s);
+        else launch_raster_debug_gather<MysteryDebugComposer>(rec, atlas_->dev(), rgb, size, n_records, pick, count, err_.dev, s);
         check_launch();
     }
 

@@ -4,6 +4,7 @@
 // constant address space like the descriptor behind it, so both stay scalar loads that do not queue behind the previous frame's stores (the Composer
 // concept of mg_raster.hpp).  A kernel of its own: the dense launches are the measured ones and stay as they are.
 #pragma once
+#include "mg_debug_stream_out.hpp"
 #include "mg_frame_records.hpp"
 #include "mg_raster.hpp"
 
@@ -53,6 +54,49 @@ inline void launch_raster_gather(const typename Composer::Desc* records, const R
         with_obs_format(fmt, [&](auto F) {
             launch(raster_gather_kernel<Composer, decltype(F)::value, false>, grid, dim3(256), lds, s, records, atlas, obs, n_records, pick, count, err);
         });
+}
+
+// mg_draw_debug_frames (include/memgym.h): the same walk over records of the DEBUG view's descriptors with a debug composer.  SIZE 84: the debug
+// surface in the observation layout (the uint8 frame's buffer stores, plain); SIZE 336: the reference's debug_rgb_array, stretched and turned on the
+// way out of LDS (mg_debug_stream_out.hpp).  Kernels of their own: no MG_OBS_* value names these rows.
+template <class Composer, int SIZE>
+__global__ __launch_bounds__(256, 7) void raster_debug_gather_kernel(const typename Composer::Desc* __restrict__ records, RasterAtlas A, void* __restrict__ rgb,
+                                                                  int n_records, const int32_t* __restrict__ pick, int count, int* err) {
+    static_assert(SIZE == 84 || SIZE == DEBUG336, "the debug surface, or its x4 stretch");
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const RasterCtx R = make_ctx(smem, A);
+    const int tid = threadIdx.x, stride = gridDim.x;
+    const cptr<typename Composer::Desc> crecords = as_const(records);
+    const cptr<int32_t> cpick = as_const(pick);
+    Composer::recycle(R);  // scratch state compose() expects (e.g. a zeroed hole mask); published by the barriers below
+    __syncthreads();
+    for (int j = blockIdx.x; j < count; j += stride) {
+        const int r = pick ? cpick[j] : j;  // workgroup-uniform index: a scalar load
+        if ((unsigned)r >= (unsigned)n_records) {
+            if (tid == 0) __hip_atomic_fetch_or(err, ERR_FRAME_INDEX, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            continue;
+        }
+        if (Composer::skip(crecords + r)) continue;
+        typename Composer::Pre P;
+        Composer::prefetch(crecords + r, R, P);
+        Composer::compose(crecords + r, P, R);
+        __syncthreads();
+        Composer::recycle(R);  // overlaps the stream-out, saves a barrier at the start of the next compose()
+        if constexpr (SIZE == 84) store_frame<MG_OBS_U8_XYC, false, true>(smem, rgb, j, tid);
+        else store_debug336(smem, rgb, j, tid);
+        __syncthreads();  // the LDS frame is reused by the next iteration
+    }
+}
+
+// size: 84 or 336 (the caller has checked).  Grid and LDS request of a plain-store raster launch over `count` frames.
+template <class Composer>
+inline void launch_raster_debug_gather(const typename Composer::Desc* records, const RasterAtlas& atlas, void* rgb, int size, int n_records,
+                                       const int32_t* pick, int count, int* err, hipStream_t s) {
+    const int forced_lds = lab_raster_lds(RASTER_LDS);
+    const int lds = forced_lds ? forced_lds : RASTER_LDS;
+    const dim3 grid(frames_grid(count));
+    if (size == 84) launch(raster_debug_gather_kernel<Composer, 84>, grid, dim3(256), lds, s, records, atlas, rgb, n_records, pick, count, err);
+    else launch(raster_debug_gather_kernel<Composer, DEBUG336>, grid, dim3(256), lds, s, records, atlas, rgb, n_records, pick, count, err);
 }
 
 }  // namespace mg

@@ -107,6 +107,30 @@ __global__ __launch_bounds__(256) void spot_debug_desc_kernel(SpotParams P0, Spo
     out[i] = d;
 }
 
+// The same descriptor for ONE instance, for the picked form below (a body of its own: spot_debug_desc_kernel stays the code it was).
+__device__ __forceinline__ SpotDesc spot_debug_desc_one(const SpotParams& P, const SpotIO& io, int i) {
+    SpotDesc d = io.desc[i];
+    const SpotCore s = io.core[i];
+    d.valid = 1;
+    if (s.pad >> 31) {
+        d.sprite = (s.pad >> 16) & 7u;
+        d.sx = (int16_t)((int)(s.pad & 0xFFu) - 128 - P.sprite_half);
+        d.sy = (int16_t)((int)((s.pad >> 8) & 0xFFu) - 128 - P.sprite_half);
+    }
+    return d;
+}
+// mg_save_debug_frames: record j <- the debug descriptor of instance idx[j] (idx == NULL: instance j), one lane per entry.  An entry < 0 is skipped, one
+// >= n is skipped and flagged; a skipped entry's record is not written.
+__global__ __launch_bounds__(256) void spot_debug_desc_picked_kernel(SpotParams P0, SpotIO io, const int32_t* __restrict__ idx, int count, SpotDesc* rec) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= count) return;
+    const int i = idx ? idx[j] : j;
+    if (i < 0) return;
+    if (i >= P0.n) return raise_error(io.err, ERR_FRAME_INDEX);
+    const SpotParams& P = io.set_of ? io.sets[set_index(io.set_of, i)] : P0;
+    rec[j] = spot_debug_desc_one(P, io, i);
+}
+
 // ---------------------------------------------------------------------------------------------------------
 static const double SCALE = 0.25;
 
@@ -565,6 +589,17 @@ class SpotFamily : public Family {
     void draw_records(const void* records, int n_records, const int32_t* pick, int count, int fmt, void* obs, hipStream_t s) override {
         with_bool(P_.ordered_holes, [&](auto BO) {
             launch_raster_gather<SpotComposerT<decltype(BO)::value>>((const SpotDesc*)records, atlas_->dev(), obs, fmt, n_records, pick, count, err_.dev, s);
+        });
+        check_launch();
+    }
+
+    void save_debug_records(const int32_t* idx, int count, void* rec, hipStream_t s) override {
+        sets_.upload(s);
+        launch_checked(spot_debug_desc_picked_kernel, dim3((count + 255) / 256), dim3(256), 0, s, P_, io(), idx, count, (SpotDesc*)rec);
+    }
+    void draw_debug_records(const void* records, int n_records, const int32_t* pick, int count, int size, void* rgb, hipStream_t s) override {
+        with_bool(P_.ordered_holes, [&](auto BO) {
+            launch_raster_debug_gather<SpotDebugComposerT<decltype(BO)::value>>((const SpotDesc*)records, atlas_->dev(), rgb, size, n_records, pick, count, err_.dev, s);
         });
         check_launch();
     }

@@ -125,6 +125,9 @@ def _load():
         L.mg_frame_layout.restype = C.c_uint64
         L.mg_save_frames.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
         L.mg_draw_frames.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]
+    if hasattr(L, "mg_save_debug_frames"):  # (absent from the older builds tools/ A/B against through MEMGYM_HIP_LIB)
+        L.mg_save_debug_frames.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+        L.mg_draw_debug_frames.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]
     L.mg_enable_peer_access.argtypes = [C.c_int, C.c_int]
     L.mg_debug_rng.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
     L.mg_debug_set_rng.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]

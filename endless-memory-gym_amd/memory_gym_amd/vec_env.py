@@ -209,6 +209,24 @@ class FrameRecords:
         return int(self.records.numel() // self.records.shape[-1])
 
 
+class DebugFrameRecords(FrameRecords):
+    """What VecMemoryGym.save_debug_frames returns: FrameRecords whose rows are DEBUG-VIEW descriptors (the same widths, another content: what
+    render_debug() draws from, include/memgym.h mg_save_debug_frames).  draw_debug_frames draws them; draw_frames refuses them."""
+    __slots__ = ()
+
+
+def _distinct_host_index(what, idx):
+    """idx as the caller gave it, where the host can see it (a list, an array, a CPU tensor): ValueError if an instance is named twice.  A device tensor
+    is not looked at (no synchronisation): there a repeated index is the caller's to avoid (include/memgym.h)."""
+    if idx is None or (isinstance(idx, torch.Tensor) and idx.device.type != "cpu"):
+        return
+    a = np.asarray(idx.numpy() if isinstance(idx, torch.Tensor) else idx)
+    if a.dtype.kind in "iu" and a.ndim == 1:
+        named = a[a >= 0]
+        if np.unique(named).size != named.size:
+            raise ValueError("%s: idx names an instance more than once (entries must be distinct; negative entries are padding)" % what)
+
+
 def _frame_rows(what, name, t, record_bytes):
     """A tensor of frame records -> its view [n, record_bytes]; ValueError unless it is a contiguous uint8 tensor whose last dimension is one record."""
     if not (isinstance(t, torch.Tensor) and t.dtype == torch.uint8 and t.dim() >= 2 and t.shape[-1] == int(record_bytes) and t.is_contiguous()):
@@ -237,6 +255,8 @@ def check_frame_draw(records, layout, record_bytes, pick=None, out=None, obs_for
     width / stride, a pick that is no one-dimensional integer tensor, more rows than records without a pick, an unknown format, an `out` of the wrong
     shape / dtype or one that is not contiguous."""
     what = "draw_frames"
+    if isinstance(records, DebugFrameRecords):
+        raise ValueError("%s: these are debug-view records (save_debug_frames): draw_debug_frames draws them" % what)
     if isinstance(records, FrameRecords):
         if records.layout != int(layout):
             raise ValueError("%s: the records (layout 0x%x) were saved from another handle, or before something changed that they would draw differently "
@@ -983,6 +1003,74 @@ class VecMemoryGym:
                                                      self.OBS_FORMATS[fmt][0], out.data_ptr(), self._stream()), "mg_draw_frames")
         return out
 
+    # ------------------------------------------------------------------ debug-view records
+    DEBUG_SIZES = {84: (84, 84, 3), 336: (336, 336, 3)}  # draw_debug_frames: the debug surface [x][y][c], or the reference's debug_rgb_array [y][x][c]
+
+    def save_debug_frames(self, idx=None, out=None):
+        """Keep the GROUND-TRUTH (debug) view of a few instances as records (include/memgym.h: mg_save_debug_frames) -> DebugFrameRecords over a uint8
+        tensor [k, frame_record_bytes]: what render_debug() would draw for instance idx[j] right now, as 16 / 64 / 128 bytes.  It counts as one debug
+        render of the named instances and of no other (Mortar Mayhem ids: the view's clone of the command schedule advances for them alone).  idx: the
+        instances, an integer tensor / list (None: all, in order); entries < 0 are skipped (their records keep their bytes); entries must be
+        DISTINCT -- a list, array or CPU tensor that names an instance twice is refused, a device tensor is not looked at.  out: a
+        DebugFrameRecords or a uint8 tensor [k, frame_record_bytes] to write into -- a row block store[t] of a larger [T, k, bytes] store.  One small
+        launch on the current stream (Endless-MysteryPath-v0: behind the launch that generates owed path segments); nothing synchronises."""
+        self._require_started("save_debug_frames")
+        _distinct_host_index("save_debug_frames", idx)
+        nbytes = self.frame_record_bytes
+        if out is not None and isinstance(out, FrameRecords) and not isinstance(out, DebugFrameRecords):
+            raise ValueError("save_debug_frames: out holds frame records (save_frames), not debug-view records")
+        idx, k, rows = check_frame_save(nbytes, self.num_envs, idx, out, self.device)
+        if rows is None:
+            out = rows = torch.empty((k, nbytes), dtype=torch.uint8, device=self.device)
+        if rows.device != self.device or rows.data_ptr() % 16:
+            raise ValueError("save_debug_frames: out must be a 16-byte aligned tensor on %s" % (self.device,))
+        with torch.cuda.device(self.device):
+            _native.check(_native.LIB.mg_save_debug_frames(self._h, None if idx is None else idx.data_ptr(), k, rows.data_ptr(), self._stream()),
+                          "mg_save_debug_frames")
+        if isinstance(out, DebugFrameRecords):
+            out.layout = self.frame_layout()
+            return out
+        return DebugFrameRecords(out, self.frame_layout())
+
+    def draw_debug_frames(self, records, pick=None, out=None, size=336):
+        """Draw kept debug views (include/memgym.h: mg_draw_debug_frames): row j of the result is the view of record pick[j] (pick=None: record j).
+        size=336: uint8 [count, 336, 336, 3], bit for bit the row render_debug() gave when the record was saved; size=84: uint8 [count, 84, 84, 3], the
+        debug surface before its stretch, in the observation layout [x][y][c].  records: a DebugFrameRecords (its layout is checked: ValueError if
+        stale, before anything is launched) or a plain uint8 tensor, viewed as [n_records, frame_record_bytes].  pick: an integer tensor / list of any
+        length, duplicates allowed; an entry outside the records leaves its row untouched and raises error bit 512.  out: a contiguous uint8 tensor of
+        the result's shape to draw into.  One raster launch on the current stream; nothing synchronises, nothing of the handle changes."""
+        what = "draw_debug_frames"
+        self._require_started(what)
+        if size not in self.DEBUG_SIZES:
+            raise ValueError("%s: size must be 84 or 336" % what)
+        if isinstance(records, FrameRecords):
+            if not isinstance(records, DebugFrameRecords):
+                raise ValueError("%s: these are frame records (save_frames): draw_frames draws them" % what)
+            if records.layout != self.frame_layout():
+                raise ValueError("%s: the records (layout 0x%x) were saved from another handle, or before something changed that they would draw differently "
+                                 "(layout 0x%x now): debug-view records are valid for the handle and the atlas they were saved under"
+                                 % (what, records.layout, self.frame_layout()))
+            records = records.records
+        rows = _frame_rows(what, "records", records, self.frame_record_bytes)
+        if pick is not None:
+            pick = _instance_index(what, "pick", pick, self.device)
+        count = rows.shape[0] if pick is None else pick.numel()
+        if count > 0 and rows.shape[0] < 1:
+            raise ValueError("%s: no records to draw from" % what)
+        shape = (count,) + self.DEBUG_SIZES[size]
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=self.device)
+        elif not (isinstance(out, torch.Tensor) and out.dtype == torch.uint8 and tuple(out.shape) == shape and out.is_contiguous()):
+            raise ValueError("%s: out must be a contiguous uint8 tensor of shape %s" % (what, shape))
+        if count == 0:  # nothing to draw (an empty tensor has no address to hand to the library)
+            return out
+        if rows.device != self.device or out.device != self.device or rows.data_ptr() % 16 or out.data_ptr() % 16:
+            raise ValueError("%s: records and out must be 16-byte aligned tensors on %s" % (what, self.device))
+        with torch.cuda.device(self.device):
+            _native.check(_native.LIB.mg_draw_debug_frames(self._h, rows.data_ptr(), rows.shape[0], None if pick is None else pick.data_ptr(), count,
+                                                           int(size), out.data_ptr(), self._stream()), "mg_draw_debug_frames")
+        return out
+
     def _scatter_rows(self, dst, tgt, rows):
         """dst[tgt[j]] = rows[j]; tgt[j] == len(dst) names nobody (a skipped entry).  No host look."""
         ext = torch.cat([dst, dst[:1]])
@@ -1198,7 +1286,8 @@ class VecMemoryGym:
                   32: "Endless Mortar Mayhem command list reached its 512-entry capacity (the episode was ended)",
                   64: "a deferred-reset queue overflowed (a previous fused launch did not drain it)",
                   256: "use_exit=False for an instance that never had an exit (the reference raises AttributeError at this reset)",
-                  512: "save_instances / load_instances / save_frames / draw_frames: an instance or record index out of range (the entry was skipped)"}
+                  512: "save_instances / load_instances / save_frames / draw_frames / save_debug_frames / draw_debug_frames: an instance or record index out of range "
+                       "(the entry was skipped)"}
 
     def check_errors(self):
         """Raise if a kernel flagged a capacity/failure condition since the last call (synchronises the device).

@@ -207,7 +207,7 @@ int mg_render(mg_env* env, void* obs_dev, void* stream);
  * between steps show what the reference shows.  After headless steps (obs_dev == NULL) or mg_advance it shows the state the last
  * of those steps left -- the view a drawn run of the same steps gives, episodes that ended inside included -- and right after
  * mg_set_state the view of the handle the blob was taken from (tests/test_gpu_debug_arrangements.py).  Synchronous (allocates and
- * frees a scratch buffer); not a hot path. */
+ * frees a scratch buffer); not a hot path.  The view of a few instances, kept and drawn later without either: mg_save_debug_frames below. */
 int mg_render_debug(mg_env* env, uint8_t* rgb_dev, void* stream);
 
 /* Env.step(action) (e.g. mortar_mayhem_grid.py:280-375) for all instances.
@@ -374,7 +374,7 @@ int mg_play(mg_env* env, const int32_t* tape_dev, int32_t steps, int mode, const
  * the labels and one mg_save_frames launch per step.  mg_debug_counter "traced_steps" counts the steps of calls with a trace, "traced_fused_steps" those taken
  * in-launch; they also count as the siblings' "advance_fused_steps" / "play_fused_steps" / "headless_steps" / "masked_steps".
  * STILL OUT OF SCOPE: the terminal frames of episodes that end inside a call (the reset frame replaces them, as in mg_advance); the MortarMayhemB ids' vector
- * observation per step; the debug view.
+ * observation per step; the debug view of the steps inside a call (between calls: mg_save_debug_frames).
  * Errors (-1): everything the sibling refuses; a mg_rollout_trace.struct_size that is no layout of this header; a frames_dev that is not 16-byte aligned;
  * actions_dev / labels_dev that are not 8-byte aligned; actions_dev or labels_dev set in mg_play_traced (the tape is the caller's, there is no teacher). */
 typedef struct mg_rollout_trace {   /* every array may be NULL */
@@ -508,8 +508,8 @@ int mg_load_instances(mg_env* env, const int32_t* idx_dev, const int32_t* rec_of
  * for its row.  mg_frame_record_bytes is sizeof the family's descriptor: 16 / 64 / 128.
  * OUT OF SCOPE: terminal-observation rows as FRAMES (final_obs_dev and the terminal descriptors the fused launches keep behind it: mg_save_frames never
  * sees them -- the frame an episode ended on is kept as a record by mg_step itself, mg_info_buffers.final_frames_dev, and drawn by mg_draw_frames like any
- * other); the debug view (mg_render_debug); the MortarMayhemB ids' vector observation.  (Descriptor traces out of mg_play / mg_advance: mg_play_traced /
- * mg_advance_traced, above.)
+ * other); the MortarMayhemB ids' vector observation.  (Descriptor traces out of mg_play / mg_advance: mg_play_traced / mg_advance_traced, above.  The
+ * debug view: records of its own, mg_save_debug_frames / mg_draw_debug_frames, below.)
  * mg_debug_counter "frame_saves" / "frame_draws" count the calls with count > 0, on the host.  MG_STATE_VERSION is unchanged: no state is added.
  * Errors (-1): before the first mg_reset / mg_set_state; a geometry option set since the last reset; a NULL or misaligned rec_dev / obs_dev; count < 0;
  * n_records < 1 with count > 0; an unknown format; pick_dev == NULL with count > n_records; n_records or count > INT32_MAX. */
@@ -518,6 +518,39 @@ uint64_t mg_frame_layout(const mg_env* env);
 int mg_save_frames(mg_env* env, const int32_t* idx_dev, int32_t count, void* rec_dev, void* stream);
 int mg_draw_frames(mg_env* env, const void* rec_dev, int64_t n_records, const int32_t* pick_dev, int64_t count, int format, void* obs_dev,
                    void* stream);
+
+/* DEBUG-VIEW RECORDS: keep the ground-truth view of a FEW instances and draw it later.  mg_render_debug draws every instance at once, from the current state,
+ * synchronously: at 65,536 instances 22 GB of views and 1.4 GB of scratch to look at one of them.  But a debug view, like a frame, is a pure function of a
+ * descriptor of the family's frame-descriptor type (16 / 64 / 128 B) and the handle's atlas -- the descriptor mg_render_debug fills for every instance before it
+ * draws.  A trainer that logs a short video of what is hidden from the agent saves the descriptors of the instances it watches, one small launch per step,
+ * and draws all of them with one launch at the end.
+ *   mg_save_debug_frames   record j <- the debug-view descriptor of instance idx_dev[j]   (idx_dev == NULL: instance j, and then count <= num_envs)
+ *   mg_draw_debug_frames   row j of rgb_dev <- the view of record pick_dev[j]              (pick_dev == NULL: record j, and then count <= n_records)
+ * DEFINITION: take a handle and a twin with the same history; every time mg_render_debug is called on the twin, mg_save_debug_frames is called on the handle
+ * for a set S of instances.  Then for every i in S the saved record, drawn at size 336, gives bit for bit row i of the twin's output at that moment; and an
+ * instance outside S behaves like an instance of a handle on which no debug render was ever made.
+ * mg_save_debug_frames computes the descriptor from the CURRENT state, exactly what mg_render_debug computes for that instance, and counts as ONE debug render
+ * of the named instances and of no other: on the five Mortar Mayhem ids the named instance's count of entries popped from the CLONE of the command
+ * visualisation list (see mg_render_debug) advances by one; nothing else in the handle changes, and an instance that is not named keeps its count.  Index
+ * conventions of mg_save_frames: an entry < 0 is skipped, an entry >= num_envs is skipped and raises error bit 512; a skipped entry leaves its record
+ * untouched and its instance is not popped.  Entries must be DISTINCT: a repeated index is not detected, and on the Mortar Mayhem ids it leaves that
+ * instance's pop count and the records of its duplicate entries undefined (on the other ids the duplicates hold the same descriptor).  Records are
+ * mg_frame_record_bytes each and valid under mg_frame_layout, by the rules of the frame records -- but they are NOT frame records: mg_draw_frames draws
+ * something else from them.  One launch, one lane per entry.  Endless-MysteryPath-v0: the view reads the path segments, so segments the handle still owes
+ * are generated first, by a launch on `stream` in front of the save (as for mg_save_instances); nothing synchronises.
+ * mg_draw_debug_frames: ONE launch, the gather form of the family's raster kernel with the composer mg_render_debug uses for the handle.  size 336: rgb_dev
+ * is uint8 [count][336 y][336 x][3], the reference's debug_rgb_array -- every pixel of the debug surface four times per axis, out[y][x][c] =
+ * surface[x >> 2][y >> 2][c], written straight from the composed frame as 16-byte stores (no second pass over memory; 64-bit row offsets).  size 84: rgb_dev
+ * is uint8 [count][84 x][84 y][3], the debug surface before its stretch, in the observation layout.  Any other size: -1.  These are no observation formats:
+ * the MG_OBS_* values and mg_set_obs_format are untouched.  Picks as for mg_draw_frames: one outside 0 .. n_records-1 leaves its row untouched and raises bit
+ * 512, duplicates are legal, count == 0 does nothing.
+ * Both calls only enqueue on `stream`, allocate nothing and can be captured into a HIP graph; indices, picks and records are read at replay.  mg_render_debug
+ * is unchanged.  mg_debug_counter "debug_frame_saves" / "debug_frame_draws" count the calls with count > 0, on the host.  MG_STATE_VERSION is unchanged: no
+ * state is added.
+ * Errors (-1): those of mg_save_frames / mg_draw_frames (rgb_dev in the place of obs_dev); idx_dev == NULL with count > num_envs; a size other than 84 / 336. */
+int mg_save_debug_frames(mg_env* env, const int32_t* idx_dev, int32_t count, void* rec_dev, void* stream);
+int mg_draw_debug_frames(mg_env* env, const void* rec_dev, int64_t n_records, const int32_t* pick_dev, int64_t count, int size, void* rgb_dev,
+                         void* stream);
 
 /* Measurement hooks (bench.py's roofline leg): mg_set_profiling(env, N) makes every N-th mg_step (N = 1: every step,
  * 0: off) bracket its kernels with hipEvents recorded on the launch stream (a bracketed step costs ~15 us of stream
@@ -539,8 +572,8 @@ int mg_get_profile(mg_env* env, int kind, double* total_ms, int64_t* launches);
  * 256  SearingSpotlights-v0: use_exit = False at the reset of an instance that has never had an exit (the reference raises
  *      AttributeError there, searing_spotlights.py:431-435; with an earlier exit it keeps drawing that one, and so does this
  *      library); no exit was drawn
- * 512  mg_save_instances / mg_load_instances / mg_save_frames / mg_draw_frames: an instance index >= num_envs, or a record index outside the
- *      call's records; the entry was skipped, nothing else changed
+ * 512  mg_save_instances / mg_load_instances / mg_save_frames / mg_draw_frames / mg_save_debug_frames / mg_draw_debug_frames: an instance index
+ *      >= num_envs, or a record index outside the call's records; the entry was skipped, nothing else changed
  * 128  reserved (rounds <= 3: a frame workgroup of the mortar family's one-launch step gave up waiting for its descriptor.
  *      Since round 4 that launch cannot time out -- a frame wave that waits too long steps the instances itself,
  *      mg_mortar.hip mortar_step_raster_kernel -- and the bit is never raised) */
@@ -640,7 +673,8 @@ int mg_enable_peer_access(int device, int peer_device);
  * has the form): steps mg_play took inside mortar_play_kernel; the steps of its loop form count as "headless_steps" and, where a mask applied,
  * "masked_steps".  "instance_saves" / "instance_loads" (every id):
  * mg_save_instances / mg_load_instances calls of this handle with count > 0, counted on the host.  "frame_saves" / "frame_draws" (every id): the same
- * for mg_save_frames / mg_draw_frames.  "traced_steps" / "traced_fused_steps" (every id; only the mortar family has the in-launch form): steps of
+ * for mg_save_frames / mg_draw_frames; "debug_frame_saves" / "debug_frame_draws" (every id): the same for mg_save_debug_frames / mg_draw_debug_frames.
+ * "traced_steps" / "traced_fused_steps" (every id; only the mortar family has the in-launch form): steps of
  * mg_advance_traced / mg_play_traced calls that came with a trace, and those of them taken inside mortar_advance_traced_kernel / mortar_play_traced_kernel.
  * Unknown name: -1.  Synchronous. */
 int mg_debug_counter(mg_env* env, const char* name, int64_t* value);
