@@ -61,6 +61,13 @@ struct mg_env {
         mg::DevArray<int32_t> claim;  // [num_envs] the entry of the current load that holds the instance
         mg::DevArray<uint8_t> mask;   // [num_envs] the row mask a load with obs_dev draws by
     } inst;
+    // mg_step_next: the calls, those that took a family's own kernel (Family::step_next), and the two flag rows of the handle's scratch, allocated at the
+    // handle's first call (include/memgym.h)
+    int64_t next_steps = 0, next_fused_steps = 0;
+    struct Next {
+        bool ready = false;
+        mg::DevArray<uint8_t> active, restart;  // [num_envs] each: !restart_dev[i] (the composed form's mask) and a copy of restart_dev, which may be done_dev
+    } nxt;
     std::string id;
     int obs_format = MG_OBS_U8_XYC;
     float* vec_dev = nullptr;     // the caller's vector-observation binding (mg_bind_vector_obs), or the single-instance block's
@@ -413,6 +420,54 @@ int mg_step_masked(mg_env* env, const int32_t* actions_dev, const uint8_t* activ
     return guarded(env, [&] {
         if (!env->started) throw std::runtime_error("mg_step_masked: before the first mg_reset / mg_set_state");
         step_call(env, "mg_step_masked", actions_dev, active_dev, obs_dev, reward_dev, done_dev, gt_dev, info, autoreset, (hipStream_t)stream);
+    });
+}
+
+}  // extern "C"
+// mg_step_next, composed form, first launch: the mask of the masked step (active = !restart) and a copy of the flags for the masked reset behind it --
+// restart may be the caller's done_dev, which the step overwrites: the copy is what makes that legal.
+__global__ __launch_bounds__(256) void next_flags_kernel(int n, const uint8_t* __restrict__ restart, uint8_t* __restrict__ active, uint8_t* __restrict__ restart_copy) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const bool again = restart[i] != 0;
+    active[i] = again ? 0 : 1;
+    restart_copy[i] = again ? 1 : 0;
+}
+extern "C" {
+
+int mg_step_next(mg_env* env, const int32_t* actions_dev, const uint8_t* restart_dev, void* obs_dev, float* reward_dev, uint8_t* done_dev, float* gt_dev,
+                 const mg_info_buffers* info, void* stream) {
+    return guarded(env, [&] {
+        const std::string who = "mg_step_next: ";
+        if (!env->started) throw std::runtime_error(who + "before the first mg_reset / mg_set_state");
+        if (!actions_dev || !restart_dev || !obs_dev || !reward_dev || !done_dev)
+            throw std::runtime_error(who + "NULL buffer (actions_dev, restart_dev, obs_dev, reward_dev and done_dev are required: mg_reset has no headless form)");
+        const mg::InfoArgs ia = mg::read_info(info);
+        if (ia.dev.final_obs_dev || ia.final_frames)
+            throw std::runtime_error(who + "final_obs_dev / final_frames_dev are set: there are no terminal rows in this mode, the terminal frame is the observation");
+        mg::Family* f = env->fam;
+        if (f->geometry_dirty()) throw std::runtime_error(who + "options that change geometry need a reset before the next step");
+        hipStream_t st = (hipStream_t)stream;
+        const int n = env->num_envs;
+        mg_env::Next& X = env->nxt;
+        if (!X.ready) {  // the handle's first call: the only one that allocates (and therefore not capturable)
+            if (mg::stream_capturing(st))
+                throw std::runtime_error(who + "the handle's first call allocates its scratch and cannot be captured; call it once eagerly");
+            X.active.alloc(n);
+            X.restart.alloc(n);
+            X.ready = true;
+        }
+        const mg_info_dev& ib = ia.dev;
+        if (f->step_next(actions_dev, restart_dev, X.restart.p, obs_dev, reward_dev, done_dev, gt_dev, &ib, st)) {
+            ++env->next_fused_steps;
+        } else {  // the pair of the definition
+            hipLaunchKernelGGL(next_flags_kernel, dim3((n + 255) / 256), dim3(256), 0, st, n, restart_dev, X.active.p, X.restart.p);
+            MG_HIP(hipGetLastError());
+            f->step(actions_dev, X.active.p, obs_dev, reward_dev, done_dev, gt_dev, &ib, 0, st);
+            f->reset(nullptr, X.restart.p, obs_dev, gt_dev, st);
+        }
+        ++env->next_steps;
+        if (ib.gt64_dev) f->ground_truth64(ib.gt64_dev, st);
     });
 }
 
@@ -1082,6 +1137,10 @@ int mg_debug_counter(mg_env* env, const char* name, int64_t* value) {
         }
         if (std::string(name) == "masked_steps") {  // every id: counted in this file
             *value = env->masked_steps;
+            return;
+        }
+        if (std::string(name) == "next_steps" || std::string(name) == "next_fused_steps") {  // every id: counted in this file
+            *value = std::string(name) == "next_steps" ? env->next_steps : env->next_fused_steps;
             return;
         }
         if (std::string(name) == "final_frame_steps") {  // every id: counted in this file

@@ -309,6 +309,13 @@ class Family {
     // mortar_play_traced_kernel, mg_mortar_trace.hpp).  `frames` of play_traced: TraceRows::frames, or NULL.
     virtual bool advance_traced(const AdvanceArgs& /*v*/, const TraceRows& /*tr*/, hipStream_t /*s*/) { return false; }
     virtual bool play_traced(const PlayArgs& /*v*/, void* /*frames*/, hipStream_t /*s*/) { return false; }
+    // mg_step_next: true = the family has run the call in launches of its own -- the NEXT form of its step kernel (an instance with restart[i] != 0 is reset by
+    // its own lane(s), the others step without auto-reset), its dense raster launch, and a last small launch that leaves the descriptor rows as the masked
+    // mg_reset of the definition leaves them (the mortar family: mg_mortar_next.hpp, the spotlight family: mg_spot_next.hpp); false = it has no such form (or
+    // the lab build switched it off) and nothing happened: mg_api.hip runs the pair of the definition.  restart may be the same memory as done: each
+    // instance's flag is read before its done is written, and kept in restart_copy ([num_envs] bytes of the handle's scratch) for the last launch.
+    virtual bool step_next(const int32_t* /*actions*/, const uint8_t* /*restart*/, uint8_t* /*restart_copy*/, void* /*obs*/, float* /*reward*/,
+                           uint8_t* /*done*/, float* /*gt*/, const mg_info_dev* /*info*/, hipStream_t /*s*/) { return false; }
     // rasterise the CURRENT frame descriptors of the instances with only[i] != 0 into `obs` (others untouched)
     virtual void raster_only(void* obs, const uint8_t* only, hipStream_t s) = 0;
     // mg_save_frames / mg_draw_frames (include/memgym.h; mg_frame_records.hpp).  frame_rows(): the frame descriptor array raster_only() draws from, as

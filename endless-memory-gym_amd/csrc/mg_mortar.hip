@@ -18,6 +18,8 @@
 //   mg_mortar_play.hpp        mortar_play_kernel: K steps of a caller-supplied action tape without a frame (mg_play), step + traces + sums per lane in one launch
 //   mg_mortar_trace.hpp       mortar_advance_traced_kernel / mortar_play_traced_kernel: the two above as kernels of their own that also keep every step's frame
 //                             descriptor, action, teacher's label, reward and done (mg_advance_traced / mg_play_traced)
+//   mg_mortar_next.hpp        mortar_step_next_kernel / mortar_next_settle_kernel: the NEXT form of the two-launch step (mg_step_next), a flagged instance is reset
+//                             by its lane instead of stepped
 //
 // The launches of a step as shipped:
 //   ONE launch for handles with one option set, in every observation format (mortar_step_raster_kernel: the step's workgroups lead the raster's grid and a frame waits for its own
@@ -43,6 +45,7 @@
 #include "mg_mortar_advance.hpp"
 #include "mg_mortar_play.hpp"
 #include "mg_mortar_trace.hpp"
+#include "mg_mortar_next.hpp"
 
 namespace mg {
 using namespace v1;  // raster generation 1 (see mg_raster_v1.hpp)
@@ -287,12 +290,7 @@ class MortarFamily : public Family {
     void reset(const int64_t* seeds, const uint8_t* mask, void* obs, float* gt, hipStream_t s) override {
         if (dirty_) rebuild();
         require_seeded(seeds);
-        for (size_t k = 0; k < sets_.size(); ++k) {  // the display schedule (commands x (duration + delay) entries) is indexed with 16 bits
-            const MortarOpt& O = sets_[k];
-            const long long n_max = P_.variant == V_ENDLESS ? O.P.initial_count : O.st_command_count.max(O.P.command_count);
-            if (!P_.taskb && n_max * ((long long)O.st_show_dur.max(O.P.show_dur) + O.st_show_delay.max(O.P.show_delay)) > 65535)
-                throw OptionError{-3, "command_count x (command_show_duration + command_show_delay) exceeds the 65,535 entries of this build's display schedule"};
-        }
+        check_schedules();
         if (seeds) seeded_ = true;  // with a mask the caller is responsible for having seeded the other instances
         sets_.upload(s);
         with_bool(sets_.per_set(), [&](auto PS) {
@@ -363,6 +361,31 @@ class MortarFamily : public Family {
         prof.begin(1, s);
         raster(obs, s);
         prof.end(1, s);
+    }
+
+    // mg_step_next in three launches (mg_mortar_next.hpp): the NEXT form of the two-launch step -- mortar_step_next_kernel, the dense raster, the settle launch.
+    // The one-launch step (mortar_step_raster_kernel) is left alone.  Lab build, MEMGYM_NEXT_FUSE=0: the composed form of mg_api.hip, for A/B
+    // measurements (tools/next_step_bench.py flips it between calls of one process: read at every call)
+    bool step_next(const int32_t* actions, const uint8_t* restart, uint8_t* restart_copy, void* obs, float* reward, uint8_t* done, float* gt,
+                   const mg_info_dev* info, hipStream_t s) override {
+        if (!lab_flag("MEMGYM_NEXT_FUSE", true)) return false;
+        const mg_info_dev ib = begin_step(info);
+        check_schedules();  // (what the masked reset of the definition refuses, before anything is stepped)
+        sets_.upload(s);
+        const MortarStepArgs sa{P_, n_, io(), actions, reward, done, gt_dim() ? gt : nullptr, ib, 0, handover_.p, nullptr};
+        const int sb = step_block(256);
+        prof.begin(0, s);
+        with_bool(sets_.per_set(), [&](auto PS) {
+            launch(mortar_step_next_kernel<decltype(PS)::value>, dim3((n_ + sb - 1) / sb), dim3(sb), 0, s, sa, restart, restart_copy);
+        });
+        end_logic(s);
+        prof.begin(1, s);
+        raster(obs, s);
+        prof.end(1, s);
+        with_bool(sets_.per_set(), [&](auto PS) {
+            launch_checked(mortar_next_settle_kernel<decltype(PS)::value>, dim3((n_ + 255) / 256), dim3(256), 0, s, P_, n_, io(), (const uint8_t*)restart_copy);
+        });
+        return true;
     }
 
     // mg_advance inside ONE launch per ADVANCE_MAX_STEPS steps (mg_mortar_advance.hpp); lab build, MEMGYM_MORTAR_ADVANCE_FUSE=0: the loop form
@@ -521,6 +544,15 @@ class MortarFamily : public Family {
     static bool fuse_step() {  // lab build: MEMGYM_MORTAR_FUSE=0 selects the two-launch form for A/B measurements
         static const bool on = lab_flag("MEMGYM_MORTAR_FUSE", true);
         return on;
+    }
+    // head of every reset: the display schedule (commands x (duration + delay) entries) is indexed with 16 bits
+    void check_schedules() {
+        for (size_t k = 0; k < sets_.size(); ++k) {
+            const MortarOpt& O = sets_[k];
+            const long long n_max = P_.variant == V_ENDLESS ? O.P.initial_count : O.st_command_count.max(O.P.command_count);
+            if (!P_.taskb && n_max * ((long long)O.st_show_dur.max(O.P.show_dur) + O.st_show_delay.max(O.P.show_delay)) > 65535)
+                throw OptionError{-3, "command_count x (command_show_duration + command_show_delay) exceeds the 65,535 entries of this build's display schedule"};
+        }
     }
     MortarIO io() {
         MortarIO o;

@@ -14,6 +14,8 @@
 //   mg_spot_logic.hpp    reset and step of one instance: new_spot, new_spots_at_reset, spot_reset, spot_step_body and the clock build's hooks
 //   mg_spot_serve.hpp    spot_reset_kernel, spot_step_kernel and spot_raster_serve_kernel with its launch constants
 //   mg_spot_expert.hpp   spot_expert_kernel: the scripted teacher of both ids (mg_expert_actions), a launch of its own
+//   mg_spot_next.hpp     spot_step_next_kernel / spot_next_settle_kernel: the NEXT form of the two-launch step (mg_step_next), a flagged instance is reset by its
+//                        16 lanes instead of stepped
 //
 // The launches of a step as shipped (auto-reset, one option set, uint8 observations; why, and the figures: DESIGN.md and fuse_resets() below):
 //   two launches   spot_step_kernel: SIXTEEN LANES per instance (4 instances per wave).  Lane s owns spotlight slot s: float64 trajectory (lerp of lerp, un-fused
@@ -44,6 +46,7 @@
 #include "mg_spot_logic.hpp"
 #include "mg_spot_serve.hpp"
 #include "mg_spot_expert.hpp"
+#include "mg_spot_next.hpp"
 
 namespace mg {
 
@@ -291,20 +294,7 @@ class SpotFamily : public Family {
     void reset(const int64_t* seeds, const uint8_t* mask, void* obs, float* gt, hipStream_t s) override {
         if (dirty_) rebuild();
         require_seeded(seeds);
-        for (size_t k = 0; k < sets_.size(); ++k) {   // 16 spotlight slots per instance.  Refuse option sets that overflow them in ANY episode that lasts as long
-            // as the fastest spotlight lives (t reaches 1 after ceil(1 / speed) steps, the slot is freed one step later);
-            // rarer overflows raise error bit 1, which mg_peek_errors shows without a synchronisation.
-            const SpotParams& Q = sets_[k].P;
-            if (Q.r_hi <= Q.r_lo) throw OptionError{-3, "spot radius range not supported"};
-            const int life_min = (int)std::ceil(1.0 / Q.speed_hi) + 1;
-            const int interval = P_.endless ? Q.spawn_interval : P_.interval0;
-            int later = interval > 0 ? (life_min - 1) / interval : 1 << 20;
-            if (!P_.endless && later > Q.num_spawns) later = Q.num_spawns;
-            if (Q.initial_spawns + later > SLOTS)
-                throw std::runtime_error("these options keep " + std::to_string(Q.initial_spawns + later) +
-                                         " spotlights alive at once; this build holds " + std::to_string(SLOTS) +
-                                         " per instance (raise spawn_interval / spot_max_speed or lower initial_spawns)");
-        }
+        check_slots();
         if (seeds) seeded_ = true;
         sets_.upload(s);
         const dim3 rg((n_ * SLOTS + 255) / 256);
@@ -385,6 +375,32 @@ class SpotFamily : public Family {
 #endif
     }
 
+    // mg_step_next in three launches (mg_spot_next.hpp): the NEXT form of the two-launch step -- spot_step_next_kernel, the dense raster, the settle launch.
+    // The fused serve launch (spot_raster_serve_kernel) is left alone: without auto-reset nothing is deferred.  Lab build, MEMGYM_NEXT_FUSE=0: the composed
+    // form of mg_api.hip, for A/B measurements (tools/next_step_bench.py flips it between calls of one process: read at every call)
+    bool step_next(const int32_t* actions, const uint8_t* restart, uint8_t* restart_copy, void* obs, float* reward, uint8_t* done, float* gt,
+                   const mg_info_dev* info, hipStream_t s) override {
+        if (!lab_flag("MEMGYM_NEXT_FUSE", true)) return false;
+        const mg_info_dev ib = begin_step(info);
+        check_slots();  // (what the masked reset of the definition refuses, before anything is stepped)
+        sets_.upload(s);
+        prof.begin(0, s);
+        const int sb = step_block(256);
+        const SpotStepArgs sa{P_, io(), actions, reward, done, gt, ib, 0, 0};
+        const dim3 sg((n_ * SLOTS + sb - 1) / sb);
+        with_bool(P_.endless, [&](auto EN) {
+            with_bool(sets_.per_set(), [&](auto PS) {
+                launch(spot_step_next_kernel<decltype(EN)::value, decltype(PS)::value>, sg, dim3(sb), 0, s, sa, restart, restart_copy);
+            });
+        });
+        end_logic(s);
+        prof.begin(1, s);
+        raster(obs, s);
+        prof.end(1, s);
+        launch_checked(spot_next_settle_kernel, dim3((n_ + 255) / 256), dim3(256), 0, s, n_, io(), (const uint8_t*)restart_copy);
+        return true;
+    }
+
     std::vector<std::pair<void*, size_t>> state_blobs() override {
         std::vector<std::pair<void*, size_t>> v = {{core_.p, core_.bytes()}, {coins_.p, coins_.bytes()}, {sp_r_.p, sp_r_.bytes()},
                                                   {sp_ang_.p, sp_ang_.bytes()}};
@@ -443,6 +459,23 @@ class SpotFamily : public Family {
 
    private:
     int64_t spot_fused_steps_ = 0;  // debug_counter("spot_fused_steps")
+    // head of every reset: 16 spotlight slots per instance.  Refuse option sets that overflow them in ANY episode that lasts as long
+    // as the fastest spotlight lives (t reaches 1 after ceil(1 / speed) steps, the slot is freed one step later);
+    // rarer overflows raise error bit 1, which mg_peek_errors shows without a synchronisation.
+    void check_slots() {
+        for (size_t k = 0; k < sets_.size(); ++k) {
+            const SpotParams& Q = sets_[k].P;
+            if (Q.r_hi <= Q.r_lo) throw OptionError{-3, "spot radius range not supported"};
+            const int life_min = (int)std::ceil(1.0 / Q.speed_hi) + 1;
+            const int interval = P_.endless ? Q.spawn_interval : P_.interval0;
+            int later = interval > 0 ? (life_min - 1) / interval : 1 << 20;
+            if (!P_.endless && later > Q.num_spawns) later = Q.num_spawns;
+            if (Q.initial_spawns + later > SLOTS)
+                throw std::runtime_error("these options keep " + std::to_string(Q.initial_spawns + later) +
+                                         " spotlights alive at once; this build holds " + std::to_string(SLOTS) +
+                                         " per instance (raise spawn_interval / spot_max_speed or lower initial_spawns)");
+        }
+    }
     SpotIO io() {
         SpotIO o;
         o.core = core_.p;

@@ -17,16 +17,21 @@ from . import envs  # noqa: F401,E402
 
 
 def make(env_id, num_envs=None, device=None, render_mode=None, obs_format="u8_xyc", final_observation=False, obs_buffer=None,
-         obs_placement=None, ground_truth64=False, on_capacity="raise", capacity=None, final_frames=False):
+         obs_placement=None, ground_truth64=False, on_capacity="raise", capacity=None, autoreset_mode="same_step", final_frames=False):
+    """autoreset_mode (batched handles): "same_step" -- an instance that finishes is reset inside the call (default); "next_step" -- gymnasium >= 1.0's
+    convention, the step after the one that ends an episode resets (VecMemoryGym.step); "disabled" -- autoreset = False, the caller resets."""
     if final_observation and final_frames:
         raise ValueError("final_observation=True together with final_frames=True: terminal frames are kept as frames or as records, pick one")
     if num_envs is None:
+        if autoreset_mode != "same_step":
+            raise ValueError("autoreset_mode belongs to batched handles (num_envs=...): the single-instance adapter never resets by itself")
         if env_id not in envs.CLASSES:
             raise ValueError("unknown env id %r" % (env_id,))
         return envs.CLASSES[env_id](render_mode=render_mode, device=device, capacity=capacity)
     return VecMemoryGym(env_id, num_envs=num_envs, device=device, render_mode=render_mode, obs_format=obs_format,
                         final_observation=final_observation, obs_buffer=obs_buffer, obs_placement=obs_placement,
-                        ground_truth64=ground_truth64, on_capacity=on_capacity, capacity=capacity, final_frames=final_frames)
+                        ground_truth64=ground_truth64, on_capacity=on_capacity, capacity=capacity, final_frames=final_frames,
+                        autoreset_mode=autoreset_mode)
 
 
 def _register_with_gymnasium():

@@ -75,6 +75,8 @@ def _load():
     if hasattr(L, "mg_step_masked"):  # (absent from the older builds tools/ A/B against through MEMGYM_HIP_LIB)
         L.mg_step_masked.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(InfoBuffers),
                                      C.c_int, C.c_void_p]
+    if hasattr(L, "mg_step_next"):  # (absent from the older builds tools/ A/B against through MEMGYM_HIP_LIB)
+        L.mg_step_next.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(InfoBuffers), C.c_void_p]
     L.mg_render.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.mg_render_debug.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.mg_state_size.argtypes = [C.c_void_p]

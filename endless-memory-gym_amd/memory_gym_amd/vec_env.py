@@ -353,11 +353,20 @@ class VecMemoryGym:
     OBS_FORMATS = {"u8_xyc": (0, torch.uint8, (84, 84, 3)), "f32_chw": (1, torch.float32, (3, 84, 84)),
                    "f16_chw": (2, torch.float16, (3, 84, 84)), "bf16_chw": (3, torch.bfloat16, (3, 84, 84)),
                    "u8_chw": (4, torch.uint8, (3, 84, 84))}
+    # "same_step": an instance that finishes is reset inside the call (gymnasium 0.29's vector convention); "disabled": autoreset = False, the caller
+    # resets with a masked reset(); "next_step": gymnasium >= 1.0's AutoresetMode.NEXT_STEP (include/memgym.h: mg_step_next), see step()
+    AUTORESET_MODES = ("same_step", "next_step", "disabled")
 
     def __init__(self, env_id, num_envs=1, device=None, render_mode=None, obs_format="u8_xyc", final_observation=False,
-                 obs_buffer=None, obs_placement=None, ground_truth64=False, on_capacity="raise", capacity=None, final_frames=False):
+                 obs_buffer=None, obs_placement=None, ground_truth64=False, on_capacity="raise", capacity=None,
+                 autoreset_mode="same_step", final_frames=False):
         if env_id not in DEFAULTS:
             raise ValueError("unknown env id %r" % (env_id,))
+        if autoreset_mode not in self.AUTORESET_MODES:
+            raise ValueError("autoreset_mode must be one of %s" % (self.AUTORESET_MODES,))
+        if autoreset_mode == "next_step" and (final_observation or final_frames):
+            raise ValueError("autoreset_mode='next_step' together with final_observation=True / final_frames=True: there are no terminal rows in "
+                             "this mode, the observation of the step that ends an episode IS the terminal observation")
         if obs_format not in self.OBS_FORMATS:
             raise ValueError("obs_format must be one of %s" % sorted(self.OBS_FORMATS))
         if final_observation and final_frames:
@@ -473,7 +482,10 @@ class VecMemoryGym:
         self._set_params = [self._applied]  # what each option set of the handle holds (set 0 = the handle-wide one)
         self._set_of = None                 # int32 [N]: the set instance i runs under, once a masked reset has used other options
         self.max_episode_steps = None
-        self.autoreset = True
+        self.autoreset = autoreset_mode != "disabled"
+        # next-step auto-reset: fixed for the handle's life.  The PENDING flags are `done_u8` itself -- the done of the last step() -- which step() hands
+        # to mg_step_next as restart_dev and done_dev at once; _clear_pending() zeroes them in every call whose results are defined on the states as they stand
+        self._next_step = autoreset_mode == "next_step"
         self._seeded = False  # no instance has an RNG stream before the first reset (or load_state_dict)
         self._swapped = False  # use_obs_buffer() since the last call that wrote every row
         self._stale = False    # step(render=False) / advance(render=False) since the last call that wrote every row: `obs` holds old bytes
@@ -635,6 +647,7 @@ class VecMemoryGym:
                 # right before the swap stay as they are: mg_render.)
                 _native.check(_native.LIB.mg_render(self._h, self.obs.data_ptr(), self._stream()), "mg_render")
             self._swapped = self._stale = False
+            self._clear_pending()
             _native.check(_native.LIB.mg_reset(self._h, None if s is None else s.data_ptr(),
                                                None if m is None else m.data_ptr(), self.obs.data_ptr(),
                                                self.gt.data_ptr() if self.gt_dim else None, self._stream()), "mg_reset")
@@ -660,7 +673,16 @@ class VecMemoryGym:
         episode record "reward" / "length", the named aux infos, "capacity_exceeded" aside, which is False) keep their previous contents.
         A mask of the wrong length raises ValueError before anything is stepped; mask=None is the ordinary step.  render=False with a
         mask is the masked headless step.  Evaluation of one episode per seed: `finished |= done` and step(a, mask=~finished) until all
-        are finished (examples/evaluate_seeds.py)."""
+        are finished (examples/evaluate_seeds.py).
+        autoreset_mode="next_step" (include/memgym.h: mg_step_next; gymnasium >= 1.0's default): the step that ends an episode returns the TERMINAL
+        observation as its ordinary observation -- bootstrap from `obs` where `done` -- and the following step() ignores that instance's action and
+        returns the first observation of the new episode with reward 0 and done False.  The pending flags are the done of the handle's last step();
+        reset(), advance(), advance_traced(), play(), load_instances(), copy_instances() and load_state_dict() clear them.  info["done_mask"] and the
+        episode-record rows are valid where done; there is no "final_observation" / "final_frames" key.  mask=... and render=False are refused
+        (ValueError) before anything is stepped."""
+        if self._next_step and (mask is not None or not render):
+            raise ValueError("step(%s) on a handle with autoreset_mode='next_step': the mode has neither a masked nor a headless form"
+                             % ("mask=..." if mask is not None else "render=False"))
         if not render and self.final_obs is not None:
             raise ValueError("step(render=False) on a handle with final_observation=True: terminal observations are frames")
         m = None
@@ -698,7 +720,22 @@ class VecMemoryGym:
                 info["final_frames"] = self.final_frames
         return (self._obs() if render else None), self.reward, self._done_bool, self._truncated, info
 
+    def _clear_pending(self):
+        """autoreset_mode="next_step": no instance is restarted by the next step()."""
+        if self._next_step:
+            self.done_u8.zero_()
+
+    @property
+    def autoreset_mode(self):
+        return "next_step" if self._next_step else ("same_step" if self.autoreset else "disabled")
+
     def _launch_step(self, a, render=True, m=None):
+        if self._next_step:  # restart_dev IS done_dev: each instance's flag is read before its done is written
+            rc = _native.LIB.mg_step_next(self._h, a.data_ptr(), self._p_done, self.obs.data_ptr(), self._p_reward, self._p_done, self._p_gt, self._p_info,
+                                          self._raw_stream())
+            if rc != 0:
+                _native.check(rc, "mg_step_next")
+            return
         if m is not None:
             if render and (self._swapped or self._stale):
                 # a drawn masked step writes the rows of the active instances only: after use_obs_buffer() or headless steps the other rows
@@ -795,6 +832,7 @@ class VecMemoryGym:
             self._adv = (t, out)
         mask = (1 << 64) - 1
         with torch.cuda.device(self.device):
+            self._clear_pending()
             if trace is not None:
                 rows = self._trace_rows(trace, True)
                 _native.check(_native.LIB.mg_advance_traced(self._h, steps, float(eps), int(seed) & mask, int(self._expert_calls if step is None else step) & mask,
@@ -880,6 +918,7 @@ class VecMemoryGym:
                          torch.zeros((K, self.num_envs), dtype=torch.uint8, device=self.device))
         rt, dt = traces[K] if trace else (None, None)
         with torch.cuda.device(self.device):
+            self._clear_pending()
             if ro is not None:
                 rows = self._trace_rows(ro, False)
                 _native.check(_native.LIB.mg_play_traced(self._h, a.data_ptr(), K, _native.MG_PLAY_EPISODE if until_done else _native.MG_PLAY_THROUGH,
@@ -1112,6 +1151,7 @@ class VecMemoryGym:
                 pr = torch.zeros(total, dtype=torch.int32, device=self.device)
                 pr[:m] = torch.arange(m, dtype=torch.int32, device=self.device) if rec is None else rec
                 calls = [(pi[c:c + k], pr[c:c + k]) for c in range(0, total, k)]
+            self._clear_pending()
             for ci, cr in calls:
                 _native.check(_native.LIB.mg_load_instances(self._h, None if ci is None else ci.data_ptr(), None if cr is None else cr.data_ptr(), k,
                                                             snap.records.data_ptr(), obs_ptr, self._stream()), "mg_load_instances")
@@ -1195,6 +1235,8 @@ class VecMemoryGym:
                 raise ValueError("use_step_buffers: need contiguous float32 [N] / uint8 [N] tensors on the handle's device")
         if reward.data_ptr() % 4:
             raise ValueError("use_step_buffers: the reward tensor must be 4-byte aligned")
+        if self._next_step:  # (the done tensor holds the pending flags: they move with it)
+            done_u8.copy_(self.done_u8)
         self.reward, self.done_u8 = reward, done_u8
         self._bind_step()
 
@@ -1232,6 +1274,8 @@ class VecMemoryGym:
         if self._set_of is not None:  # per-instance option sets in use
             sd["option_sets"] = [dict(p) for p in self._set_params]
             sd["set_of"] = self._set_of.cpu().numpy()
+        if self._next_step:  # the pending flags belong to a rollout in this mode: a checkpointed one resumes bit for bit
+            sd["next_step_pending"] = self.done_u8.cpu().numpy().copy()
         return sd
 
     def load_state_dict(self, sd):
@@ -1266,6 +1310,9 @@ class VecMemoryGym:
             buf = np.ascontiguousarray(sd["blob"], dtype=np.uint8)
             _native.check(_native.LIB.mg_set_state(self._h, buf.ctypes.data, buf.size), "mg_set_state")
             self._seeded = bool(sd.get("seeded", True))  # (env.obs shows the restored episodes from the next step on)
+            self._clear_pending()
+            if self._next_step and sd.get("next_step_pending") is not None:
+                self.done_u8.copy_(torch.as_tensor(np.asarray(sd["next_step_pending"], dtype=np.uint8), device=self.device))
 
     def set_profiling(self, every):
         """Bracket the kernels of every `every`-th step with HIP events (0/False = off, 1/True = every step)."""

@@ -27,7 +27,23 @@ except Exception:  # gymnasium is not a dependency of the hot path
 
 
 class GymnasiumVectorEnv(_Base):
-    def __init__(self, env_id, num_envs, device=None, obs_format="u8_xyc", as_numpy=False, on_capacity="raise", capacity=None, final_frames=False):
+    def __init__(self, env_id, num_envs, device=None, obs_format="u8_xyc", as_numpy=False, on_capacity="raise", capacity=None,
+                 autoreset_mode="same_step", final_frames=False):
+        # autoreset_mode="next_step": gymnasium >= 1.0's default convention (AutoresetMode.NEXT_STEP; include/memgym.h: mg_step_next) -- the step that ends an
+        # episode returns the terminal observation as `obs`, the following step ignores that sub-environment's action and returns the first observation of
+        # the new episode with reward 0 and both flags False.  There is no "final_observation" / "final_info": the end-of-episode entries ("reward", "length",
+        # the id's aux names) are [N] arrays directly in `infos`, with masks infos["_" + key], as gymnasium >= 1.0 aggregates sub-environment infos.
+        if autoreset_mode not in ("same_step", "next_step"):
+            raise ValueError("GymnasiumVectorEnv: autoreset_mode must be 'same_step' or 'next_step'")
+        self.autoreset_mode = autoreset_mode
+        if autoreset_mode == "next_step":
+            if final_frames:
+                raise ValueError("autoreset_mode='next_step' together with final_frames=True: there are no terminal rows in this mode")
+            self.final_frames = False
+            self.env = VecMemoryGym(env_id, num_envs=num_envs, device=device, obs_format=obs_format, ground_truth64=bool(as_numpy), on_capacity=on_capacity,
+                                    capacity=capacity, autoreset_mode="next_step")
+            self._finish_init(num_envs, as_numpy)
+            return
         # as_numpy: gymnasium's host-side layout with the reference's dtypes -- rewards and info["ground_truth"] as float64
         # on_capacity="truncate": a sub-environment whose episode this build ended on one of its capacities (VecMemoryGym) comes back with
         # terminations[i] = False and truncations[i] = True, like a time limit; its final_observation / final_info are set as for any end
@@ -37,6 +53,9 @@ class GymnasiumVectorEnv(_Base):
         self.final_frames = bool(final_frames)
         self.env = VecMemoryGym(env_id, num_envs=num_envs, device=device, obs_format=obs_format, final_observation=not self.final_frames,
                                 ground_truth64=bool(as_numpy), on_capacity=on_capacity, capacity=capacity, final_frames=self.final_frames)
+        self._finish_init(num_envs, as_numpy)
+
+    def _finish_init(self, num_envs, as_numpy):
         self.as_numpy = bool(as_numpy)
         done = False
         if _Base is not object:  # gymnasium 0.29: VectorEnv.__init__(num_envs, observation_space, action_space) batches the spaces
@@ -52,7 +71,12 @@ class GymnasiumVectorEnv(_Base):
             self.single_action_space = self.env.action_space
             self.observation_space, self.action_space = self._batched_spaces()
             self.closed = False
-        self.metadata = self.env.metadata
+        self.metadata = dict(self.env.metadata)  # (a copy: the mode is this object's, not the class's)
+        try:  # gymnasium >= 1.0 names the modes; older ones (and hosts without gymnasium) get the string
+            from gymnasium.vector import AutoresetMode
+            self.metadata["autoreset_mode"] = AutoresetMode.NEXT_STEP if self.autoreset_mode == "next_step" else AutoresetMode.SAME_STEP
+        except Exception:
+            self.metadata["autoreset_mode"] = self.autoreset_mode
         self.spec = None
 
     def _batched_spaces(self):
@@ -73,7 +97,24 @@ class GymnasiumVectorEnv(_Base):
         obs, info = self.env.reset(seed=seed, options=options)
         return self._host(obs), self._host(info)
 
+    def _step_next(self, actions):
+        obs, reward, done, trunc, info = self.env.step(actions)
+        term = done if self.env.capacity_u8 is None else (done & ~trunc)  # gymnasium: an episode ends EITHER terminated or truncated
+        infos = {}
+        if "ground_truth" in info:
+            infos["ground_truth"] = info["ground_truth"]
+        if "capacity_exceeded" in info:
+            infos["capacity_exceeded"] = info["capacity_exceeded"]
+        for k in ["reward", "length"] + list(self.env.info_names):  # rows valid where the mask is set
+            infos[k] = info[k]
+            infos["_" + k] = done
+        if not self.as_numpy:
+            return obs, reward, term, trunc, infos
+        return self._host(obs), self.env.reward64.cpu().numpy(), term.cpu().numpy(), trunc.cpu().numpy(), self._host(infos)
+
     def step(self, actions):
+        if self.autoreset_mode == "next_step":
+            return self._step_next(actions)
         obs, reward, done, trunc, info = self.env.step(actions, render=not self.final_frames)
         ep = {"reward": info["reward"], "length": info["length"]}
         for nm in self.env.info_names:

@@ -259,6 +259,36 @@ int mg_step(mg_env* env, const int32_t* actions_dev, void* obs_dev, float* rewar
 int mg_step_masked(mg_env* env, const int32_t* actions_dev, const uint8_t* active_dev, void* obs_dev, float* reward_dev,
                    uint8_t* done_dev, float* gt_dev, const mg_info_buffers* info, int autoreset, void* stream);
 
+/* NEXT-STEP AUTO-RESET (gymnasium >= 1.0, AutoresetMode.NEXT_STEP): Env.step(action) (e.g. mortar_mayhem_grid.py:280-375) for the instances with
+ * restart_dev[i] == 0, Env.reset() (seed=None, :213-278) for those with restart_dev[i] != 0 -- the caller feeds the previous call's done_dev back in, so
+ * that the step that ends an episode returns the TERMINAL observation as its ordinary observation and the following call returns the first observation
+ * of the new episode, with reward 0 and done 0.  restart_dev: uint8 [num_envs], read on `stream` by the call's launches; the host never looks at it.
+ * DEFINITION: the pair  mg_step_masked(env, actions_dev, active = !restart, obs_dev, reward_dev, done_dev, gt_dev, info, autoreset = 0, stream);
+ *                       mg_reset(env, NULL, restart, obs_dev, gt_dev, stream);   [+ mg_ground_truth64 into info->gt64_dev where that is set]
+ *   restart_dev[i] != 0  the instance is reset instead of stepped: its PCG64 stream continues (seeds_dev == NULL), it keeps the option set it has, its action
+ *                        entry is not interpreted; reward_dev[i] = 0, done_dev[i] = 0, and where given reward64_dev[i] = 0 and capacity_dev[i] = 0; its rows of
+ *                        ep_reward_dev, ep_length_dev and aux_dev[k] keep their previous contents; its rows of obs_dev, gt_dev, gt64_dev and the bound vector
+ *                        observation are the reset's.
+ *   restart_dev[i] == 0  everything mg_step(..., autoreset = 0) would do to the instance, bit for bit; row i of obs_dev is the frame after the step, which is
+ *                        the terminal frame where done_dev[i] is set, and the instance stays in its terminal state until a later call restarts it.
+ * Every row of obs_dev is written.  The handle's memory afterwards is the pair's, bit for bit -- also the frame descriptor rows: those of the instances
+ * that were not restarted are marked "leave the frame untouched" as after any masked mg_reset (mg_render / mg_save_frames right behind the call skip
+ * them; obs_dev holds their frames, and their next step rewrites the rows).
+ * ALIASING: restart_dev == done_dev is legal and the intended use.  Each instance's flag is read before its done is written.
+ * Launches: the mortar and the spotlight family run the NEXT form of their two-launch step -- mortar_step_next_kernel / spot_step_next_kernel, in which a
+ * flagged instance is reset by its own lane(s), the family's dense raster launch, and one small launch that settles the descriptor rows; their
+ * one-launch / fused serve arrangements are not used.  The Mystery Path ids run the pair itself behind one small launch that writes the mask and a copy
+ * of the flags into the handle's scratch.  A linear chain on `stream`, nothing synchronises; the handle's first call allocates that scratch (2 x
+ * num_envs bytes) and therefore refuses a stream that is being captured, later calls can be captured into a HIP graph: restart_dev and actions_dev are
+ * read at replay.  Per-instance option sets and every observation format work as documented; MG_STATE_VERSION is unchanged: no state is added.
+ * mg_debug_counter "next_steps" counts the calls, "next_fused_steps" those that took a family's own kernel.
+ * Refused (-1) before anything is stepped: before the first mg_reset / mg_set_state; a NULL actions_dev, restart_dev, obs_dev, reward_dev or done_dev
+ * (there is no headless next-step call: mg_reset has no headless form); info->final_obs_dev or info->final_frames_dev set (there are no terminal rows
+ * in this mode: the terminal frame is the observation); a geometry option set since the last reset.  An active mask together with restart flags does
+ * not exist. */
+int mg_step_next(mg_env* env, const int32_t* actions_dev, const uint8_t* restart_dev, void* obs_dev, float* reward_dev,
+                 uint8_t* done_dev, float* gt_dev, const mg_info_buffers* info, void* stream);
+
 /* The float64 ground truth of every instance from the CURRENT state (what the last mg_reset / mg_step left), [num_envs][mg_gt_dim]
  * on the device: the doubles the reference puts into info["ground_truth"] after reset() as well as after step().  Enqueued on
  * `stream`; a no-op for env ids without ground truth. */
