@@ -10,6 +10,7 @@
 #include "mg_frame_records.hpp"
 #include "mg_instances.hpp"
 #include "mg_lab.hpp"
+#include "mg_sequences.hpp"
 
 namespace mg {
 static thread_local std::string g_last_error;
@@ -56,6 +57,14 @@ struct mg_env {
     int64_t instance_saves = 0, instance_loads = 0;
     int64_t frame_saves = 0, frame_draws = 0;  // mg_debug_counter: mg_save_frames / mg_draw_frames calls with count > 0
     int64_t debug_frame_saves = 0, debug_frame_draws = 0;  // mg_debug_counter: mg_save_debug_frames / mg_draw_debug_frames calls with count > 0
+    // mg_split_episodes / mg_draw_frames_padded: the host-side counters, and what a split passes from its count launch to its write launch, allocated at
+    // the handle's first split (include/memgym.h)
+    int64_t sequence_splits = 0, padded_draws = 0;
+    struct Sequences {
+        bool ready = false;
+        mg::DevArray<int32_t> first;      // [num_envs] the sequences of the workgroup's instances in front of this one
+        mg::DevArray<int32_t> block_sum;  // [ceil(num_envs / SEQ_BLOCK)] the workgroup's sum, then the sum of the workgroups in front of it
+    } seq;
     struct Instances {
         bool ready = false;
         mg::DevArray<int32_t> claim;  // [num_envs] the entry of the current load that holds the instance
@@ -845,6 +854,63 @@ int mg_draw_frames(mg_env* env, const void* rec_dev, int64_t n_records, const in
     });
 }
 
+// ---- episode sequences (include/memgym.h: mg_split_episodes / mg_sequence_picks / mg_draw_frames_padded; mg_sequences.hpp and the PAD forms of the two
+// gather rasters) ----
+int mg_split_episodes(mg_env* env, const uint8_t* done_dev, int32_t steps, const int32_t* steps_of_dev, const uint8_t* start_dev, int32_t length,
+                      mg_sequence* seq_dev, int32_t capacity, int32_t* count_dev, void* stream) {
+    return guarded(env, [&] {
+        const std::string who = "mg_split_episodes: ";
+        if (!env->started) throw std::runtime_error(who + "before the first mg_reset / mg_set_state");
+        if (const char* no = mg::split_refusal(done_dev, steps, length, seq_dev, capacity, count_dev, env->num_envs)) throw std::runtime_error(who + no);
+        hipStream_t st = (hipStream_t)stream;
+        const int n = env->num_envs, blocks = (n + mg::SEQ_BLOCK - 1) / mg::SEQ_BLOCK;
+        mg_env::Sequences& Q = env->seq;
+        if (!Q.ready) {
+            if (mg::stream_capturing(st))
+                throw std::runtime_error(who + "the handle's first call allocates its scratch and cannot be captured; call it once eagerly");
+            Q.first.alloc(n);
+            Q.block_sum.alloc(blocks);
+            Q.ready = true;
+        }
+        hipLaunchKernelGGL(mg::seq_count_kernel, dim3(blocks), dim3(mg::SEQ_BLOCK), 0, st, done_dev, steps, n, steps_of_dev, length, Q.first.p, Q.block_sum.p);
+        MG_HIP(hipGetLastError());
+        hipLaunchKernelGGL(mg::seq_scan_kernel, dim3(1), dim3(mg::SEQ_BLOCK), 0, st, Q.block_sum.p, blocks, count_dev);
+        MG_HIP(hipGetLastError());
+        if (capacity > 0) {
+            hipLaunchKernelGGL(mg::seq_write_kernel, dim3(blocks), dim3(mg::SEQ_BLOCK), 0, st, done_dev, steps, n, steps_of_dev, start_dev, length,
+                               (const int32_t*)Q.first.p, (const int32_t*)Q.block_sum.p, (int4*)seq_dev, capacity);
+            MG_HIP(hipGetLastError());
+        }
+        ++env->sequence_splits;
+    });
+}
+
+int mg_sequence_picks(mg_env* env, const mg_sequence* seq_dev, const int32_t* count_dev, int32_t capacity, const int32_t* sel_dev, int32_t m,
+                      int32_t length, int32_t* pick_dev, uint8_t* mask_dev, void* stream) {
+    return guarded(env, [&] {
+        const std::string who = "mg_sequence_picks: ";
+        if (const char* no = mg::picks_refusal(seq_dev, count_dev, capacity, m, length, pick_dev)) throw std::runtime_error(who + no);
+        if (m == 0) return;
+        const int64_t lanes = (int64_t)m * length;
+        hipLaunchKernelGGL(mg::seq_picks_kernel, dim3((unsigned)((lanes + mg::SEQ_BLOCK - 1) / mg::SEQ_BLOCK)), dim3(mg::SEQ_BLOCK), 0, (hipStream_t)stream,
+                           (const int4*)seq_dev, count_dev, capacity, sel_dev, m, length, env->num_envs, pick_dev, mask_dev, env->fam->error_word());
+        MG_HIP(hipGetLastError());
+    });
+}
+
+int mg_draw_frames_padded(mg_env* env, const void* rec_dev, int64_t n_records, const int32_t* pick_dev, int64_t count, int format, void* obs_dev,
+                          void* stream) {
+    return guarded(env, [&] {
+        const std::string who = "mg_draw_frames_padded: ";
+        if (!env->started) throw std::runtime_error(who + "before the first mg_reset / mg_set_state");
+        if (const char* no = mg::frame_draw_refusal(rec_dev, n_records, pick_dev != nullptr, count, format, obs_dev)) throw std::runtime_error(who + no);
+        if (env->fam->geometry_dirty()) throw std::runtime_error(who + "options that change geometry need a reset first");
+        if (count == 0) return;
+        env->fam->draw_records_padded(rec_dev, (int)n_records, pick_dev, (int)count, format, obs_dev, (hipStream_t)stream);
+        ++env->padded_draws;
+    });
+}
+
 // ---- debug-view records (include/memgym.h: mg_save_debug_frames / mg_draw_debug_frames; the picked *_debug_desc kernels of the three families, the debug
 // gather forms of the two raster skeletons, mg_debug_stream_out.hpp) ----
 int mg_save_debug_frames(mg_env* env, const int32_t* idx_dev, int32_t count, void* rec_dev, void* stream) {
@@ -1129,6 +1195,10 @@ int mg_debug_counter(mg_env* env, const char* name, int64_t* value) {
         }
         if (std::string(name) == "frame_saves" || std::string(name) == "frame_draws") {  // every id: counted in this file
             *value = std::string(name) == "frame_saves" ? env->frame_saves : env->frame_draws;
+            return;
+        }
+        if (std::string(name) == "sequence_splits" || std::string(name) == "padded_draws") {  // every id: counted in this file
+            *value = std::string(name) == "sequence_splits" ? env->sequence_splits : env->padded_draws;
             return;
         }
         if (std::string(name) == "debug_frame_saves" || std::string(name) == "debug_frame_draws") {  // every id: counted in this file

@@ -324,6 +324,8 @@ class Family {
     // atlas; nothing of the handle is written.  The arguments have passed frame_draw_refusal().
     virtual std::pair<const void*, size_t> frame_rows() = 0;
     virtual void draw_records(const void* records, int n_records, const int32_t* pick, int count, int fmt, void* obs, hipStream_t s) = 0;
+    // mg_draw_frames_padded: draw_records() through the PAD form of the gather launch -- a pick below 0 writes its row as zeros and raises no error.
+    virtual void draw_records_padded(const void* records, int n_records, const int32_t* pick, int count, int fmt, void* obs, hipStream_t s) = 0;
     // true: step(..., autoreset = 1) with info->final_obs_dev set keeps the terminal observations ITSELF (the frame workgroup of a finishing
     // instance draws the terminal frame into final_obs_dev, then the reset frame into obs); false: mg_step takes the generic path (a step
     // without auto-reset, the terminal rows copied, a masked reset).  Asked once per call, on the stream of the call.

@@ -623,6 +623,10 @@ class MortarFamily : public Family {
         launch_raster_gather<MortarComposer>((const MortarDesc*)records, atlas_->dev(), obs, fmt, n_records, pick, count, err_.dev, s);
         check_launch();
     }
+    void draw_records_padded(const void* records, int n_records, const int32_t* pick, int count, int fmt, void* obs, hipStream_t s) override {
+        launch_raster_gather_pad<MortarComposer>((const MortarDesc*)records, atlas_->dev(), obs, fmt, n_records, pick, count, err_.dev, s);
+        check_launch();
+    }
     // (the one-launch step keeps terminal observations itself: the conditions under which step() takes that launch; lab
     // MEMGYM_MORTAR_FINAL_FUSED=0: the generic path of mg_step)
     bool keeps_final_obs(hipStream_t s) override {

@@ -245,6 +245,12 @@ class MysteryFamily : public Family {
         else launch_raster_gather<MysteryComposer>(rec, atlas_->dev(), obs, fmt, n_records, pick, count, err_.dev, s);
         check_launch();
     }
+    void draw_records_padded(const void* records, int n_records, const int32_t* pick, int count, int fmt, void* obs, hipStream_t s) override {
+        const MysteryDesc* rec = (const MysteryDesc*)records;
+        if (big_sprites_) launch_raster_gather_pad<MysteryBigComposer>(rec, atlas_->dev(), obs, fmt, n_records, pick, count, err_.dev, s);
+        else launch_raster_gather_pad<MysteryComposer>(rec, atlas_->dev(), obs, fmt, n_records, pick, count, err_.dev, s);
+        check_launch();
+    }
     // (Endless: the debug view reads the segment store -- owed segments are generated first, on the call's stream, as before an instance save)
     void save_debug_records(const int32_t* idx, int count, void* rec, hipStream_t s) override {
         before_instance_save(s);

@@ -47,6 +47,46 @@ inline void launch_raster_gather(const typename Composer::Desc* records, const R
     });
 }
 
+// The PAD form: mg_draw_frames_padded (include/memgym.h).  raster_gather_kernel with one difference -- a pick below 0 is a PADDING row: the workgroup
+// writes it as zeros (store_zero_row: 16-byte stores of a zero vector straight from registers; no compose, no LDS, no barrier) and raises no error.
+// A kernel of its own: the gather forms above are the measured ones and keep their symbols and their code.
+template <class Composer, int FMT>
+__global__ __launch_bounds__(256, 7) void raster_gather_pad_kernel(const typename Composer::Desc* __restrict__ records, RasterAtlas A, void* __restrict__ obs,
+                                                                int n_records, const int32_t* __restrict__ pick, int count, int* err) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const RasterCtx R = make_ctx(smem, A);
+    const int tid = threadIdx.x;
+    for (int j = blockIdx.x; j < count; j += gridDim.x) {
+        const int r = pick ? __builtin_amdgcn_readfirstlane(pick[j]) : j;  // workgroup-uniform: the descriptor pointer stays uniform (scalar loads)
+        if (r < 0) {
+            store_zero_row<FMT>(obs, j, tid);
+            continue;
+        }
+        if (r >= n_records) {
+            if (tid == 0) __hip_atomic_fetch_or(err, ERR_FRAME_INDEX, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            continue;
+        }
+        const typename Composer::Desc* d = records + r;
+        if (Composer::skip(d)) continue;
+        Composer::compose(d, R);
+        __syncthreads();
+        store_frame<FMT, false>(smem, obs, j, tid);
+        __syncthreads();  // the LDS frame is reused by the next iteration
+    }
+}
+
+// grid and LDS request: launch_raster_gather's
+template <class Composer>
+inline void launch_raster_gather_pad(const typename Composer::Desc* records, const RasterAtlas& atlas, void* obs, int fmt, int n_records,
+                                     const int32_t* pick, int count, int* err, hipStream_t s) {
+    const int forced_lds = lab_raster_lds(RASTER_LDS);
+    const int lds = forced_lds ? forced_lds : RASTER_LDS;
+    const dim3 grid(frames_grid(count));
+    with_obs_format(fmt, [&](auto F) {
+        launch(raster_gather_pad_kernel<Composer, decltype(F)::value>, grid, dim3(256), lds, s, records, atlas, obs, n_records, pick, count, err);
+    });
+}
+
 // mg_draw_debug_frames (include/memgym.h): the same walk over records of the DEBUG view's descriptors with a debug composer.  SIZE 84: the debug
 // surface in the observation layout (the uint8 frame's stream-out); SIZE 336: the reference's debug_rgb_array, stretched and turned on the way out
 // of LDS (mg_debug_stream_out.hpp).  Kernels of their own: no MG_OBS_* value names these rows.

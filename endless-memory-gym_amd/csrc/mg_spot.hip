@@ -625,6 +625,12 @@ class SpotFamily : public Family {
         });
         check_launch();
     }
+    void draw_records_padded(const void* records, int n_records, const int32_t* pick, int count, int fmt, void* obs, hipStream_t s) override {
+        with_bool(P_.ordered_holes, [&](auto BO) {
+            launch_raster_gather_pad<SpotComposerT<decltype(BO)::value>>((const SpotDesc*)records, atlas_->dev(), obs, fmt, n_records, pick, count, err_.dev, s);
+        });
+        check_launch();
+    }
 
     void save_debug_records(const int32_t* idx, int count, void* rec, hipStream_t s) override {
         sets_.upload(s);

@@ -234,4 +234,24 @@ __device__ __forceinline__ void store_frame(uint8_t* __restrict__ frame, void* _
     }
 }
 
+// A PADDING row (mg_draw_frames_padded, a pick below 0): row `env` of `obs` in format FMT as zeros, every byte -- 1,323 / 2,646 / 5,292 16-byte stores
+// of a zero vector straight from registers, lane-contiguous like the uint8 frame's (1 KiB per wave instruction); no LDS, no barrier, so any lane may
+// call it on its own.  The row offset is store_frame's: 64-bit, the uint8 formats' stride OBS_STRIDE_U8.  NT as for store_frame (uint8 format only).
+template <int FMT, bool NT = false>
+__device__ __forceinline__ void store_zero_row(void* __restrict__ obs, int env, int tid) {
+    constexpr bool U8 = FMT == MG_OBS_U8_XYC || FMT == MG_OBS_U8_CYX;
+    constexpr size_t STRIDE = U8 ? OBS_STRIDE_U8 : (size_t)FRAME_BYTES * (FMT == MG_OBS_F32_CYX ? 4 : 2);
+    constexpr int VEC16 = FRAME_VEC16 * (U8 ? 1 : (FMT == MG_OBS_F32_CYX ? 4 : 2));
+    u32x4* dst = reinterpret_cast<u32x4*>(static_cast<uint8_t*>(obs) + (size_t)env * STRIDE);
+    const u32x4 zero = (u32x4)(0u);
+#pragma unroll
+    for (int q = 0; q < (VEC16 + 255) / 256; ++q) {
+        const int at = tid + 256 * q;
+        if (256 * (q + 1) <= VEC16 || at < VEC16) {
+            if constexpr (NT) __builtin_nontemporal_store(zero, &dst[at]);
+            else dst[at] = zero;
+        }
+    }
+}
+
 }  // namespace mg

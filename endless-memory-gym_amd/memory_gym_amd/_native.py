@@ -39,6 +39,13 @@ class RolloutTraceRows(C.Structure):  # include/memgym.h: mg_rollout_trace (devi
                 ("reward_dev", C.c_void_p), ("done_dev", C.c_void_p)]
 
 
+class Sequence(C.Structure):  # include/memgym.h: mg_sequence, one entry of mg_split_episodes' table (16 bytes)
+    _fields_ = [("instance", C.c_int32), ("t0", C.c_int32), ("len", C.c_int32), ("flags", C.c_int32)]
+
+
+MG_SEQ_FIRST, MG_SEQ_LAST = 1, 2  # include/memgym.h: mg_sequence.flags
+
+
 class ObsAllocInfo(C.Structure):
     _fields_ = [("zones", C.c_int), ("pieces", C.c_int), ("piece_bytes", C.c_size_t), ("searched_bytes", C.c_size_t),
                 ("probe_same_tbps", C.c_double), ("probe_cross_tbps", C.c_double), ("search_ms", C.c_double)]
@@ -130,6 +137,10 @@ def _load():
     if hasattr(L, "mg_save_debug_frames"):  # (absent from the older builds tools/ A/B against through MEMGYM_HIP_LIB)
         L.mg_save_debug_frames.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
         L.mg_draw_debug_frames.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]
+    if hasattr(L, "mg_split_episodes"):  # (absent from the older builds tools/ A/B against through MEMGYM_HIP_LIB)
+        L.mg_split_episodes.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+        L.mg_sequence_picks.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mg_draw_frames_padded.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]
     L.mg_enable_peer_access.argtypes = [C.c_int, C.c_int]
     L.mg_debug_rng.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
     L.mg_debug_set_rng.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]

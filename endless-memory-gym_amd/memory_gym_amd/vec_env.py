@@ -347,6 +347,110 @@ def check_rollout_trace(ro, steps, num_envs, action_dim, record_bytes, teacher, 
             raise ValueError("%s: trace.%s must be %d-byte aligned" % (what, name, align))
 
 
+MAX_PICK = (1 << 31) - 1  # include/memgym.h: a pick is an int32 -- mg_split_episodes refuses (steps + 1) * num_envs beyond it
+
+
+def check_split_episodes(done, length, num_envs, steps=None, starts=None, capacity=None, device=None):
+    """The argument checks of split_episodes, which need no handle: -> (done as a uint8 view [K, N], K, length, steps as an int32 tensor [N] or None,
+    starts as a uint8 view [N] or None, capacity as an int or None).  ValueError for a `done` that is no contiguous bool / uint8 tensor [K, N] with
+    K >= 1 and N = num_envs, a length below 1, (K + 1) * N beyond an int32, `steps` that is no int32 / int64 tensor [N], `starts` that is no contiguous
+    bool / uint8 tensor [N], a negative capacity, and anything that does not lie on `device` (if given)."""
+    what = "split_episodes"
+    if not (isinstance(done, torch.Tensor) and done.dtype in (torch.bool, torch.uint8) and done.dim() == 2):
+        raise ValueError("%s: done must be a contiguous bool or uint8 tensor [K, N]" % what)
+    K, N = int(done.shape[0]), int(done.shape[1])
+    if N != int(num_envs) or K < 1:
+        raise ValueError("%s: done is %s, need [K >= 1, %d] (the handle's instances)" % (what, tuple(done.shape), int(num_envs)))
+    if (K + 1) * N > MAX_PICK:
+        raise ValueError("%s: (K + 1) * N = %d does not fit the int32 of a pick: split slices of the rollout" % (what, (K + 1) * N))
+    if not done.is_contiguous():
+        raise ValueError("%s: done must be a contiguous bool or uint8 tensor [K, N]" % what)
+    if isinstance(length, bool) or not isinstance(length, (int, np.integer)) or length < 1 or length > MAX_PICK:
+        raise ValueError("%s: length must be an integer >= 1, got %r" % (what, length))
+    if device is not None and done.device != device:
+        raise ValueError("%s: done is on %s, the handle on %s" % (what, done.device, device))
+    if steps is not None:
+        if not (isinstance(steps, torch.Tensor) and steps.dtype in (torch.int32, torch.int64) and tuple(steps.shape) == (N,)):
+            raise ValueError("%s: steps must be an int32 or int64 tensor [%d] (e.g. what play() returned as steps_played)" % (what, N))
+        if device is not None and steps.device != device:
+            raise ValueError("%s: steps is on %s, the handle on %s" % (what, steps.device, device))
+        steps = steps.to(torch.int32).contiguous()
+    if starts is not None:
+        if not (isinstance(starts, torch.Tensor) and starts.dtype in (torch.bool, torch.uint8) and tuple(starts.shape) == (N,) and starts.is_contiguous()):
+            raise ValueError("%s: starts must be a contiguous bool or uint8 tensor [%d]" % (what, N))
+        if device is not None and starts.device != device:
+            raise ValueError("%s: starts is on %s, the handle on %s" % (what, starts.device, device))
+        starts = starts.view(torch.uint8)
+    if capacity is not None:
+        if isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer)) or capacity < 0 or capacity > MAX_PICK:
+            raise ValueError("%s: capacity must be an integer >= 0, got %r" % (what, capacity))
+        capacity = int(capacity)
+    return done.view(torch.uint8), K, int(length), steps, starts, capacity
+
+
+class EpisodeSequences:
+    """What VecMemoryGym.split_episodes returns (include/memgym.h: mg_split_episodes): a rollout of `steps` steps of `num_envs` instances cut into
+    episodes at done and chopped into sequences of at most `length` steps.
+        table    int32 [capacity, 4]   one row per sequence: instance, t0, len, flags (1: starts an episode, 2: ends with its episode's done), ordered
+                                       by (instance, t0); rows from the count on are untouched
+        count    int32 [1]             the true number of sequences, on the device (it may exceed the capacity: the table then holds the first `capacity`)
+    len(seqs) reads the count (a synchronisation); picks() and gather() do not."""
+    __slots__ = ("table", "count", "length", "steps", "num_envs", "_env")
+
+    def __init__(self, table, count, length, steps, num_envs, env=None):
+        self.table, self.count, self.length, self.steps, self.num_envs, self._env = table, count, int(length), int(steps), int(num_envs), env
+
+    @property
+    def capacity(self):
+        return int(self.table.shape[0])
+
+    def __len__(self):
+        s = int(self.count.item())
+        if s > self.capacity:
+            raise ValueError("EpisodeSequences: the rollout has %d sequences, the table holds %d: split again with capacity >= %d" % (s, self.capacity, s))
+        return s
+
+    def picks(self, sel=None, m=None):
+        """-> (pick int32 [M, L], mask bool [M, L]) (include/memgym.h: mg_sequence_picks): row j belongs to sequence sel[j] (sel=None: sequence j,
+        M = m, default len(self) -- which synchronises; m = capacity does not, rows beyond the count are padding).  pick[j, l] = (t0 + l) * N + instance
+        for l < len, -1 behind it: an index into the flattened [K + 1, N] frame store of the trace and into its flattened [K, N] action / label /
+        reward / done rows.  sel: an integer tensor / list [M]; an entry < 0 gives a padding row, an entry at or beyond the number of sequences the
+        table holds a padding row and error bit 512.  One launch on the current stream."""
+        what = "EpisodeSequences.picks"
+        env = self._env
+        if env is None:
+            raise ValueError("%s: these sequences belong to no handle" % what)
+        if sel is not None:
+            if m is not None:
+                raise ValueError("%s: give sel or m, not both" % what)
+            sel = _instance_index(what, "sel", sel, env.device)
+            M = sel.numel()
+        else:
+            M = len(self) if m is None else m
+            if isinstance(M, bool) or not isinstance(M, (int, np.integer)) or M < 0:
+                raise ValueError("%s: m must be an integer >= 0, got %r" % (what, m))
+            M = int(M)
+        if M * self.length > MAX_PICK:
+            raise ValueError("%s: %d rows of %d picks do not fit one call" % (what, M, self.length))
+        pick = torch.empty((M, self.length), dtype=torch.int32, device=env.device)
+        mask = torch.empty((M, self.length), dtype=torch.bool, device=env.device)
+        if M:
+            with torch.cuda.device(env.device):
+                _native.check(_native.LIB.mg_sequence_picks(env._h, self.table.data_ptr() if self.capacity else None, self.count.data_ptr(), self.capacity,
+                                                            None if sel is None else sel.data_ptr(), M, self.length, pick.data_ptr(), mask.data_ptr(),
+                                                            env._stream()), "mg_sequence_picks")
+        return pick, mask
+
+    def gather(self, x, sel=None):
+        """x [K, N, ...] (actions, labels, reward, done) or [K + 1, N, ...] (per-frame data) -> [M, L, ...], zero at the pads: x flattened over its
+        first two dimensions, indexed with picks(sel)."""
+        if not (isinstance(x, torch.Tensor) and x.dim() >= 2 and int(x.shape[0]) in (self.steps, self.steps + 1) and int(x.shape[1]) == self.num_envs):
+            raise ValueError("EpisodeSequences.gather: x must be a tensor [%d or %d, %d, ...]" % (self.steps, self.steps + 1, self.num_envs))
+        pick, mask = self.picks(sel)
+        rows = x.reshape((-1,) + tuple(x.shape[2:]))[pick.clamp(min=0).long()]
+        return torch.where(mask.reshape(mask.shape + (1,) * (x.dim() - 2)), rows, torch.zeros_like(rows))
+
+
 class VecMemoryGym:
     metadata ={"render_modes": ["rgb_array", "debug_rgb_array"], "render_fps": 25}
 
@@ -1042,6 +1146,81 @@ class VecMemoryGym:
                                                      self.OBS_FORMATS[fmt][0], out.data_ptr(), self._stream()), "mg_draw_frames")
         return out
 
+    # ------------------------------------------------------------------ episode sequences
+    def split_episodes(self, done, length, steps=None, starts=None, capacity=None):
+        """Cut a rollout into episode sequences on the device (include/memgym.h: mg_split_episodes) -> EpisodeSequences.  done: a bool or uint8 tensor
+        [K, N], e.g. trace.done; every episode is cut at its done and chopped into sequences of at most `length` steps, ordered by (instance, t0).
+        steps: an integer tensor [N], the steps instance i took (play()'s steps_played; clamped to 0 .. K), None: K for all.  starts: a bool / uint8
+        tensor [N], whether the rollout's first step starts an episode of instance i (it only sets the flag of the first sequence), None: all do.
+        capacity: the rows of the table.  None allocates N * ceil(K / length) + int(done.sum()), which always suffices -- and READS done.sum() ON THE
+        HOST: the one place that synchronises.  An explicit capacity synchronises nothing; the count may then exceed it (len() raises, the table holds
+        the first `capacity` sequences).  Three small launches on the current stream; the handle's first call allocates an int32 per instance and
+        cannot be captured into a graph, every later one can."""
+        self._require_started("split_episodes")
+        d8, K, L, steps, starts, capacity = check_split_episodes(done, length, self.num_envs, steps, starts, capacity, self.device)
+        if capacity is None:
+            capacity = self.num_envs * ((K + L - 1) // L) + int(d8.sum())
+        table = torch.empty((capacity, 4), dtype=torch.int32, device=self.device)
+        count = torch.empty((1,), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            _native.check(_native.LIB.mg_split_episodes(self._h, d8.data_ptr(), K, None if steps is None else steps.data_ptr(),
+                                                        None if starts is None else starts.data_ptr(), L, table.data_ptr() if capacity else None,
+                                                        capacity, count.data_ptr(), self._stream()), "mg_split_episodes")
+        return EpisodeSequences(table, count, L, K, self.num_envs, self)
+
+    def draw_frames_padded(self, records, pick, out=None, obs_format=None):
+        """draw_frames with padding rows (include/memgym.h: mg_draw_frames_padded): a pick below 0 writes its row as zeros, every byte, and is no
+        error.  Everything else -- the arguments, the checks, a pick at or beyond the records (row untouched, error bit 512), the single raster
+        launch -- is draw_frames; pick=None equals it."""
+        self._require_started("draw_frames_padded")
+        fmt = self.obs_format if obs_format is None else obs_format
+        rows, pick, count, (dt, shape) = check_frame_draw(records, self.frame_layout(), self.frame_record_bytes, pick, out, fmt, self.device)
+        if out is None:
+            out = torch.empty((count,) + shape, dtype=dt, device=self.device)
+        if count == 0:  # nothing to draw (an empty tensor has no address to hand to the library)
+            return out
+        if rows.device != self.device or out.device != self.device or rows.data_ptr() % 16 or out.data_ptr() % 16:
+            raise ValueError("draw_frames_padded: records and out must be 16-byte aligned tensors on %s" % (self.device,))
+        with torch.cuda.device(self.device):
+            _native.check(_native.LIB.mg_draw_frames_padded(self._h, rows.data_ptr(), rows.shape[0], None if pick is None else pick.data_ptr(), count,
+                                                            self.OBS_FORMATS[fmt][0], out.data_ptr(), self._stream()), "mg_draw_frames_padded")
+        return out
+
+    def draw_sequences(self, frames, seqs, sel=None, out=None, obs_format=None):
+        """Frames of a minibatch of sequences -> (obs [M, L] + shape of the format, mask bool [M, L]): row (j, l) is the observation step t0 + l of
+        sequence sel[j] was played in (sel=None: all sequences, M = len(seqs)), zeros where the sequence is shorter than L and for entries of sel below
+        0.  frames: the RolloutTrace the sequences were cut from, or a FrameRecords / uint8 tensor over its [K + 1, N] frame store; its layout is
+        checked as draw_frames checks it, and a trace whose K or N is not the sequences' is refused.  out: a contiguous tensor [M, L] + shape to draw
+        into.  Two launches on the current stream: the picks, and the PAD form of the gather raster."""
+        what = "draw_sequences"
+        self._require_started(what)
+        if not isinstance(seqs, EpisodeSequences):
+            raise ValueError("%s: seqs must be the EpisodeSequences split_episodes returned" % what)
+        if isinstance(frames, RolloutTrace):
+            if not (isinstance(frames.frames, torch.Tensor) and frames.frames.dim() == 3):
+                raise ValueError("%s: the trace keeps no frames" % what)
+            if (frames.steps, frames.num_envs) != (seqs.steps, seqs.num_envs):
+                raise ValueError("%s: the trace holds %d steps of %d instances, the sequences were cut from %d steps of %d"
+                                 % (what, frames.steps, frames.num_envs, seqs.steps, seqs.num_envs))
+            frames = FrameRecords(frames.frames, frames.frame_layout)
+        fmt = self.obs_format if obs_format is None else obs_format
+        if fmt not in self.OBS_FORMATS:
+            raise ValueError("%s: obs_format must be one of %s" % (what, sorted(self.OBS_FORMATS)))
+        _, dt, shape = self.OBS_FORMATS[fmt]
+        n_rec = (frames.records if isinstance(frames, FrameRecords) else frames)
+        if isinstance(n_rec, torch.Tensor) and n_rec.dim() >= 2 and n_rec.numel() // max(1, int(n_rec.shape[-1])) < (seqs.steps + 1) * seqs.num_envs:
+            raise ValueError("%s: frames holds fewer than (%d + 1) * %d records" % (what, seqs.steps, seqs.num_envs))
+        pick, mask = seqs.picks(sel)
+        M, L = int(pick.shape[0]), seqs.length
+        if out is not None:
+            if not (isinstance(out, torch.Tensor) and out.dtype == dt and tuple(out.shape) == (M, L) + shape and out.is_contiguous()):
+                raise ValueError("%s: out must be a contiguous %s tensor of shape %s" % (what, dt, (M, L) + shape))
+            flat = out.view((M * L,) + shape)
+        else:
+            flat = None
+        flat = self.draw_frames_padded(frames, pick.view(-1), out=flat, obs_format=fmt)
+        return flat.view((M, L) + shape), mask
+
     # ------------------------------------------------------------------ debug-view records
     DEBUG_SIZES = {84: (84, 84, 3), 336: (336, 336, 3)}  # draw_debug_frames: the debug surface [x][y][c], or the reference's debug_rgb_array [y][x][c]
 
@@ -1333,8 +1512,8 @@ class VecMemoryGym:
                   32: "Endless Mortar Mayhem command list reached its 512-entry capacity (the episode was ended)",
                   64: "a deferred-reset queue overflowed (a previous fused launch did not drain it)",
                   256: "use_exit=False for an instance that never had an exit (the reference raises AttributeError at this reset)",
-                  512: "save_instances / load_instances / save_frames / draw_frames / save_debug_frames / draw_debug_frames: an instance or record index out of range "
-                       "(the entry was skipped)"}
+                  512: "save_instances / load_instances / save_frames / draw_frames / draw_frames_padded / draw_sequences / save_debug_frames / "
+                       "draw_debug_frames / EpisodeSequences.picks: an instance, record or sequence index out of range (the entry was skipped)"}
 
     def check_errors(self):
         """Raise if a kernel flagged a capacity/failure condition since the last call (synchronises the device).

@@ -183,6 +183,18 @@ class GymnasiumVectorEnv(_Base):
         """VecMemoryGym.new_rollout -> RolloutTrace (device tensors, whatever as_numpy says: a trace is drawn from on the device)."""
         return self.env.new_rollout(steps, labels=labels)
 
+    def split_episodes(self, done, length, steps=None, starts=None, capacity=None):
+        """VecMemoryGym.split_episodes -> EpisodeSequences (device tensors, whatever as_numpy says: sequences are drawn from on the device)."""
+        return self.env.split_episodes(done, length, steps=steps, starts=starts, capacity=capacity)
+
+    def draw_frames_padded(self, records, pick, out=None, obs_format=None):
+        """VecMemoryGym.draw_frames_padded: draw_frames whose picks below 0 give rows of zeros (a device tensor, whatever as_numpy says)."""
+        return self.env.draw_frames_padded(records, pick, out=out, obs_format=obs_format)
+
+    def draw_sequences(self, frames, seqs, sel=None, out=None, obs_format=None):
+        """VecMemoryGym.draw_sequences -> (obs [M, L, ...], mask [M, L]) of a minibatch of sequences (device tensors, whatever as_numpy says)."""
+        return self.env.draw_sequences(frames, seqs, sel=sel, out=out, obs_format=obs_format)
+
     def advance(self, steps, eps=0.0, seed=0, step=None, render=True, stats=True):
         """`steps` steps under the scripted teacher without a frame (VecMemoryGym.advance) -> (obs or None, stats); numpy with as_numpy.
         Episodes that end inside the call are NOT reported as `final_observation` / `final_info`: they are counted and summed in `stats`."""

@@ -549,6 +549,60 @@ int mg_save_frames(mg_env* env, const int32_t* idx_dev, int32_t count, void* rec
 int mg_draw_frames(mg_env* env, const void* rec_dev, int64_t n_records, const int32_t* pick_dev, int64_t count, int format, void* obs_dev,
                    void* stream);
 
+/* EPISODE SEQUENCES: cut a rollout into episodes at `done`, chop the episodes into sequences of at most `length` steps, and draw minibatches of sequences
+ * [m][length] with zero rows at the pads -- what every trainer of a recurrent or memory-based agent does with a rollout, here on the device, enqueue-only,
+ * in a deterministic order.
+ *   mg_split_episodes       done rows [steps][num_envs] -> a table of mg_sequence {instance, t0, len, flags}, ordered by (instance, t0)
+ *   mg_sequence_picks       sequences (all, or a selection) -> pick[m][length] record indices, -1 at the pads, and an optional mask
+ *   mg_draw_frames_padded   mg_draw_frames, but a pick below 0 writes its row as ZEROS and is no error
+ * mg_split_episodes, DEFINITION.  done_dev is [steps][num_envs], one byte each, step-major: what a trace's done_dev holds.  For instance i let
+ * n_i = steps_of_dev ? clamp(steps_of_dev[i], 0, steps) : steps; rows t >= n_i of that instance are ignored (steps_of_dev = mg_play's steps_played_dev:
+ * a trace made with MG_PLAY_EPISODE or with a mask gives no sequences for steps the instance never took).  Walk t = 0 .. n_i - 1 with t0 = 0 and
+ * first = start_dev ? start_dev[i] != 0 : 1:
+ *   a sequence closes at t when done[t][i] is set, or t - t0 + 1 == length, or t == n_i - 1;
+ *   the closing sequence is {i, t0, t - t0 + 1, (first ? MG_SEQ_FIRST : 0) | (done[t][i] ? MG_SEQ_LAST : 0)};
+ *   after a sequence has closed, t0 = t + 1 and first = done[t][i].
+ * The table holds all instances' sequences ordered by (instance, t0) ascending; the order is part of the definition, and no atomic decides where an entry
+ * lands.  *count_dev receives the TRUE number of sequences S, also when S > capacity.  Entries 0 .. min(S, capacity) - 1 are written, nothing is written
+ * at or beyond capacity, entries S .. capacity - 1 are left untouched.  capacity == 0 with seq_dev == NULL is legal and only counts.  A table is always
+ * large enough at num_envs * ceil(steps / length) plus the number of set done bytes.
+ * LAUNCHES: three small ones -- a lane per instance counts (lanes of a wave read 64 neighbouring bytes of a done row), one workgroup scans the
+ * workgroups' sums and writes *count_dev, a lane per instance walks its column again and writes its entries, each as one 16-byte store.  The scratch (an
+ * int32 per instance and one per 256 instances) is allocated AT THE HANDLE'S FIRST CALL, which therefore cannot be captured; every later call allocates
+ * nothing and can be captured into a HIP graph: done_dev, steps_of_dev and start_dev are read at replay.  Nothing synchronises.
+ * Errors (-1): before the first mg_reset / mg_set_state; a NULL done_dev or count_dev; steps < 1, length < 1 or capacity < 0; a NULL or not 16-byte
+ * aligned seq_dev with capacity > 0; (steps + 1) * num_envs > INT32_MAX (a pick is an int32).
+ * mg_sequence_picks: row j of pick_dev ([m][length] int32) is taken from sequence s = sel_dev ? sel_dev[j] : j.  With V = min(*count_dev, capacity), the
+ * number of entries the table holds:
+ *   0 <= s < V                  pick[j][l] = (t0 + l) * num_envs + instance for l < len, -1 for l >= len;
+ *   s < 0                       a whole row of -1, no error: a minibatch padded to a fixed m;
+ *   s >= V, sel_dev == NULL     a whole row of -1, no error: "all sequences" with m == capacity, capturable;
+ *   s >= V, sel_dev set         a whole row of -1 and error bit 512 (mg_poll_errors).
+ * mask_dev is optional, uint8 [m][length]: 1 where the pick is 0 or more.  The pick indexes the flattened [steps + 1][num_envs] frame store of a trace
+ * whose row 0 is the frame before the call's first step (the Python mirror's RolloutTrace.frames) -- row t there is the observation action t was played
+ * in -- and the same number indexes the flattened [steps][num_envs] action, label, reward and done rows.  ONE launch, a lane per element; count_dev is
+ * read on the device, nothing synchronises, nothing is allocated; capturable.  num_envs is the handle's.
+ * Errors (-1): a NULL count_dev or pick_dev; capacity < 0; a NULL or misaligned seq_dev with capacity > 0; m < 0; length < 1; m * length > INT32_MAX.
+ * mg_draw_frames_padded: mg_draw_frames with ONE difference -- a pick below 0 writes its row as zeros, every byte, in every format, and raises no error.
+ * Everything else is mg_draw_frames word for word: a pick at or above n_records leaves its row untouched and raises bit 512; a record the composer skips
+ * leaves its row untouched; the refusals, the 64-bit row offsets, the single launch (the PAD form of the family's gather raster: the workgroup that meets
+ * a padding row stores 21,168 / 42,336 / 84,672 bytes of zeros as 16-byte vectors straight from registers, without a compose) and capturability are the
+ * same.  pick_dev == NULL is legal and then equals mg_draw_frames.
+ * mg_debug_counter "sequence_splits" counts the mg_split_episodes calls, "padded_draws" the mg_draw_frames_padded calls with count > 0, on the host.
+ * MG_STATE_VERSION is unchanged: no state is added.
+ * OUT OF SCOPE: sliding memory windows for transformer agents; sequences that continue across two traces (the start of a trace starts a sequence,
+ * start_dev only sets the MG_SEQ_FIRST flag); terminal frames inside a traced call (still the trace's own open item); the MortarMayhemB ids' vector
+ * observation per step. */
+typedef struct mg_sequence { int32_t instance, t0, len, flags; } mg_sequence;   /* 16 bytes, stored as one vector */
+#define MG_SEQ_FIRST 1   /* the sequence starts an episode */
+#define MG_SEQ_LAST  2   /* the sequence ends with its episode's done */
+int mg_split_episodes(mg_env* env, const uint8_t* done_dev, int32_t steps, const int32_t* steps_of_dev, const uint8_t* start_dev,
+                      int32_t length, mg_sequence* seq_dev, int32_t capacity, int32_t* count_dev, void* stream);
+int mg_sequence_picks(mg_env* env, const mg_sequence* seq_dev, const int32_t* count_dev, int32_t capacity, const int32_t* sel_dev,
+                      int32_t m, int32_t length, int32_t* pick_dev, uint8_t* mask_dev, void* stream);
+int mg_draw_frames_padded(mg_env* env, const void* rec_dev, int64_t n_records, const int32_t* pick_dev, int64_t count, int format,
+                          void* obs_dev, void* stream);
+
 /* DEBUG-VIEW RECORDS: keep the ground-truth view of a FEW instances and draw it later.  mg_render_debug draws every instance at once, from the current state,
  * synchronously: at 65,536 instances 22 GB of views and 1.4 GB of scratch to look at one of them.  But a debug view, like a frame, is a pure function of a
  * descriptor of the family's frame-descriptor type (16 / 64 / 128 B) and the handle's atlas -- the descriptor mg_render_debug fills for every instance before it
