@@ -214,6 +214,12 @@ struct KernelProfile {
 
 struct ExpertArgs;  // mg_expert.hpp
 
+// The refusal of a handle whose geometry options changed since its last reset, worded once.  who: an entry point's "mg_x: ", or empty (a family's own
+// guard); before: what the reset must come before -- "first", "before the next step", "before the next render"
+inline std::runtime_error stale_geometry(const std::string& who, const char* before) {
+    return std::runtime_error(who + "options that change geometry need a reset " + before);
+}
+
 // mg_advance (include/memgym.h) as it reaches a family that can run the whole loop inside its own launches: the policy's arguments, the handle's
 // scratch rows (what the loop's mg_expert_actions / mg_step calls would be given: info holds reward64, the episode record and the named aux slots,
 // nothing else) and the caller's sums.
@@ -257,7 +263,7 @@ struct TraceRows {
     uint8_t* done;     // [steps][num_envs]
 };
 
-// What the C ABI (mg_api.hip) sees of an environment family, and the host-side plumbing the three families share: the error
+// What the C ABI (mg_api.hip and its mg_api_*.hpp) sees of an environment family, and the host-side plumbing the three families share: the error
 // word, the RNG streams, the "seeded" / "geometry changed" guards and the debug view's scratch frames.
 class Family {
    public:
@@ -268,7 +274,7 @@ class Family {
     virtual ~Family() {}
     virtual int action_dim() const = 0;
     virtual int gt_dim() const = 0;
-    // mg_single_step (mg_api.hip) asks the NEXT step() -- that call only, however it ends -- to store `ticket` to *flag_dev (a word the
+    // mg_single_step (mg_api_single.hpp) asks the NEXT step() -- that call only, however it ends -- to store `ticket` to *flag_dev (a word the
     // host polls) from its own last kernel once its results are out.  Whether that happened is decided where step() chooses its launch:
     // done_flag_stored() is true iff the step() that just returned launched such a kernel (reading it clears it); otherwise the caller
     // puts a stream memory operation behind the step's launches.  A family without such a kernel ignores the request.
@@ -300,10 +306,10 @@ class Family {
     virtual void step(const int32_t* actions, const uint8_t* active, void* obs, float* reward, uint8_t* done, float* gt,
                       const mg_info_dev* info, int autoreset, hipStream_t s, void* final_frames = nullptr) = 0;
     // mg_advance: true = the family has run the loop of include/memgym.h's definition inside launches of its own (the mortar family:
-    // mortar_advance_kernel); false = it has no such form (or the lab build switched it off) and nothing happened: mg_api.hip runs the loop.
+    // mortar_advance_kernel); false = it has no such form (or the lab build switched it off) and nothing happened: mg_api_rollout.hpp runs the loop.
     virtual bool advance(const AdvanceArgs& /*v*/, hipStream_t /*s*/) { return false; }
     // mg_play: true = the family has run the loop of include/memgym.h's definition inside launches of its own (the mortar family:
-    // mortar_play_kernel); false = it has no such form (or the lab build switched it off) and nothing happened: mg_api.hip runs the loop.
+    // mortar_play_kernel); false = it has no such form (or the lab build switched it off) and nothing happened: mg_api_rollout.hpp runs the loop.
     virtual bool play(const PlayArgs& /*v*/, hipStream_t /*s*/) { return false; }
     // mg_advance_traced / mg_play_traced with a trace: the same contract, the traced in-launch forms (the mortar family: mortar_advance_traced_kernel /
     // mortar_play_traced_kernel, mg_mortar_trace.hpp).  `frames` of play_traced: TraceRows::frames, or NULL.
@@ -379,13 +385,17 @@ class Family {
     virtual bool debug_counter(const std::string& /*name*/, int64_t* /*out*/) { return false; }
 
    protected:
+    // head of everything that reads the geometry's constants and atlases: a geometry option set since the last reset has not reached them yet
+    void require_geometry(const char* before = "before the next step") const {
+        if (dirty_) throw stale_geometry("", before);
+    }
     // head of every reset(): without seeds the instances keep their RNG streams, so they must have some
     void require_seeded(const int64_t* seeds) const {
         if (!seeds && !seeded_) throw std::runtime_error("reset(seed=None) before any seeded reset");
     }
     // head of every step(): the caller's info buffers, all null where it passed none
     mg_info_dev begin_step(const mg_info_dev* info) const {
-        if (dirty_) throw std::runtime_error("options that change geometry need a reset before the next step");
+        require_geometry();
         mg_info_dev ib;
         memset(&ib, 0, sizeof(ib));
         if (info) ib = *info;
@@ -412,7 +422,7 @@ class Family {
     // raster_debug(): `fill(dbg)` writes the debug view's descriptors of all instances into scratch, `raster(dbg)` draws them
     template <typename Desc, typename Fill, typename Raster>
     void debug_frames(hipStream_t s, Fill fill, Raster raster) {
-        if (dirty_) throw std::runtime_error("options that change geometry need a reset before the next render");
+        require_geometry("before the next render");
         DevArray<Desc> dbg;
         dbg.alloc(n_, false);
         fill(dbg.p);

@@ -1,6 +1,6 @@
 // mg_frame_records.hpp -- mg_save_frames / mg_draw_frames (include/memgym.h): a frame kept as the descriptor row its step left, drawn later by the
 // gather forms of the two raster skeletons (mg_raster_gather_v1.hpp, mg_raster_gather.hpp).  Here: what the two calls refuse, the layout value, the
-// bytes of one observation row: host code that compiles without a GPU compiler (tests/host/frame_records_check.cpp).  The save's row gather is in mg_api.hip.
+// bytes of one observation row: host code that compiles without a GPU compiler (tests/host/frame_records_check.cpp).  The save's row gather is in mg_api_records.hpp.
 #pragma once
 #include <cstddef>
 #include <cstdint>

@@ -112,7 +112,7 @@ __global__ __launch_bounds__(256) void mortar_debug_desc_kernel(MortarParams P0,
     out[i] = d;
 }
 
-// The same descriptor for ONE instance, for the picked form below (a body of its own: mortar_debug_desc_kernel stays the code it was).
+// The same descriptor for ONE instance, for the picked form below (a body of its own: mortar_debug_desc_kernel stays the code it was; DESIGN.md 3.4a).
 __device__ __forceinline__ MortarDesc mortar_debug_desc_one(const MortarParams& P, const MortarIO& io, int i) {
     const MortarState s = io.state[i];
     const uint8_t* cmds = io.cmds + (size_t)i * P.cmd_cap;
@@ -309,7 +309,7 @@ class MortarFamily : public Family {
         flag_stored_ = false;
         const mg_info_dev ib = begin_step(info);
         sets_.upload(s);
-        const MortarStepArgs sa{P_, n_, io(), actions, reward, done, gt_dim() ? gt : nullptr, ib, autoreset, handover_.p, nullptr};
+        const MortarStepArgs sa = step_args(actions, reward, done, gt, ib, autoreset);
         // one launch: mortar_step_raster_kernel (handles with ONE option set: the per-set step code reads its parameters from memory)
         // (a headless step, obs == NULL: mortar_step_kernel alone; a masked step, active != NULL: its MASKED form, then the active instances' frames)
         if (obs && !active && one_launch(s)) {
@@ -364,7 +364,7 @@ class MortarFamily : public Family {
     }
 
     // mg_step_next in three launches (mg_mortar_next.hpp): the NEXT form of the two-launch step -- mortar_step_next_kernel, the dense raster, the settle launch.
-    // The one-launch step (mortar_step_raster_kernel) is left alone.  Lab build, MEMGYM_NEXT_FUSE=0: the composed form of mg_api.hip, for A/B
+    // The one-launch step (mortar_step_raster_kernel) is left alone.  Lab build, MEMGYM_NEXT_FUSE=0: the composed form of mg_api.hip (mg_step_next), for A/B
     // measurements (tools/next_step_bench.py flips it between calls of one process: read at every call)
     bool step_next(const int32_t* actions, const uint8_t* restart, uint8_t* restart_copy, void* obs, float* reward, uint8_t* done, float* gt,
                    const mg_info_dev* info, hipStream_t s) override {
@@ -372,7 +372,7 @@ class MortarFamily : public Family {
         const mg_info_dev ib = begin_step(info);
         check_schedules();  // (what the masked reset of the definition refuses, before anything is stepped)
         sets_.upload(s);
-        const MortarStepArgs sa{P_, n_, io(), actions, reward, done, gt_dim() ? gt : nullptr, ib, 0, handover_.p, nullptr};
+        const MortarStepArgs sa = step_args(actions, reward, done, gt, ib, 0);
         const int sb = step_block(256);
         prof.begin(0, s);
         with_bool(sets_.per_set(), [&](auto PS) {
@@ -388,82 +388,60 @@ class MortarFamily : public Family {
         return true;
     }
 
-    // mg_advance inside ONE launch per ADVANCE_MAX_STEPS steps (mg_mortar_advance.hpp); lab build, MEMGYM_MORTAR_ADVANCE_FUSE=0: the loop form
-    // of mg_api.hip -- expert launch, headless step, accumulate launch per step -- for A/B measurements (tools/headless_bench.py flips it
-    // between calls of one process: read at every call)
+    // mg_advance, mg_play and their traced forms inside ONE launch per ADVANCE_MAX_STEPS steps (mg_mortar_advance.hpp, mg_mortar_play.hpp, mg_mortar_trace.hpp): the
+    // chunks of the call (rollout_chunks), the arguments of a chunk (advance_chunk / play_step_args / play_chunk) and its rows of the caller's [steps][...] arrays
+    // (row_at: 64-bit offsets) are below, with the private members.  Lab build, MEMGYM_MORTAR_ADVANCE_FUSE=0 / MEMGYM_MORTAR_PLAY_FUSE=0: the loop forms of
+    // mg_api_rollout.hpp -- per step an expert launch (advance), the headless (masked) step and an accumulate launch -- for A/B measurements; the traced forms
+    // follow the switch of their untraced sibling (tools/headless_bench.py, play_bench.py and rollout_trace_bench.py flip them between calls of one process:
+    // read at every call)
     bool advance(const AdvanceArgs& v, hipStream_t s) override {
         if (!lab_flag("MEMGYM_MORTAR_ADVANCE_FUSE", true)) return false;
-        if (dirty_) throw std::runtime_error("options that change geometry need a reset before the next step");
+        require_geometry();
         sets_.upload(s);
-        const MortarStepArgs sa{P_, n_, io(), v.actions, v.reward, v.done, gt_dim() ? v.gt : nullptr, v.info, 1, handover_.p, nullptr};
-        for (int t0 = 0; t0 < v.steps; t0 += ADVANCE_MAX_STEPS) {
-            const int k = v.steps - t0 < ADVANCE_MAX_STEPS ? v.steps - t0 : ADVANCE_MAX_STEPS;
-            const MortarAdvanceArgs aa{k, t0 == 0 ? 1 : 0, v.eps, v.seed, v.step0 + (uint64_t)t0, v.actions, v.out};
+        const MortarStepArgs sa = step_args(v.actions, v.reward, v.done, v.gt, v.info, 1);
+        rollout_chunks(v.steps, [&](int t0, int k) {
             with_bool(sets_.per_set(), [&](auto PS) {
-                launch_checked(mortar_advance_kernel<decltype(PS)::value>, dim3((n_ + 255) / 256), dim3(256), 0, s, sa, aa);
+                launch_checked(mortar_advance_kernel<decltype(PS)::value>, dim3((n_ + 255) / 256), dim3(256), 0, s, sa, advance_chunk(v, t0, k));
             });
-        }
+        });
         return true;
     }
-
-    // mg_play inside ONE launch per ADVANCE_MAX_STEPS steps (mg_mortar_play.hpp); lab build, MEMGYM_MORTAR_PLAY_FUSE=0: the loop form of mg_api.hip -- headless
-    // (masked) step and accumulate launch per step -- for A/B measurements (tools/play_bench.py flips it between calls of one process: read at every call)
     bool play(const PlayArgs& v, hipStream_t s) override {
         if (!lab_flag("MEMGYM_MORTAR_PLAY_FUSE", true)) return false;
-        if (dirty_) throw std::runtime_error("options that change geometry need a reset before the next step");
+        require_geometry();
         sets_.upload(s);
-        const int row = n_ * action_dim();
-        for (int t0 = 0; t0 < v.steps; t0 += ADVANCE_MAX_STEPS) {
-            const int k = v.steps - t0 < ADVANCE_MAX_STEPS ? v.steps - t0 : ADVANCE_MAX_STEPS;
-            const MortarStepArgs sa{P_, n_, io(), v.tape + (size_t)t0 * (size_t)row, v.reward, v.done, gt_dim() ? v.gt : nullptr, v.info, v.episode ? 0 : 1,
-                                    handover_.p, nullptr};
-            const MortarPlayArgs pa{k, t0 == 0 ? 1 : 0, t0 + k == v.steps ? 1 : 0, v.episode, row, v.active, v.alive,
-                                    v.reward_trace ? v.reward_trace + (size_t)t0 * (size_t)n_ : nullptr,
-                                    v.done_trace ? v.done_trace + (size_t)t0 * (size_t)n_ : nullptr, v.played, v.out};
+        rollout_chunks(v.steps, [&](int t0, int k) {
             with_bool(sets_.per_set(), [&](auto PS) {
-                launch_checked(mortar_play_kernel<decltype(PS)::value>, dim3((n_ + 255) / 256), dim3(256), 0, s, sa, pa);
+                launch_checked(mortar_play_kernel<decltype(PS)::value>, dim3((n_ + 255) / 256), dim3(256), 0, s, play_step_args(v, t0), play_chunk(v, t0, k));
             });
-        }
+        });
         return true;
     }
-
-    // mg_advance_traced / mg_play_traced inside ONE launch per ADVANCE_MAX_STEPS steps (mg_mortar_trace.hpp): the host offsets every trace row pointer by the
-    // steps the launches before took, in 64 bits.  The lab switches of the untraced forms govern these too (tools/rollout_trace_bench.py flips them).
     bool advance_traced(const AdvanceArgs& v, const TraceRows& tr, hipStream_t s) override {
         if (!lab_flag("MEMGYM_MORTAR_ADVANCE_FUSE", true)) return false;
-        if (dirty_) throw std::runtime_error("options that change geometry need a reset before the next step");
+        require_geometry();
         sets_.upload(s);
-        const MortarStepArgs sa{P_, n_, io(), v.actions, v.reward, v.done, gt_dim() ? v.gt : nullptr, v.info, 1, handover_.p, nullptr};
+        const MortarStepArgs sa = step_args(v.actions, v.reward, v.done, v.gt, v.info, 1);
         const size_t row = (size_t)n_ * (size_t)action_dim();
-        for (int t0 = 0; t0 < v.steps; t0 += ADVANCE_MAX_STEPS) {
-            const int k = v.steps - t0 < ADVANCE_MAX_STEPS ? v.steps - t0 : ADVANCE_MAX_STEPS;
-            const MortarAdvanceArgs aa{k, t0 == 0 ? 1 : 0, v.eps, v.seed, v.step0 + (uint64_t)t0, v.actions, v.out};
-            const size_t at = (size_t)t0 * (size_t)n_;
-            const MortarTraceRows rows{tr.frames ? (MortarDesc*)tr.frames + at : nullptr, tr.actions ? tr.actions + (size_t)t0 * row : nullptr,
-                                       tr.labels ? tr.labels + (size_t)t0 * row : nullptr, tr.reward ? tr.reward + at : nullptr, tr.done ? tr.done + at : nullptr};
+        rollout_chunks(v.steps, [&](int t0, int k) {
+            const MortarTraceRows rows{row_at((MortarDesc*)tr.frames, t0, n_), row_at(tr.actions, t0, row), row_at(tr.labels, t0, row), row_at(tr.reward, t0, n_),
+                                       row_at(tr.done, t0, n_)};
             with_bool(sets_.per_set(), [&](auto PS) {
-                launch_checked(mortar_advance_traced_kernel<decltype(PS)::value>, dim3((n_ + 255) / 256), dim3(256), 0, s, sa, aa, rows);
+                launch_checked(mortar_advance_traced_kernel<decltype(PS)::value>, dim3((n_ + 255) / 256), dim3(256), 0, s, sa, advance_chunk(v, t0, k), rows);
             });
-        }
+        });
         return true;
     }
     bool play_traced(const PlayArgs& v, void* frames, hipStream_t s) override {
         if (!lab_flag("MEMGYM_MORTAR_PLAY_FUSE", true)) return false;
-        if (dirty_) throw std::runtime_error("options that change geometry need a reset before the next step");
+        require_geometry();
         sets_.upload(s);
-        const int row = n_ * action_dim();
-        for (int t0 = 0; t0 < v.steps; t0 += ADVANCE_MAX_STEPS) {
-            const int k = v.steps - t0 < ADVANCE_MAX_STEPS ? v.steps - t0 : ADVANCE_MAX_STEPS;
-            const size_t at = (size_t)t0 * (size_t)n_;
-            const MortarStepArgs sa{P_, n_, io(), v.tape + (size_t)t0 * (size_t)row, v.reward, v.done, gt_dim() ? v.gt : nullptr, v.info, v.episode ? 0 : 1,
-                                    handover_.p, nullptr};
-            const MortarPlayArgs pa{k, t0 == 0 ? 1 : 0, t0 + k == v.steps ? 1 : 0, v.episode, row, v.active, v.alive,
-                                    v.reward_trace ? v.reward_trace + at : nullptr, v.done_trace ? v.done_trace + at : nullptr, v.played, v.out};
-            MortarDesc* const fr = frames ? (MortarDesc*)frames + at : nullptr;
+        rollout_chunks(v.steps, [&](int t0, int k) {
             with_bool(sets_.per_set(), [&](auto PS) {
-                launch_checked(mortar_play_traced_kernel<decltype(PS)::value>, dim3((n_ + 255) / 256), dim3(256), 0, s, sa, pa, fr);
+                launch_checked(mortar_play_traced_kernel<decltype(PS)::value>, dim3((n_ + 255) / 256), dim3(256), 0, s, play_step_args(v, t0), play_chunk(v, t0, k),
+                               row_at((MortarDesc*)frames, t0, n_));
             });
-        }
+        });
         return true;
     }
 
@@ -483,7 +461,7 @@ class MortarFamily : public Family {
     }
 
     void expert_actions(const ExpertArgs& x, hipStream_t s) override {
-        if (dirty_) throw std::runtime_error("options that change geometry need a reset before the next step");
+        require_geometry();
         sets_.upload(s);
         launch_checked(mortar_expert_kernel, expert_grid(n_), dim3(EXPERT_BLOCK), 0, s, P_, n_, io(), x);
     }
@@ -554,6 +532,31 @@ class MortarFamily : public Family {
                 throw OptionError{-3, "command_count x (command_show_duration + command_show_delay) exceeds the 65,535 entries of this build's display schedule"};
         }
     }
+    // the arguments of every form of the step kernel: the caller's rows (gt: NULL for the ids without a ground truth) on the handle's arrays
+    MortarStepArgs step_args(const int32_t* actions, float* reward, uint8_t* done, float* gt, const mg_info_dev& ib, int autoreset) {
+        return MortarStepArgs{P_, n_, io(), actions, reward, done, gt_dim() ? gt : nullptr, ib, autoreset, handover_.p, nullptr};
+    }
+    // A rollout of `steps` goes out in launches of at most ADVANCE_MAX_STEPS steps: f(t0, k) for the k steps from step t0
+    template <class F>
+    static void rollout_chunks(int steps, F&& f) {
+        for (int t0 = 0; t0 < steps; t0 += ADVANCE_MAX_STEPS) f(t0, steps - t0 < ADVANCE_MAX_STEPS ? steps - t0 : ADVANCE_MAX_STEPS);
+    }
+    // row t0 of a caller's [steps][width] array, the offset in 64 bits; an array the caller left out stays NULL
+    template <class T>
+    static T* row_at(T* base, int t0, size_t width) {
+        return base ? base + (size_t)t0 * width : nullptr;
+    }
+    // the chunk from step t0 as the advance / play kernels take it: `first` (the sums start from zero), play's `last` (no alive bytes stored for a next launch)
+    static MortarAdvanceArgs advance_chunk(const AdvanceArgs& v, int t0, int k) {
+        return MortarAdvanceArgs{k, t0 == 0 ? 1 : 0, v.eps, v.seed, v.step0 + (uint64_t)t0, v.actions, v.out};
+    }
+    MortarStepArgs play_step_args(const PlayArgs& v, int t0) {
+        return step_args(row_at(v.tape, t0, (size_t)n_ * (size_t)action_dim()), v.reward, v.done, v.gt, v.info, v.episode ? 0 : 1);
+    }
+    MortarPlayArgs play_chunk(const PlayArgs& v, int t0, int k) const {
+        return MortarPlayArgs{k, t0 == 0 ? 1 : 0, t0 + k == v.steps ? 1 : 0, v.episode, n_ * action_dim(), v.active, v.alive, row_at(v.reward_trace, t0, n_),
+                              row_at(v.done_trace, t0, n_), v.played, v.out};
+    }
     MortarIO io() {
         MortarIO o;
         o.state = state_.p;
@@ -620,11 +623,11 @@ class MortarFamily : public Family {
     }
     std::pair<const void*, size_t> frame_rows() override { return {desc_.p, sizeof(MortarDesc)}; }
     void draw_records(const void* records, int n_records, const int32_t* pick, int count, int fmt, void* obs, hipStream_t s) override {
-        launch_raster_gather<MortarComposer>((const MortarDesc*)records, atlas_->dev(), obs, fmt, n_records, pick, count, err_.dev, s);
+        launch_raster_gather<MortarComposer, false>((const MortarDesc*)records, atlas_->dev(), obs, fmt, n_records, pick, count, err_.dev, s);
         check_launch();
     }
     void draw_records_padded(const void* records, int n_records, const int32_t* pick, int count, int fmt, void* obs, hipStream_t s) override {
-        launch_raster_gather_pad<MortarComposer>((const MortarDesc*)records, atlas_->dev(), obs, fmt, n_records, pick, count, err_.dev, s);
+        launch_raster_gather<MortarComposer, true>((const MortarDesc*)records, atlas_->dev(), obs, fmt, n_records, pick, count, err_.dev, s);
         check_launch();
     }
     // (the one-launch step keeps terminal observations itself: the conditions under which step() takes that launch; lab

@@ -111,7 +111,7 @@ __global__ __launch_bounds__(256) void mystery_debug_desc_kernel(MysteryParams P
     out[i] = d;
 }
 
-// The same descriptor for ONE instance, for the picked form below (a body of its own: mystery_debug_desc_kernel stays the code it was).
+// The same descriptor for ONE instance, for the picked form below (a body of its own: mystery_debug_desc_kernel stays the code it was; DESIGN.md 3.4a).
 __device__ __forceinline__ MysteryDesc mystery_debug_desc_one(const MysteryParams& P, const MysteryIO& io, int i) {
     const MysteryCore s = io.core[i];
     MysteryDesc d = io.desc[i];
@@ -217,7 +217,7 @@ class MysteryFamily : public Family {
     }
     // (Endless: whatever is owed stays owed -- the node the expert aims at exists when a step has returned, mg_mystery_expert.hpp emp_expert)
     void expert_actions(const ExpertArgs& x, hipStream_t s) override {
-        if (dirty_) throw std::runtime_error("options that change geometry need a reset before the next step");
+        require_geometry();
         sets_.upload(s);
         launch_checked(mystery_expert_kernel, expert_grid(n_), dim3(EXPERT_BLOCK), 0, s, P_, io(), x);
     }
@@ -232,8 +232,7 @@ class MysteryFamily : public Family {
     }
     void raster_debug(void* frames, hipStream_t s) override;
     void raster_only(void* obs, const uint8_t* only, hipStream_t s) override {
-        if (big_sprites_) launch_raster<MysteryBigComposer>(desc_.p, atlas_->dev(), obs, obs_format, n_, s, only);
-        else launch_raster<MysteryComposer>(desc_.p, atlas_->dev(), obs, obs_format, n_, s, only);
+        with_composers([&](auto C) { launch_raster<typename decltype(C)::Obs>(desc_.p, atlas_->dev(), obs, obs_format, n_, s, only); });
         check_launch();
     }
     // (Endless: the descriptor rows are complete once the step's launches have run -- a queued instance's row is rewritten by the wave that serves its entry,
@@ -241,14 +240,12 @@ class MysteryFamily : public Family {
     std::pair<const void*, size_t> frame_rows() override { return {desc_.p, sizeof(MysteryDesc)}; }
     void draw_records(const void* records, int n_records, const int32_t* pick, int count, int fmt, void* obs, hipStream_t s) override {
         const MysteryDesc* rec = (const MysteryDesc*)records;
-        if (big_sprites_) launch_raster_gather<MysteryBigComposer>(rec, atlas_->dev(), obs, fmt, n_records, pick, count, err_.dev, s);
-        else launch_raster_gather<MysteryComposer>(rec, atlas_->dev(), obs, fmt, n_records, pick, count, err_.dev, s);
+        with_composers([&](auto C) { launch_raster_gather<typename decltype(C)::Obs, false>(rec, atlas_->dev(), obs, fmt, n_records, pick, count, err_.dev, s); });
         check_launch();
     }
     void draw_records_padded(const void* records, int n_records, const int32_t* pick, int count, int fmt, void* obs, hipStream_t s) override {
         const MysteryDesc* rec = (const MysteryDesc*)records;
-        if (big_sprites_) launch_raster_gather_pad<MysteryBigComposer>(rec, atlas_->dev(), obs, fmt, n_records, pick, count, err_.dev, s);
-        else launch_raster_gather_pad<MysteryComposer>(rec, atlas_->dev(), obs, fmt, n_records, pick, count, err_.dev, s);
+        with_composers([&](auto C) { launch_raster_gather<typename decltype(C)::Obs, true>(rec, atlas_->dev(), obs, fmt, n_records, pick, count, err_.dev, s); });
         check_launch();
     }
     // (Endless: the debug view reads the segment store -- owed segments are generated first, on the call's stream, as before an instance save)
@@ -261,8 +258,7 @@ class MysteryFamily : public Family {
     }
     void draw_debug_records(const void* records, int n_records, const int32_t* pick, int count, int size, void* rgb, hipStream_t s) override {
         const MysteryDesc* rec = (const MysteryDesc*)records;
-        if (big_sprites_) launch_raster_debug_gather<MysteryDebugBigComposer>(rec, atlas_->dev(), rgb, size, n_records, pick, count, err_.dev, s);
-        else launch_raster_debug_gather<MysteryDebugComposer>(rec, atlas_->dev(), rgb, size, n_records, pick, count, err_.dev, s);
+        with_composers([&](auto C) { launch_raster_debug_gather<typename decltype(C)::Debug>(rec, atlas_->dev(), rgb, size, n_records, pick, count, err_.dev, s); });
         check_launch();
     }
 
@@ -381,12 +377,24 @@ class MysteryFamily : public Family {
     }
     virtual void add_templates(Atlas&) {}  // rebuild(): the id's background templates, if it has any
 
+    // The composers every raster launch of the handle draws with, chosen once: f(C) with decltype(C)::Obs the observation's and ::Debug the debug view's
+    // (agent sprites beyond MysteryComposer's registers: the Big pair).  A launch names its launcher and one of the two, nothing else.
+    template <class O, class D>
+    struct Composers {
+        using Obs = O;
+        using Debug = D;
+    };
+    template <class F>
+    void with_composers(F&& f) {
+        if (big_sprites_) f(Composers<MysteryBigComposer, MysteryDebugBigComposer>{});
+        else f(Composers<MysteryComposer, MysteryDebugComposer>{});
+    }
+
     void raster(void* obs, hipStream_t s) { raster_only(obs, nullptr, s); }
     // tail of reset(): the frames of the instances that were reset
     void draw_reset_frames(const uint8_t* mask, void* obs, hipStream_t s) {
         reset_frames(mask, [&](const uint8_t* m) {
-            if (big_sprites_) launch_raster_sparse<MysteryBigComposer>(desc_.p, atlas_->dev(), obs, obs_format, n_, s, m);
-            else launch_raster_sparse<MysteryComposer>(desc_.p, atlas_->dev(), obs, obs_format, n_, s, m);
+            with_composers([&](auto C) { launch_raster_sparse<typename decltype(C)::Obs>(desc_.p, atlas_->dev(), obs, obs_format, n_, s, m); });
         }, [&] { raster(obs, s); });
     }
     // tail of a step() in the plain arrangement: the logic is out, the frames are a launch of their own (a headless step has none; a masked step, active != NULL:
@@ -426,8 +434,7 @@ void MysteryFamily::raster_debug(void* frames, hipStream_t s) {
             });
         },
         [&](MysteryDesc* dbg) {
-            if (big_sprites_) launch_raster<MysteryDebugBigComposer>(dbg, atlas_->dev(), frames, MG_OBS_U8_XYC, n_, s);
-            else launch_raster<MysteryDebugComposer>(dbg, atlas_->dev(), frames, MG_OBS_U8_XYC, n_, s);
+            with_composers([&](auto C) { launch_raster<typename decltype(C)::Debug>(dbg, atlas_->dev(), frames, MG_OBS_U8_XYC, n_, s); });
         });
 }
 

@@ -40,25 +40,9 @@ __global__ __launch_bounds__(256, 7) void raster_gather_kernel(const typename Co
     }
 }
 
-// grid, LDS request and store flavour: launch_raster's for a launch of `count` frames
-template <class Composer>
-inline void launch_raster_gather(const typename Composer::Desc* records, const RasterAtlas& atlas, void* obs, int fmt, int n_records, const int32_t* pick,
-                                 int count, int* err, hipStream_t s) {
-    const int forced_lds = lab_raster_lds(RASTER_LDS);
-    const bool nt = fmt == MG_OBS_U8_XYC && raster_nt(count);
-    const int lds = forced_lds ? forced_lds : (nt ? RASTER_LDS_REQUEST : RASTER_LDS);
-    const dim3 grid(frames_grid(count));
-    if (nt)  // (the non-temporal stream exists for the uint8 format only)
-        launch(raster_gather_kernel<Composer, MG_OBS_U8_XYC, true>, grid, dim3(256), lds, s, records, atlas, obs, n_records, pick, count, err);
-    else
-        with_obs_format(fmt, [&](auto F) {
-            launch(raster_gather_kernel<Composer, decltype(F)::value, false>, grid, dim3(256), lds, s, records, atlas, obs, n_records, pick, count, err);
-        });
-}
-
 // The PAD form: mg_draw_frames_padded (include/memgym.h).  raster_gather_kernel with one difference -- a pick below 0 is a PADDING row: the workgroup
 // writes it as zeros (store_zero_row: 16-byte stores of a zero vector straight from registers, non-temporal where the launch's frames are; no compose, no
-// LDS, no barrier -- the recycled scratch stays as the last frame left it) and raises no error.  A kernel of its own: the gather forms above are the
+// LDS, no barrier -- the recycled scratch stays as the last frame left it) and raises no error.  A kernel of its own (DESIGN.md 3.4a): the gather forms above are the
 // measured ones and keep their symbols and their code.
 template <class Composer, int FMT, bool NT = false>
 __global__ __launch_bounds__(256, 7) void raster_gather_pad_kernel(const typename Composer::Desc* __restrict__ records, RasterAtlas A, void* __restrict__ obs,
@@ -91,20 +75,23 @@ __global__ __launch_bounds__(256, 7) void raster_gather_pad_kernel(const typenam
     }
 }
 
-// grid, LDS request and store flavour: launch_raster_gather's
-template <class Composer>
-inline void launch_raster_gather_pad(const typename Composer::Desc* records, const RasterAtlas& atlas, void* obs, int fmt, int n_records,
-                                     const int32_t* pick, int count, int* err, hipStream_t s) {
+// The launch of either form -- PAD: raster_gather_pad_kernel (mg_draw_frames_padded), else raster_gather_kernel (mg_draw_frames).  Grid, LDS request and
+// store flavour: launch_raster's for a launch of `count` frames
+template <class Composer, bool PAD>
+inline void launch_raster_gather(const typename Composer::Desc* records, const RasterAtlas& atlas, void* obs, int fmt, int n_records, const int32_t* pick,
+                                 int count, int* err, hipStream_t s) {
     const int forced_lds = lab_raster_lds(RASTER_LDS);
     const bool nt = fmt == MG_OBS_U8_XYC && raster_nt(count);
     const int lds = forced_lds ? forced_lds : (nt ? RASTER_LDS_REQUEST : RASTER_LDS);
     const dim3 grid(frames_grid(count));
-    if (nt)  // (the non-temporal stream exists for the uint8 format only)
-        launch(raster_gather_pad_kernel<Composer, MG_OBS_U8_XYC, true>, grid, dim3(256), lds, s, records, atlas, obs, n_records, pick, count, err);
-    else
-        with_obs_format(fmt, [&](auto F) {
-            launch(raster_gather_pad_kernel<Composer, decltype(F)::value, false>, grid, dim3(256), lds, s, records, atlas, obs, n_records, pick, count, err);
-        });
+    auto go = [&](auto F, auto NT) {
+        constexpr int FMT = decltype(F)::value;
+        constexpr bool STREAM = decltype(NT)::value;
+        launch(PAD ? raster_gather_pad_kernel<Composer, FMT, STREAM> : raster_gather_kernel<Composer, FMT, STREAM>, grid, dim3(256), lds, s, records, atlas, obs,
+               n_records, pick, count, err);
+    };
+    if (nt) go(std::integral_constant<int, MG_OBS_U8_XYC>{}, std::true_type{});  // (the non-temporal stream exists for the uint8 format only)
+    else with_obs_format(fmt, [&](auto F) { go(F, std::false_type{}); });
 }
 
 // mg_draw_debug_frames (include/memgym.h): the same walk over records of the DEBUG view's descriptors with a debug composer.  SIZE 84: the debug

@@ -35,21 +35,9 @@ __global__ __launch_bounds__(256, 7) void raster_gather_kernel(const typename Co
     }
 }
 
-// grid and LDS request: launch_raster's for a launch of `count` frames
-template <class Composer>
-inline void launch_raster_gather(const typename Composer::Desc* records, const RasterAtlas& atlas, void* obs, int fmt, int n_records, const int32_t* pick,
-                                 int count, int* err, hipStream_t s) {
-    const int forced_lds = lab_raster_lds(RASTER_LDS);
-    const int lds = forced_lds ? forced_lds : RASTER_LDS;
-    const dim3 grid(frames_grid(count));
-    with_obs_format(fmt, [&](auto F) {
-        launch(raster_gather_kernel<Composer, decltype(F)::value>, grid, dim3(256), lds, s, records, atlas, obs, n_records, pick, count, err);
-    });
-}
-
 // The PAD form: mg_draw_frames_padded (include/memgym.h).  raster_gather_kernel with one difference -- a pick below 0 is a PADDING row: the workgroup
 // writes it as zeros (store_zero_row: 16-byte stores of a zero vector straight from registers; no compose, no LDS, no barrier) and raises no error.
-// A kernel of its own: the gather forms above are the measured ones and keep their symbols and their code.
+// A kernel of its own (DESIGN.md 3.4a): the gather forms above are the measured ones and keep their symbols and their code.
 template <class Composer, int FMT>
 __global__ __launch_bounds__(256, 7) void raster_gather_pad_kernel(const typename Composer::Desc* __restrict__ records, RasterAtlas A, void* __restrict__ obs,
                                                                 int n_records, const int32_t* __restrict__ pick, int count, int* err) {
@@ -75,15 +63,18 @@ __global__ __launch_bounds__(256, 7) void raster_gather_pad_kernel(const typenam
     }
 }
 
-// grid and LDS request: launch_raster_gather's
-template <class Composer>
-inline void launch_raster_gather_pad(const typename Composer::Desc* records, const RasterAtlas& atlas, void* obs, int fmt, int n_records,
-                                     const int32_t* pick, int count, int* err, hipStream_t s) {
+// The launch of either form -- PAD: raster_gather_pad_kernel (mg_draw_frames_padded), else raster_gather_kernel (mg_draw_frames).  Grid and LDS request:
+// launch_raster's for a launch of `count` frames
+template <class Composer, bool PAD>
+inline void launch_raster_gather(const typename Composer::Desc* records, const RasterAtlas& atlas, void* obs, int fmt, int n_records, const int32_t* pick,
+                                 int count, int* err, hipStream_t s) {
     const int forced_lds = lab_raster_lds(RASTER_LDS);
     const int lds = forced_lds ? forced_lds : RASTER_LDS;
     const dim3 grid(frames_grid(count));
     with_obs_format(fmt, [&](auto F) {
-        launch(raster_gather_pad_kernel<Composer, decltype(F)::value>, grid, dim3(256), lds, s, records, atlas, obs, n_records, pick, count, err);
+        constexpr int FMT = decltype(F)::value;
+        launch(PAD ? raster_gather_pad_kernel<Composer, FMT> : raster_gather_kernel<Composer, FMT>, grid, dim3(256), lds, s, records, atlas, obs, n_records, pick, count,
+               err);
     });
 }
 

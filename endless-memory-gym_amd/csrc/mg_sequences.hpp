@@ -1,5 +1,5 @@
 // mg_sequences.hpp -- mg_split_episodes / mg_sequence_picks (include/memgym.h): a rollout's done rows cut into episode sequences of at most `length` steps,
-// and the sequences turned into [m][length] picks for mg_draw_frames_padded.  Nothing here depends on the family: included from mg_api.hip only.
+// and the sequences turned into [m][length] picks for mg_draw_frames_padded.  Nothing here depends on the family: included from mg_api_records.hpp only.
 // The table's ORDER is part of the definition -- (instance, t0) ascending -- so no atomic decides where an entry lands: a lane per instance counts its
 // sequences, a scan over the instances gives every lane its first entry, a lane per instance walks its column again and writes.  Lanes of a wave read 64
 // neighbouring bytes of a done row in both walks.  Three small launches: count (with the scan inside each workgroup), the scan of the workgroups' sums

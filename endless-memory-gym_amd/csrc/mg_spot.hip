@@ -110,7 +110,7 @@ __global__ __launch_bounds__(256) void spot_debug_desc_kernel(SpotParams P0, Spo
     out[i] = d;
 }
 
-// The same descriptor for ONE instance, for the picked form below (a body of its own: spot_debug_desc_kernel stays the code it was).
+// The same descriptor for ONE instance, for the picked form below (a body of its own: spot_debug_desc_kernel stays the code it was; DESIGN.md 3.4a).
 __device__ __forceinline__ SpotDesc spot_debug_desc_one(const SpotParams& P, const SpotIO& io, int i) {
     SpotDesc d = io.desc[i];
     const SpotCore s = io.core[i];
@@ -422,7 +422,7 @@ class SpotFamily : public Family {
         return v;
     }
     void expert_actions(const ExpertArgs& x, hipStream_t s) override {
-        if (dirty_) throw std::runtime_error("options that change geometry need a reset before the next step");
+        require_geometry();
         sets_.upload(s);
         launch_checked(spot_expert_kernel, expert_grid(n_), dim3(EXPERT_BLOCK), 0, s, P_, io(), x);
     }
@@ -621,13 +621,13 @@ class SpotFamily : public Family {
     std::pair<const void*, size_t> frame_rows() override { return {desc_.p, sizeof(SpotDesc)}; }
     void draw_records(const void* records, int n_records, const int32_t* pick, int count, int fmt, void* obs, hipStream_t s) override {
         with_bool(P_.ordered_holes, [&](auto BO) {
-            launch_raster_gather<SpotComposerT<decltype(BO)::value>>((const SpotDesc*)records, atlas_->dev(), obs, fmt, n_records, pick, count, err_.dev, s);
+            launch_raster_gather<SpotComposerT<decltype(BO)::value>, false>((const SpotDesc*)records, atlas_->dev(), obs, fmt, n_records, pick, count, err_.dev, s);
         });
         check_launch();
     }
     void draw_records_padded(const void* records, int n_records, const int32_t* pick, int count, int fmt, void* obs, hipStream_t s) override {
         with_bool(P_.ordered_holes, [&](auto BO) {
-            launch_raster_gather_pad<SpotComposerT<decltype(BO)::value>>((const SpotDesc*)records, atlas_->dev(), obs, fmt, n_records, pick, count, err_.dev, s);
+            launch_raster_gather<SpotComposerT<decltype(BO)::value>, true>((const SpotDesc*)records, atlas_->dev(), obs, fmt, n_records, pick, count, err_.dev, s);
         });
         check_launch();
     }

@@ -18,7 +18,7 @@ static int fail(const char* what) {
 
 static bool says(const char* got, const char* want) { return got && strstr(got, want); }
 
-// frame_rows_save_kernel's walk (mg_api.hip), lane by lane: -> entries flagged
+// frame_rows_save_kernel's walk (mg_api_records.hpp), lane by lane: -> entries flagged
 static int save_walk(const std::vector<unsigned char>& descs, int vec_per_row, const std::vector<int32_t>* idx, int count, int num_envs, std::vector<unsigned char>& rec) {
     int flagged = 0;
     const int64_t lanes = (((int64_t)count * vec_per_row + 255) / 256) * 256;  // whole workgroups, as launched
