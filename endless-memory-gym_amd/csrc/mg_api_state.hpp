@@ -33,6 +33,8 @@ const HandleCounter HANDLE_COUNTERS[] = {
     {"debug_frame_saves", &mg_env::debug_frame_saves}, {"debug_frame_draws", &mg_env::debug_frame_draws},
     {"masked_steps", &mg_env::masked_steps}, {"next_steps", &mg_env::next_steps},
     {"next_fused_steps", &mg_env::next_fused_steps}, {"final_frame_steps", &mg_env::final_frame_steps},
+    {"episode_positions", &mg_env::episode_positions}, {"window_picks", &mg_env::window_picks},
+    {"row_gathers", &mg_env::row_gathers},
 };
 }  // namespace
 

@@ -451,6 +451,185 @@ class EpisodeSequences:
         return torch.where(mask.reshape(mask.shape + (1,) * (x.dim() - 2)), rows, torch.zeros_like(rows))
 
 
+def _plain_int(what, name, v, least):
+    """v as an int; ValueError unless it is an integer (no bool, no float) in least .. MAX_PICK"""
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < least or v > MAX_PICK:
+        raise ValueError("%s: %s must be an integer >= %d, got %r" % (what, name, least, v))
+    return int(v)
+
+
+def _per_instance_int32(what, name, t, n, device):
+    """an int32 / int64 tensor [n] (on `device` if given) -> a contiguous int32 tensor; None stays None"""
+    if t is None:
+        return None
+    if not (isinstance(t, torch.Tensor) and t.dtype in (torch.int32, torch.int64) and tuple(t.shape) == (n,)):
+        raise ValueError("%s: %s must be an int32 or int64 tensor [%d]" % (what, name, n))
+    if device is not None and t.device != device:
+        raise ValueError("%s: %s is on %s, the handle on %s" % (what, name, t.device, device))
+    return t.to(torch.int32).contiguous()
+
+
+def check_episode_windows(done, window, num_envs, lag=0, back=0, steps=None, pos0=None, device=None):
+    """The argument checks of episode_positions / episode_windows, which need no handle: -> (done as a uint8 view [K, N], K, window, lag, back, steps as
+    an int32 tensor [N] or None, pos0 as an int32 tensor [N] or None).  ValueError for a `done` that is no contiguous bool / uint8 tensor [K, N] with
+    K >= 1 and N = num_envs, a window below 1, a negative lag or back, (back + K + 1) * N beyond an int32, `steps` / `pos0` that are no int32 / int64
+    tensors [N], and anything that does not lie on `device` (if given)."""
+    what = "episode_windows"
+    if not (isinstance(done, torch.Tensor) and done.dtype in (torch.bool, torch.uint8) and done.dim() == 2):
+        raise ValueError("%s: done must be a contiguous bool or uint8 tensor [K, N]" % what)
+    K, N = int(done.shape[0]), int(done.shape[1])
+    if N != int(num_envs) or K < 1:
+        raise ValueError("%s: done is %s, need [K >= 1, %d] (the handle's instances)" % (what, tuple(done.shape), int(num_envs)))
+    window, lag, back = _plain_int(what, "window", window, 1), _plain_int(what, "lag", lag, 0), _plain_int(what, "back", back, 0)
+    if (back + K + 1) * N > MAX_PICK:
+        raise ValueError("%s: (back + K + 1) * N = %d does not fit the int32 of a pick: take slices of the rollout" % (what, (back + K + 1) * N))
+    if not done.is_contiguous():
+        raise ValueError("%s: done must be a contiguous bool or uint8 tensor [K, N]" % what)
+    if device is not None and done.device != device:
+        raise ValueError("%s: done is on %s, the handle on %s" % (what, done.device, device))
+    return (done.view(torch.uint8), K, window, lag, back, _per_instance_int32(what, "steps", steps, N, device),
+            _per_instance_int32(what, "pos0", pos0, N, device))
+
+
+def _pick_tensor(what, name, t, device=None):
+    """An index argument of any shape -> a contiguous int32 tensor of that shape (on `device` if given); integer tensors, arrays and lists are taken"""
+    if not isinstance(t, torch.Tensor):
+        a = np.asarray(t)
+        if a.dtype.kind not in "iu":
+            raise ValueError("%s: %s must hold integers, got dtype %s" % (what, name, a.dtype))
+        t = torch.as_tensor(a.astype(np.int64))
+    if t.dtype not in (torch.int32, torch.int64):
+        raise ValueError("%s: %s must be an int32 or int64 tensor, got %s" % (what, name, t.dtype))
+    t = t.to(dtype=torch.int32) if device is None else t.to(device=device, dtype=torch.int32)
+    return t.contiguous()
+
+
+def check_gather_rows(x, pick, out=None, device=None):
+    """The argument checks of gather_rows, which need no handle: -> (x, pick as a contiguous int32 tensor or None, the result's shape, bytes of a row).
+    ValueError for an `x` that is no contiguous tensor [R, ...] with rows of at least one byte, a pick that holds no integers, more rows than x has
+    without a pick, and an `out` of another shape / dtype / device than the result or one that is not contiguous."""
+    what = "gather_rows"
+    if not (isinstance(x, torch.Tensor) and x.dim() >= 1 and x.is_contiguous()):
+        raise ValueError("%s: x must be a contiguous tensor [R, ...]" % what)
+    row_bytes = int(np.prod(x.shape[1:], dtype=np.int64)) * x.element_size()
+    if row_bytes < 1:
+        raise ValueError("%s: a row of x %s holds no byte" % (what, tuple(x.shape)))
+    if int(x.shape[0]) > MAX_PICK:
+        raise ValueError("%s: x has %d rows, a pick is an int32" % (what, int(x.shape[0])))
+    if device is not None and x.device != device:
+        raise ValueError("%s: x is on %s, the handle on %s" % (what, x.device, device))
+    if pick is not None:
+        pick = _pick_tensor(what, "pick", pick, x.device)
+    shape = ((int(x.shape[0]),) if pick is None else tuple(pick.shape)) + tuple(x.shape[1:])
+    if (x.shape[0] if pick is None else pick.numel()) > MAX_PICK:
+        raise ValueError("%s: more than %d rows in one call" % (what, MAX_PICK))
+    if out is not None and not (isinstance(out, torch.Tensor) and out.dtype == x.dtype and tuple(out.shape) == shape and out.is_contiguous()
+                                and out.device == x.device):
+        raise ValueError("%s: out must be a contiguous %s tensor of shape %s on %s" % (what, x.dtype, shape, x.device))
+    return x, pick, shape, row_bytes
+
+
+class EpisodeWindows:
+    """What VecMemoryGym.episode_windows returns (include/memgym.h: mg_episode_positions / mg_window_picks): the sliding memory windows of a rollout of
+    `steps` steps of `num_envs` instances.
+        pos      int32 [K + 1, N]   the steps instance i's episode had already taken at store row t (mg_episode_positions)
+        window   W, the rows of a window;  lag: the window of sample (t, i) ends at row t - lag;  back: rows of the previous trace a window may reach into
+    The window of sample s = t * N + i holds the rows max(t - pos[t, i], t - lag - W + 1, -back) .. t - lag, oldest first, pads behind them.  `carry`
+    is the next call's pos0.  Nothing here synchronises."""
+    __slots__ = ("pos", "window", "lag", "back", "steps", "num_envs", "_env")
+
+    def __init__(self, pos, window, lag, back, steps, num_envs, env=None):
+        self.pos, self.window, self.lag, self.back, self.steps, self.num_envs, self._env = pos, int(window), int(lag), int(back), int(steps), int(num_envs), env
+
+    @property
+    def carry(self):
+        """row K of pos: the positions behind the rollout's last step -- the pos0 of the next rollout's episode_windows"""
+        return self.pos[self.steps]
+
+    def picks(self, sel=None, m=None):
+        """-> (pick int32 [M, W], mask bool [M, W], len int32 [M]) (include/memgym.h: mg_window_picks): row j belongs to sample sel[j] = t * N + i
+        (sel=None: sample j, M = m, default (K + 1) * N: every sample, the bootstrap row included).  pick[j, l] = (back + lo + l) * N + i for l < len,
+        -1 behind it: an index into a flattened [back + K + 1, N] store whose first `back` rows are the last `back` rows of the previous rollout.
+        sel: an integer tensor / list [M]; an entry < 0 gives a padding row, an entry at or beyond (K + 1) * N a padding row and error bit 512.  One
+        launch on the current stream."""
+        what = "EpisodeWindows.picks"
+        env = self._env
+        if env is None:
+            raise ValueError("%s: these windows belong to no handle" % what)
+        samples = (self.steps + 1) * self.num_envs
+        if sel is not None:
+            if m is not None:
+                raise ValueError("%s: give sel or m, not both" % what)
+            sel = _instance_index(what, "sel", sel, env.device)
+            M = sel.numel()
+        else:
+            M = samples if m is None else m
+            if isinstance(M, bool) or not isinstance(M, (int, np.integer)) or M < 0 or M > samples:
+                raise ValueError("%s: m must be an integer in 0 .. %d, got %r" % (what, samples, m))
+            M = int(M)
+        if M * self.window > MAX_PICK:
+            raise ValueError("%s: %d rows of %d picks do not fit one call" % (what, M, self.window))
+        pick = torch.empty((M, self.window), dtype=torch.int32, device=env.device)
+        mask = torch.empty((M, self.window), dtype=torch.bool, device=env.device)
+        length = torch.empty((M,), dtype=torch.int32, device=env.device)
+        if M:
+            with torch.cuda.device(env.device):
+                _native.check(_native.LIB.mg_window_picks(env._h, self.pos.data_ptr(), self.steps, None if sel is None else sel.data_ptr(), M, self.window,
+                                                          self.lag, self.back, pick.data_ptr(), mask.data_ptr(), length.data_ptr(), env._stream()),
+                              "mg_window_picks")
+        return pick, mask, length
+
+    def store(self, x, prefix=None):
+        """The store the picks index, [(back + rows of x) * N, ...]: cat(prefix, x) flattened over its first two dimensions.  x: [K, N, ...] (actions,
+        rewards: a pick of row K is then out of range) or [K + 1, N, ...] (per-frame data: hidden states, values).  prefix: [back, N, ...], the last
+        `back` rows of the previous rollout's x in front of its row K_prev; required when back > 0.  ValueError otherwise."""
+        what = "EpisodeWindows.gather"
+        if not (isinstance(x, torch.Tensor) and x.dim() >= 2 and int(x.shape[0]) in (self.steps, self.steps + 1) and int(x.shape[1]) == self.num_envs):
+            raise ValueError("%s: x must be a tensor [%d or %d, %d, ...]" % (what, self.steps, self.steps + 1, self.num_envs))
+        if self.back > 0:
+            if prefix is None:
+                raise ValueError("%s: back = %d: a prefix [%d, %d, ...] is required (the last rows of the previous rollout)" % (what, self.back, self.back, self.num_envs))
+            if not (isinstance(prefix, torch.Tensor) and prefix.dtype == x.dtype and prefix.device == x.device
+                    and tuple(prefix.shape) == (self.back, self.num_envs) + tuple(x.shape[2:])):
+                raise ValueError("%s: prefix must be a %s tensor of shape %s on %s" % (what, x.dtype, (self.back, self.num_envs) + tuple(x.shape[2:]), x.device))
+            x = torch.cat((prefix, x), 0)
+        elif prefix is not None and int(prefix.shape[0]) != 0:
+            raise ValueError("%s: back = 0: there is no room for a prefix" % what)
+        return x.contiguous().view((-1,) + tuple(x.shape[2:]))
+
+    def gather(self, x, sel=None, prefix=None):
+        """x [K, N, ...] or [K + 1, N, ...] -> [M, W, ...], zero rows at the pads: gather_rows on store(x, prefix), indexed with picks(sel).  One launch
+        for the picks and one for the rows (include/memgym.h: mg_gather_rows_padded), on the current stream."""
+        rows = self.store(x, prefix)
+        if self._env is None:
+            raise ValueError("EpisodeWindows.gather: these windows belong to no handle")
+        return self._env.gather_rows(rows, self.picks(sel)[0])
+
+
+def check_window_frames(frames, windows, record_bytes):
+    """The layout checks of draw_windows, which need no handle: -> a FrameRecords or uint8 tensor for draw_frames_padded.  With back == 0 `frames` may be
+    the RolloutTrace the windows were made from (its K and N are checked); with back > 0 it must be a FrameRecords / uint8 store of
+    [back + K + 1, N, record_bytes] rows that the caller assembled.  ValueError otherwise."""
+    what = "draw_windows"
+    if not isinstance(windows, EpisodeWindows):
+        raise ValueError("%s: windows must be the EpisodeWindows episode_windows returned" % what)
+    if isinstance(frames, RolloutTrace):
+        if windows.back > 0:
+            raise ValueError("%s: back = %d: a trace holds no rows of the previous rollout; pass a FrameRecords / uint8 store of [%d + %d + 1, %d, %d] rows"
+                             % (what, windows.back, windows.back, windows.steps, windows.num_envs, int(record_bytes)))
+        if not (isinstance(frames.frames, torch.Tensor) and frames.frames.dim() == 3):
+            raise ValueError("%s: the trace keeps no frames" % what)
+        if (frames.steps, frames.num_envs) != (windows.steps, windows.num_envs):
+            raise ValueError("%s: the trace holds %d steps of %d instances, the windows were made from %d steps of %d"
+                             % (what, frames.steps, frames.num_envs, windows.steps, windows.num_envs))
+        return FrameRecords(frames.frames, frames.frame_layout)
+    rec = frames.records if isinstance(frames, FrameRecords) else frames
+    want = (windows.back + windows.steps + 1, windows.num_envs, int(record_bytes))
+    if not (isinstance(rec, torch.Tensor) and rec.dtype == torch.uint8 and tuple(rec.shape) == want and rec.is_contiguous()):
+        raise ValueError("%s: frames must be a contiguous uint8 store of shape %s (back + K + 1 rows of N records)" % (what, want))
+    return frames
+
+
 class VecMemoryGym:
     metadata ={"render_modes": ["rgb_array", "debug_rgb_array"], "render_fps": 25}
 
@@ -1221,6 +1400,70 @@ class VecMemoryGym:
         flat = self.draw_frames_padded(frames, pick.view(-1), out=flat, obs_format=fmt)
         return flat.view((M, L) + shape), mask
 
+    # ------------------------------------------------------------------ memory windows
+    def episode_positions(self, done, steps=None, pos0=None):
+        """-> int32 [K + 1, N] (include/memgym.h: mg_episode_positions): row t holds the steps instance i's episode had already taken when frame t of
+        the rollout's [K + 1, N] store was shown.  done: a bool or uint8 tensor [K, N], e.g. trace.done.  steps: an integer tensor [N], the steps
+        instance i took (play()'s steps_played), None: K for all.  pos0: an integer tensor [N], the positions at the rollout's first frame -- row K of
+        the previous rollout's result -- None: every instance starts an episode.  One small launch on the current stream; nothing synchronises,
+        nothing is allocated in the handle."""
+        self._require_started("episode_positions")
+        d8, K, _, _, _, steps, pos0 = check_episode_windows(done, 1, self.num_envs, 0, 0, steps, pos0, self.device)
+        pos = torch.empty((K + 1, self.num_envs), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            _native.check(_native.LIB.mg_episode_positions(self._h, d8.data_ptr(), K, None if steps is None else steps.data_ptr(),
+                                                           None if pos0 is None else pos0.data_ptr(), pos.data_ptr(), self._stream()), "mg_episode_positions")
+        return pos
+
+    def episode_windows(self, done, window, lag=0, back=0, steps=None, pos0=None):
+        """The sliding memory windows of a rollout (include/memgym.h: MEMORY WINDOWS) -> EpisodeWindows: episode_positions(done, steps, pos0) with the
+        window's shape.  window: the rows of a window.  lag: 0 -- the window of sample (t, i) ends with its own row t (windows of frames); 1 -- one row
+        earlier (memories of past hidden states).  back: how many rows of the previous rollout a window may reach into; its picks then index a store
+        of [back + K + 1, N] rows.  One small launch."""
+        self._require_started("episode_windows")
+        d8, K, window, lag, back, steps, pos0 = check_episode_windows(done, window, self.num_envs, lag, back, steps, pos0, self.device)
+        return EpisodeWindows(self.episode_positions(d8, steps, pos0), window, lag, back, K, self.num_envs, self)
+
+    def gather_rows(self, x, pick, out=None):
+        """Rows of a store by index, zero rows at the pads (include/memgym.h: mg_gather_rows_padded): x [R, ...] contiguous, of any dtype and row
+        length; pick: integers of any shape, or None (row j) -> pick.shape + x.shape[1:].  A pick below 0 gives a row of zeros; a pick at or beyond
+        R leaves its row as it was and raises error bit 512.  out: a contiguous tensor of the result's shape and x's dtype that shares no byte
+        with x.  One launch on the current stream; nothing synchronises."""
+        x, pick, shape, row_bytes = check_gather_rows(x, pick, out, self.device)
+        if out is None:
+            out = torch.empty(shape, dtype=x.dtype, device=self.device)
+        count = int(x.shape[0]) if pick is None else pick.numel()
+        if count:
+            with torch.cuda.device(self.device):
+                _native.check(_native.LIB.mg_gather_rows_padded(self._h, x.data_ptr(), int(x.shape[0]), row_bytes, None if pick is None else pick.data_ptr(),
+                                                                count, out.data_ptr(), self._stream()), "mg_gather_rows_padded")
+        return out
+
+    def draw_windows(self, frames, windows, sel=None, out=None, obs_format=None):
+        """Frames of a minibatch of windows -> (obs [M, W] + shape of the format, mask bool [M, W], len int32 [M]): row (j, l) is the l-th oldest frame
+        of the window of sample sel[j] (sel=None: every sample), zeros behind the window's len and for entries of sel below 0.  frames: with
+        back == 0 the RolloutTrace the windows were made from, or a FrameRecords / uint8 tensor [K + 1, N, frame_record_bytes]; with back > 0 a
+        FrameRecords / uint8 store [back + K + 1, N, frame_record_bytes] whose first `back` rows are the previous rollout's frames[K_prev - back : K_prev].
+        Its layout is checked as draw_sequences checks it.  out: a contiguous tensor [M, W] + shape to draw into.  Two launches on the current
+        stream: the picks, and the PAD form of the gather raster."""
+        what = "draw_windows"
+        self._require_started(what)
+        frames = check_window_frames(frames, windows, self.frame_record_bytes)
+        fmt = self.obs_format if obs_format is None else obs_format
+        if fmt not in self.OBS_FORMATS:
+            raise ValueError("%s: obs_format must be one of %s" % (what, sorted(self.OBS_FORMATS)))
+        _, dt, shape = self.OBS_FORMATS[fmt]
+        pick, mask, length = windows.picks(sel)
+        M, W = int(pick.shape[0]), windows.window
+        if out is not None:
+            if not (isinstance(out, torch.Tensor) and out.dtype == dt and tuple(out.shape) == (M, W) + shape and out.is_contiguous()):
+                raise ValueError("%s: out must be a contiguous %s tensor of shape %s" % (what, dt, (M, W) + shape))
+            flat = out.view((M * W,) + shape)
+        else:
+            flat = None
+        flat = self.draw_frames_padded(frames, pick.view(-1), out=flat, obs_format=fmt)
+        return flat.view((M, W) + shape), mask, length
+
     # ------------------------------------------------------------------ debug-view records
     DEBUG_SIZES = {84: (84, 84, 3), 336: (336, 336, 3)}  # draw_debug_frames: the debug surface [x][y][c], or the reference's debug_rgb_array [y][x][c]
 
@@ -1513,7 +1756,8 @@ class VecMemoryGym:
                   64: "a deferred-reset queue overflowed (a previous fused launch did not drain it)",
                   256: "use_exit=False for an instance that never had an exit (the reference raises AttributeError at this reset)",
                   512: "save_instances / load_instances / save_frames / draw_frames / draw_frames_padded / draw_sequences / save_debug_frames / "
-                       "draw_debug_frames / EpisodeSequences.picks: an instance, record or sequence index out of range (the entry was skipped)"}
+                       "draw_debug_frames / EpisodeSequences.picks / EpisodeWindows.picks / draw_windows / gather_rows: an instance, record, sequence, "
+                       "sample or row index out of range (the entry was skipped)"}
 
     def check_errors(self):
         """Raise if a kernel flagged a capacity/failure condition since the last call (synchronises the device).

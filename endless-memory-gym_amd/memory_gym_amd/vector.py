@@ -195,6 +195,22 @@ class GymnasiumVectorEnv(_Base):
         """VecMemoryGym.draw_sequences -> (obs [M, L, ...], mask [M, L]) of a minibatch of sequences (device tensors, whatever as_numpy says)."""
         return self.env.draw_sequences(frames, seqs, sel=sel, out=out, obs_format=obs_format)
 
+    def episode_positions(self, done, steps=None, pos0=None):
+        """VecMemoryGym.episode_positions -> int32 [K + 1, N] (a device tensor, whatever as_numpy says: positions are picked from on the device)."""
+        return self.env.episode_positions(done, steps=steps, pos0=pos0)
+
+    def episode_windows(self, done, window, lag=0, back=0, steps=None, pos0=None):
+        """VecMemoryGym.episode_windows -> EpisodeWindows (device tensors, whatever as_numpy says: windows are drawn and gathered on the device)."""
+        return self.env.episode_windows(done, window, lag=lag, back=back, steps=steps, pos0=pos0)
+
+    def gather_rows(self, x, pick, out=None):
+        """VecMemoryGym.gather_rows: rows of a store by index, zero rows where the pick is below 0 (a device tensor, whatever as_numpy says)."""
+        return self.env.gather_rows(x, pick, out=out)
+
+    def draw_windows(self, frames, windows, sel=None, out=None, obs_format=None):
+        """VecMemoryGym.draw_windows -> (obs [M, W, ...], mask [M, W], len [M]) of a minibatch of windows (device tensors, whatever as_numpy says)."""
+        return self.env.draw_windows(frames, windows, sel=sel, out=out, obs_format=obs_format)
+
     def advance(self, steps, eps=0.0, seed=0, step=None, render=True, stats=True):
         """`steps` steps under the scripted teacher without a frame (VecMemoryGym.advance) -> (obs or None, stats); numpy with as_numpy.
         Episodes that end inside the call are NOT reported as `final_observation` / `final_info`: they are counted and summed in `stats`."""

@@ -590,7 +590,8 @@ int mg_draw_frames(mg_env* env, const void* rec_dev, int64_t n_records, const in
  * same.  pick_dev == NULL is legal and then equals mg_draw_frames.
  * mg_debug_counter "sequence_splits" counts the mg_split_episodes calls, "padded_draws" the mg_draw_frames_padded calls with count > 0, on the host.
  * MG_STATE_VERSION is unchanged: no state is added.
- * OUT OF SCOPE: sliding memory windows for transformer agents; sequences that continue across two traces (the start of a trace starts a sequence,
+ * OUT OF SCOPE: sliding memory windows for transformer agents (windows of their own: mg_window_picks, below, and there a window does reach into the
+ * previous trace); sequences that continue across two traces (the start of a trace starts a sequence,
  * start_dev only sets the MG_SEQ_FIRST flag); terminal frames inside a traced call (still the trace's own open item); the MortarMayhemB ids' vector
  * observation per step. */
 typedef struct mg_sequence { int32_t instance, t0, len, flags; } mg_sequence;   /* 16 bytes, stored as one vector */
@@ -602,6 +603,64 @@ int mg_sequence_picks(mg_env* env, const mg_sequence* seq_dev, const int32_t* co
                       int32_t m, int32_t length, int32_t* pick_dev, uint8_t* mask_dev, void* stream);
 int mg_draw_frames_padded(mg_env* env, const void* rec_dev, int64_t n_records, const int32_t* pick_dev, int64_t count, int format,
                           void* obs_dev, void* stream);
+
+/* MEMORY WINDOWS: for every training sample (t, i) the window of instance i's previous `window` steps inside the same episode, with a mask and a length --
+ * what a TransformerXL-style agent with a sliding episodic memory trains on -- and the gather of such windows from a trainer's own per-step store
+ * (hidden states, values, log-probs) with zero rows at the pads.  A window reaches back over an episode's earlier steps INCLUDING INTO THE PREVIOUS TRACE.
+ *   mg_episode_positions    done rows [steps][num_envs] -> pos [steps + 1][num_envs]: how many steps the episode of a store row had already taken
+ *   mg_window_picks         positions, samples (all, or a selection) -> pick[m][window] row indices, -1 at the pads, an optional mask and length
+ *   mg_gather_rows_padded   rows of ANY byte length gathered by pick; a pick below 0 writes its row as ZEROS and is no error
+ * All three are enqueue-only on `stream`, synchronise nothing, keep no scratch in the handle and allocate nothing -- so even a handle's first call can be
+ * captured into a HIP graph; the arrays are read at replay, the integers are the captured values.  MG_STATE_VERSION is unchanged: no state is added.
+ * mg_episode_positions, DEFINITION.  done_dev is [steps][num_envs] bytes, step-major: a trace's done_dev.  pos_dev is int32 [steps + 1][num_envs]: row t
+ * is the number of steps instance i's current episode had already taken when the observation of row t of the [steps + 1][num_envs] frame store was shown
+ * (row 0 of that store is the frame before the call's first step, as in mg_sequence_picks).  With n_i as in mg_split_episodes (steps_of_dev clamped to
+ * 0 .. steps, NULL: steps):
+ *   pos[0][i]   = pos0_dev ? max(pos0_dev[i], 0) : 0
+ *   pos[t+1][i] = done[t][i] ? 0 : pos[t][i] + 1     for t <  n_i     (a position stops counting at INT32_MAX)
+ *   pos[t+1][i] = pos[t][i]                          for t >= n_i
+ * Row `steps` is the carry-out: passed as pos0_dev of the next trace's call it makes positions continue across two traces.  Under MG_PLAY_EPISODE the
+ * carry-out of a finished instance is 0, which is right once the caller has reset it.
+ * LAUNCHES: one small one, a lane per instance walking its column; the lanes of a wave read 64 neighbouring bytes of a done row and store 64 neighbouring
+ * int32, as the split's count kernel does.  No atomic, no scratch.
+ * Errors (-1): before the first mg_reset / mg_set_state; a NULL done_dev or pos_dev; steps < 1; (steps + 1) * num_envs > INT32_MAX.
+ * mg_window_picks, DEFINITION.  Row j of pick_dev ([m][window] int32) belongs to sample s = sel_dev ? sel_dev[j] : j, with s = t * num_envs + i and
+ * 0 <= t <= steps (row `steps` is the bootstrap observation).  pos_dev is what mg_episode_positions wrote for this trace.  Let
+ *   e   = t - pos[t][i]                   the episode's first row, which may be negative: the episode began in an earlier trace
+ *   hi  = t - lag
+ *   lo  = max(e, hi - window + 1, -back)
+ *   len = max(0, hi - lo + 1)
+ * then pick[j][l] = (back + lo + l) * num_envs + i for l < len, and -1 behind it: the valid picks first, oldest first, the pads after them -- the
+ * sequences' convention.  A pick indexes a store of [back + steps + 1][num_envs] rows whose first `back` rows are the LAST `back` rows before row 0 of
+ * this trace: rows K_prev - back .. K_prev - 1 of the previous trace's [K_prev + 1][num_envs] store (its row K_prev is this trace's row 0).  back = 0 keeps
+ * a window inside the trace.  lag = 0: the window ends with the sample's own observation (windows of frames); lag = 1: it ends one step earlier
+ * (TransformerXL memories of past hidden states); any lag >= 0 is legal.  mask_dev (uint8 [m][window], 1 where the pick is 0 or more) and len_dev
+ * (int32 [m]) are optional.
+ *   s < 0                                              a whole row of -1, len 0, no error: a minibatch padded to a fixed m;
+ *   s >= (steps + 1) * num_envs, sel_dev set           a whole row of -1, len 0 and error bit 512 (mg_poll_errors);
+ *   sel_dev == NULL                                    m <= (steps + 1) * num_envs is required.
+ * ONE launch, a lane per element; pos_dev and sel_dev are read at replay.  num_envs is the handle's.
+ * Errors (-1): a NULL pos_dev or pick_dev; steps < 1, m < 0, window < 1, lag < 0 or back < 0; m * window > INT32_MAX;
+ * (back + steps + 1) * num_envs > INT32_MAX; sel_dev == NULL with m > (steps + 1) * num_envs.
+ * mg_gather_rows_padded: row j of dst_dev receives row pick_dev[j] of src_dev ([n_rows] rows), row_bytes bytes each, for any row_bytes >= 1 and any
+ * alignment of the two bases.  A pick below 0 writes the row as zeros, every byte, and is no error; a pick at or beyond n_rows leaves the row untouched and
+ * raises bit 512; pick_dev == NULL means row j, and then count <= n_rows is required.  src and dst must not overlap: the call refuses it where the two
+ * ranges (n_rows rows, count rows) share a byte.  Byte offsets are 64-bit.
+ * ONE launch.  The host chooses the widest access of 16 / 8 / 4 / 2 / 1 bytes that divides row_bytes and both base addresses.  Rows of 32 accesses or more
+ * take the ROW form: a wave walks four neighbouring output rows together, the picks read wave-uniformly, the four rows' loads of a round issued before
+ * its first store, a zero row stored straight from registers.  Shorter rows (an action, a reward, a done byte) take the PACKED form: lanes over the
+ * flattened count * row_bytes / width accesses, so that a wave is not spent on 4 bytes.  No LDS, no barrier, no atomic except the error word's.
+ * Errors (-1): count, n_rows < 0 or > INT32_MAX; row_bytes < 1 or > INT32_MAX; pick_dev == NULL with count > n_rows; with count > 0: a NULL dst_dev, a
+ * NULL src_dev with n_rows > 0, overlapping ranges.
+ * mg_debug_counter "episode_positions", "window_picks" and "row_gathers" count the calls that were not refused, on the host.
+ * OUT OF SCOPE: windows that reach back over more than one earlier trace in one store (assemble a longer prefix: the definition only needs `back` rows
+ * in front of row 0); attention masks for segment-level recurrence with gradients across segments; terminal frames inside a traced call. */
+int mg_episode_positions(mg_env* env, const uint8_t* done_dev, int32_t steps, const int32_t* steps_of_dev, const int32_t* pos0_dev,
+                         int32_t* pos_dev, void* stream);
+int mg_window_picks(mg_env* env, const int32_t* pos_dev, int32_t steps, const int32_t* sel_dev, int32_t m, int32_t window, int32_t lag,
+                    int32_t back, int32_t* pick_dev, uint8_t* mask_dev, int32_t* len_dev, void* stream);
+int mg_gather_rows_padded(mg_env* env, const void* src_dev, int64_t n_rows, int64_t row_bytes, const int32_t* pick_dev, int64_t count,
+                          void* dst_dev, void* stream);
 
 /* DEBUG-VIEW RECORDS: keep the ground-truth view of a FEW instances and draw it later.  mg_render_debug draws every instance at once, from the current state,
  * synchronously: at 65,536 instances 22 GB of views and 1.4 GB of scratch to look at one of them.  But a debug view, like a frame, is a pure function of a
