@@ -10,7 +10,11 @@ If gymnasium is installed on the host the ids are also registered there (gymnasi
 single-instance adapter), mirroring the reference's registration side effect on import.
 """
 from .reset_params import DEFAULTS, process_reset_params  # noqa: F401
-from .vec_env import ENV_IDS, DebugFrameRecords, EpisodeSequences, EpisodeWindows, FrameRecords, InstanceSnapshot, MemoryGymEnv, RolloutTrace, VecMemoryGym, alloc_obs_buffer  # noqa: F401
+from .vec_env import ENV_IDS, VecMemoryGym  # noqa: F401
+from .episodes import EpisodeSequences, EpisodeWindows  # noqa: F401
+from .obs_memory import alloc_obs_buffer  # noqa: F401
+from .records import DebugFrameRecords, FrameRecords, InstanceSnapshot, RolloutTrace  # noqa: F401
+from .single import MemoryGymEnv  # noqa: F401
 from .vector import GymnasiumVectorEnv  # noqa: F401
 from . import envs  # noqa: F401,E402
 

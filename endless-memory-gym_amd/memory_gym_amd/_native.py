@@ -39,6 +39,13 @@ class RolloutTraceRows(C.Structure):  # include/memgym.h: mg_rollout_trace (devi
                 ("reward_dev", C.c_void_p), ("done_dev", C.c_void_p)]
 
 
+def new_struct(cls):
+    """one of the structures above with its first member set: the library reads struct_size bytes of it and no more (include/memgym.h)"""
+    s = cls()
+    s.struct_size = C.sizeof(cls)
+    return s
+
+
 class Sequence(C.Structure):  # include/memgym.h: mg_sequence, one entry of mg_split_episodes' table (16 bytes)
     _fields_ = [("instance", C.c_int32), ("t0", C.c_int32), ("len", C.c_int32), ("flags", C.c_int32)]
 

@@ -217,7 +217,7 @@ class PeerObsBuffer:
     def _check_exportable(tensor):
         """hipIpcGetMemHandle works on hipMalloc allocations only; a zone-balanced buffer (mg_obs_alloc: hipMemCreate pieces in a
         reserved virtual range) would fail late and cryptically inside torch's reduce_tensor.  Refuse it here, by name."""
-        from .vec_env import is_balanced_buffer
+        from .obs_memory import is_balanced_buffer  # (in here: tests/test_dist_gloo.py loads this file on its own, without the package and its library)
         if is_balanced_buffer(tensor):
             raise ValueError("PeerObsBuffer: a buffer from mg_obs_alloc (obs_placement='balanced') cannot be exported through HIP IPC; "
                              "share an ordinary allocation (torch.empty) -- its rows are filled over xGMI at a fifth of one memory "

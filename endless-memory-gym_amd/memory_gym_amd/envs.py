@@ -2,7 +2,7 @@
 registration uses `module:Class` entry points exactly like the reference's (memory_gym/__init__.py:13-61) and
 `isinstance(env.unwrapped, GridMortarMayhemEnv)` style checks keep working.  Each class is the single-instance adapter
 (`MemoryGymEnv`) bound to one env id; constructor signature as in the reference: `Class(render_mode=None)`."""
-from .vec_env import MemoryGymEnv
+from .single import MemoryGymEnv
 
 
 def _bind(name, env_id, ref):

@@ -12,15 +12,24 @@ stream and return torch tensors that alias the kernels' output buffers (no copie
 
 `MemoryGymEnv` is the num_envs == 1 adapter with the reference's exact single-instance signature
 (numpy obs, Python float reward, bool done, False, dict info).
+
+This module holds the handle.  What it returns and takes lives below it and is re-exported here under the names it always had: the observation
+memory (obs_memory.py), the value types with their handle-free checks (records.py, episodes.py, over _args.py), the handle's calls over kept
+rollouts (record_calls.py, its base class); the adapter (single.py) sits on top of it.
 """
 import ctypes as C
 import os
-import weakref
 
 import numpy as np
 import torch
 
 from . import _native
+from ._args import MAX_PICK, aligned_on, index_tensor, ptr  # noqa: F401
+from .episodes import EpisodeSequences, EpisodeWindows, check_episode_windows, check_gather_rows, check_split_episodes, check_window_frames  # noqa: F401
+from .obs_memory import alloc_obs_buffer, is_balanced_buffer  # noqa: F401
+from .record_calls import RecordCalls
+from .records import (MAX_DRAW_RECORDS, OBS_FORMATS, DebugFrameRecords, FrameRecords, InstanceSnapshot, RolloutTrace, _distinct_host_index,  # noqa: F401
+                      check_frame_draw, check_frame_save, check_instance_load, check_instance_save, check_rollout_trace)
 from .reset_params import DEFAULTS, calc_max_episode_steps, process_reset_params
 
 ENV_IDS = list(DEFAULTS.keys())
@@ -56,586 +65,10 @@ def _spaces(action_dim, gt_dim, vec_dim=0):
     return act, obs, gt
 
 
-_BALANCED = weakref.WeakSet()  # live mg_obs_alloc buffers of this process
-
-
-def is_balanced_buffer(tensor):
-    """True if `tensor` lies in memory obtained from mg_obs_alloc (HIP virtual memory: physical pieces mapped into a reserved
-    range).  Such memory has no IPC handle (hipIpcGetMemHandle needs a hipMalloc allocation): memory_gym_amd.dist.PeerObsBuffer
-    refuses to export it; collectives (RCCL) and peer access work on it like on any device memory."""
-    p = tensor.data_ptr()
-    return any(o.ptr is not None and o.ptr <= p < o.ptr + o.nbytes for o in _BALANCED)
-
-
-class _ObsMemory:
-    """Owner of a device buffer obtained from mg_obs_alloc; tensors made from it keep it alive (CUDA array interface)."""
-
-    def __init__(self, ptr, shape, typestr, info):
-        self.ptr, self.info = ptr, info
-        self.nbytes = int(np.prod(shape))
-        _BALANCED.add(self)
-        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (ptr, False), "version": 2, "strides": None}
-
-    def __del__(self):
-        try:
-            if self.ptr:
-                _native.LIB.mg_obs_free(C.c_void_p(self.ptr))
-                self.ptr = None
-        except Exception:
-            pass
-
-
-def alloc_obs_buffer(shape, dtype, device, search_budget_bytes=None, frame_bytes=None):
-    """A tensor of `shape` / `dtype` on `device` whose memory comes from mg_obs_alloc_for (pieces from two HBM zones, see
-    include/memgym.h); returns (tensor, info dict).  The memory is released when the last tensor viewing it goes away.
-    `frame_bytes`: bytes of one instance's observation (default: what `shape[1:]` and `dtype` say) -- the pieces are dealt to the zones
-    by the raster launch's windows of 14,336 observations.
-    MEMGYM_OBS_SEARCH_MS bounds the search in time (default 1,500 ms), MEMGYM_OBS_SEARCH_GB its transient filler allocations
-    (default: half of the free memory, at
-    most 128 GiB -- VRAM that other processes on the GPU cannot have for the few milliseconds the search lasts; 0 = do not
-    search).  The buffer is accessible from this device and from every device with peer access to it."""
-    device = torch.device(device)
-    elem = torch.empty((), dtype=dtype).element_size()
-    nbytes = int(np.prod(shape)) * elem
-    if search_budget_bytes is None:
-        e = os.environ.get("MEMGYM_OBS_SEARCH_GB")
-        search_budget_bytes = _native.MG_OBS_SEARCH_DEFAULT if e is None else int(float(e) * (1 << 30))
-    ms = os.environ.get("MEMGYM_OBS_SEARCH_MS")  # time bound of the search (default 1,500 ms; include/memgym.h: mg_obs_set_search_ms)
-    if ms is not None and hasattr(_native.LIB, "mg_obs_set_search_ms"):
-        _native.check(_native.LIB.mg_obs_set_search_ms(float(ms)), "mg_obs_set_search_ms")
-    ptr, info = C.c_void_p(), _native.ObsAllocInfo()
-    with torch.cuda.device(device):
-        torch.cuda.current_stream().synchronize()
-        if frame_bytes is None:
-            frame_bytes = int(np.prod(shape[1:])) * elem if len(shape) > 1 else 84 * 84 * 3
-        lab = os.environ.get("MEMGYM_OBS_FRAME_BYTES")  # tools/fmt_ab.sh: the piece order of another format (A/B of the window rule)
-        if lab:
-            frame_bytes = int(lab)
-        if hasattr(_native.LIB, "mg_obs_alloc_for"):
-            _native.check(_native.LIB.mg_obs_alloc_for(device.index or 0, nbytes, C.c_size_t(frame_bytes), C.c_size_t(search_budget_bytes), C.byref(ptr),
-                                                       C.byref(info)), "mg_obs_alloc_for")
-        else:  # (a build of an earlier round, loaded through MEMGYM_HIP_LIB by tools/)
-            _native.check(_native.LIB.mg_obs_alloc(device.index or 0, nbytes, C.c_size_t(search_budget_bytes), C.byref(ptr), C.byref(info)), "mg_obs_alloc")
-    # bfloat16 has no array-interface typestr: expose the bytes and view them
-    owner = _ObsMemory(ptr.value, (nbytes,), "|u1", {k: getattr(info, k) for k, _ in info._fields_})
-    t = torch.as_tensor(owner, device=device).view(dtype).view(tuple(shape))
-    return t, owner.info
-
-
-class InstanceSnapshot:
-    """What VecMemoryGym.save_instances returns: `records`, a uint8 tensor [k, instance_bytes] on the handle's device (record j = the j-th saved
-    instance; the layout of a record is private), `layout`, the value of mg_instance_layout when it was taken (unique to the handle, new after every
-    rebuild of its geometry: load_instances refuses a snapshot whose layout is not the handle's current one), and `set_of`, the saved instances'
-    option-set indices (int32 [k]) or None where the handle had one option set."""
-    __slots__ = ("records", "layout", "set_of")
-
-    def __init__(self, records, layout, set_of=None):
-        self.records, self.layout, self.set_of = records, int(layout), set_of
-
-    @property
-    def count(self):
-        return int(self.records.shape[0])
-
-
-def _instance_index(what, name, t, device=None):
-    """An index argument of save_instances / load_instances / copy_instances -> a contiguous int32 tensor [m] (on `device` if given).  Integer
-    tensors, arrays and lists are taken; anything else, and anything that is not one-dimensional, is a ValueError."""
-    if not isinstance(t, torch.Tensor):
-        a = np.asarray(t)
-        if a.dtype.kind not in "iu":
-            raise ValueError("%s: %s must hold integers, got dtype %s" % (what, name, a.dtype))
-        t = torch.as_tensor(a.astype(np.int64))
-    if t.dtype not in (torch.int32, torch.int64):
-        raise ValueError("%s: %s must be an int32 or int64 tensor, got %s" % (what, name, t.dtype))
-    if t.dim() != 1:
-        raise ValueError("%s: %s must have one dimension, got shape %s" % (what, name, tuple(t.shape)))
-    t = t.to(dtype=torch.int32) if device is None else t.to(device=device, dtype=torch.int32)
-    return t.contiguous()
-
-
-def check_instance_load(snap, layout, instance_bytes, num_envs, idx=None, rec=None, device=None):
-    """The argument checks of load_instances, which need no handle: -> (idx, rec) as int32 tensors or None.  ValueError for a snapshot of another
-    handle or of an earlier geometry (`layout`), records of the wrong width, index tensors of the wrong dtype or length."""
-    what = "load_instances"
-    if not isinstance(snap, InstanceSnapshot):
-        raise ValueError("%s: need the InstanceSnapshot save_instances returned" % what)
-    if snap.layout != int(layout):
-        raise ValueError("%s: the snapshot (layout 0x%x) was taken from another handle, or before this handle's geometry was rebuilt (layout 0x%x): "
-                         "records are valid for the handle and the geometry they were saved under" % (what, snap.layout, int(layout)))
-    r = snap.records
-    if not (isinstance(r, torch.Tensor) and r.dtype == torch.uint8 and r.dim() == 2 and r.shape[1] == int(instance_bytes) and r.is_contiguous()):
-        raise ValueError("%s: snapshot.records must be a contiguous uint8 tensor [k, %d]" % (what, int(instance_bytes)))
-    if idx is not None:
-        idx = _instance_index(what, "idx", idx, device)
-    if rec is not None:
-        rec = _instance_index(what, "rec", rec, device)
-    m = num_envs if idx is None else idx.numel()
-    if rec is not None and rec.numel() != m:
-        raise ValueError("%s: rec must have one entry per loaded instance (%d), got %d" % (what, m, rec.numel()))
-    if rec is None and m > snap.count:
-        raise ValueError("%s: %d instances named, the snapshot holds %d records (pass rec= to load a record into several instances)" % (what, m, snap.count))
-    if snap.set_of is not None and tuple(snap.set_of.shape) != (snap.count,):
-        raise ValueError("%s: snapshot.set_of must have one entry per record" % what)
-    return idx, rec
-
-
-def check_instance_save(instance_bytes, num_envs, idx=None, out=None, device=None):
-    """The argument checks of save_instances, which need no handle: -> (idx as an int32 tensor or None, number of records)."""
-    what = "save_instances"
-    if idx is not None:
-        idx = _instance_index(what, "idx", idx, device)
-    k = num_envs if idx is None else idx.numel()
-    if out is not None:
-        if not isinstance(out, InstanceSnapshot):
-            raise ValueError("%s: out must be an InstanceSnapshot" % what)
-        r = out.records
-        if not (isinstance(r, torch.Tensor) and r.dtype == torch.uint8 and tuple(r.shape) == (k, int(instance_bytes)) and r.is_contiguous()):
-            raise ValueError("%s: out.records must be a contiguous uint8 tensor [%d, %d]" % (what, k, int(instance_bytes)))
-    return idx, k
-
-
-class FrameRecords:
-    """What VecMemoryGym.save_frames returns: `records`, a uint8 tensor [..., frame_record_bytes] on the handle's device (one row = the frame descriptor
-    of one instance at one moment: 16 / 64 / 128 bytes, its layout private), and `layout`, the value of mg_frame_layout when it was taken (unique to the
-    handle, new whenever a stored descriptor would draw differently: draw_frames refuses records whose layout is not the handle's current one).  A
-    trainer that fills a [T, N, bytes] store step by step (save_frames(out=store[t])) wraps the whole store: FrameRecords(store, env.frame_layout())."""
-    __slots__ = ("records", "layout")
-
-    def __init__(self, records, layout):
-        self.records, self.layout = records, int(layout)
-
-    @property
-    def count(self):
-        return int(self.records.numel() // self.records.shape[-1])
-
-
-class DebugFrameRecords(FrameRecords):
-    """What VecMemoryGym.save_debug_frames returns: FrameRecords whose rows are DEBUG-VIEW descriptors (the same widths, another content: what
-    render_debug() draws from, include/memgym.h mg_save_debug_frames).  draw_debug_frames draws them; draw_frames refuses them."""
-    __slots__ = ()
-
-
-def _distinct_host_index(what, idx):
-    """idx as the caller gave it, where the host can see it (a list, an array, a CPU tensor): ValueError if an instance is named twice.  A device tensor
-    is not looked at (no synchronisation): there a repeated index is the caller's to avoid (include/memgym.h)."""
-    if idx is None or (isinstance(idx, torch.Tensor) and idx.device.type != "cpu"):
-        return
-    a = np.asarray(idx.numpy() if isinstance(idx, torch.Tensor) else idx)
-    if a.dtype.kind in "iu" and a.ndim == 1:
-        named = a[a >= 0]
-        if np.unique(named).size != named.size:
-            raise ValueError("%s: idx names an instance more than once (entries must be distinct; negative entries are padding)" % what)
-
-
-def _frame_rows(what, name, t, record_bytes):
-    """A tensor of frame records -> its view [n, record_bytes]; ValueError unless it is a contiguous uint8 tensor whose last dimension is one record."""
-    if not (isinstance(t, torch.Tensor) and t.dtype == torch.uint8 and t.dim() >= 2 and t.shape[-1] == int(record_bytes) and t.is_contiguous()):
-        raise ValueError("%s: %s must be a contiguous uint8 tensor [..., %d]" % (what, name, int(record_bytes)))
-    return t.view(-1, int(record_bytes))
-
-
-def check_frame_save(record_bytes, num_envs, idx=None, out=None, device=None):
-    """The argument checks of save_frames, which need no handle: -> (idx as an int32 tensor or None, number of records, out's records as [k, bytes] or
-    None).  out: a FrameRecords or a plain uint8 tensor [k, record_bytes] -- e.g. the row block store[t] of a [T, N, bytes] store -- contiguous."""
-    what = "save_frames"
-    if idx is not None:
-        idx = _instance_index(what, "idx", idx, device)
-    k = num_envs if idx is None else idx.numel()
-    rows = None
-    if out is not None:
-        rows = _frame_rows(what, "out", out.records if isinstance(out, FrameRecords) else out, record_bytes)
-        if rows.shape[0] != k:
-            raise ValueError("%s: out holds %d records, the call saves %d" % (what, rows.shape[0], k))
-    return idx, k, rows
-
-
-def check_frame_draw(records, layout, record_bytes, pick=None, out=None, obs_format="u8_xyc", device=None):
-    """The argument checks of draw_frames, which need no handle: -> (records as [n, bytes], pick as an int32 tensor or None, count, (dtype, shape) of
-    one row).  ValueError for records of another handle or an earlier layout (FrameRecords only: a plain tensor carries none), of the wrong dtype /
-    width / stride, a pick that is no one-dimensional integer tensor, more rows than records without a pick, an unknown format, an `out` of the wrong
-    shape / dtype or one that is not contiguous."""
-    what = "draw_frames"
-    if isinstance(records, DebugFrameRecords):
-        raise ValueError("%s: these are debug-view records (save_debug_frames): draw_debug_frames draws them" % what)
-    if isinstance(records, FrameRecords):
-        if records.layout != int(layout):
-            raise ValueError("%s: the records (layout 0x%x) were saved from another handle, or before something changed that they would draw differently "
-                             "(layout 0x%x now): frame records are valid for the handle and the atlas they were saved under" % (what, records.layout, int(layout)))
-        records = records.records
-    rows = _frame_rows(what, "records", records, record_bytes)
-    if obs_format not in VecMemoryGym.OBS_FORMATS:
-        raise ValueError("%s: obs_format must be one of %s" % (what, sorted(VecMemoryGym.OBS_FORMATS)))
-    _, dt, shape = VecMemoryGym.OBS_FORMATS[obs_format]
-    if pick is not None:
-        pick = _instance_index(what, "pick", pick, device)
-    count = rows.shape[0] if pick is None else pick.numel()
-    if count > 0 and rows.shape[0] < 1:
-        raise ValueError("%s: no records to draw from" % what)
-    if out is not None and not (isinstance(out, torch.Tensor) and out.dtype == dt and tuple(out.shape) == (count,) + shape and out.is_contiguous()):
-        raise ValueError("%s: out must be a contiguous %s tensor of shape %s" % (what, dt, (count,) + shape))
-    return rows, pick, count, (dt, shape)
-
-
-MAX_DRAW_RECORDS = (1 << 31) - 1  # include/memgym.h: mg_draw_frames refuses n_records > INT32_MAX
-
-
-class RolloutTrace:
-    """What VecMemoryGym.new_rollout returns and advance_traced(ro) / play(trace=ro) fill (include/memgym.h: mg_advance_traced / mg_play_traced): K steps
-    of N instances kept as
-        frames   uint8   [K + 1, N, frame_record_bytes]   the frame records, and `frame_layout`, the value of mg_frame_layout they were filled under
-        actions  int32   [K, N] or [K, N, 2]              the action played at step t (advance only; play leaves it alone: the tape is the caller's)
-        labels   int32   same shape, or None              the teacher's answer at eps = 0 in the state the action was played in (new_rollout(labels=True))
-        reward   float32 [K, N]                           done   bool [K, N]
-    (any of them may be None: not kept -- e.g. RolloutTrace(frames, 0, None, None, None, None) keeps the frame records alone)
-    in the gymnasium convention: frames[t] is the observation actions[t] / labels[t] belong to, frames[t + 1] the result of step t (the new episode's
-    first frame where the step auto-reset the instance; for an instance that did not step, the frame it keeps).  draw() turns picks of it into frames."""
-    __slots__ = ("frames", "frame_layout", "actions", "labels", "reward", "done")
-
-    def __init__(self, frames, frame_layout, actions, labels, reward, done):
-        self.frames, self.frame_layout, self.actions, self.labels, self.reward, self.done = frames, int(frame_layout), actions, labels, reward, done
-
-    @property
-    def steps(self):
-        return int(self.frames.shape[0]) - 1 if self.frames is not None else int(next(t for t in (self.reward, self.done, self.actions) if t is not None).shape[0])
-
-    @property
-    def num_envs(self):
-        return int(next(t for t in (self.frames, self.reward, self.done, self.actions) if t is not None).shape[1])
-
-    def draw(self, env, t, i, out=None, obs_format=None):
-        """Frames of the trace: row j of the result is frames[t[j], i[j]] drawn in `obs_format` (default: the handle's) -- draw_frames over the flattened
-        store with pick = t * N + i.  t, i: integers, or integer tensors / lists of one length (t in 0 .. K, i in 0 .. N - 1).  ValueError, before anything
-        is launched: a trace filled under another handle or an earlier frame layout, t and i of different lengths, a store of more records than
-        mg_draw_frames accepts, and whatever draw_frames refuses about `out`."""
-        what = "RolloutTrace.draw"
-        if not (isinstance(self.frames, torch.Tensor) and self.frames.dim() == 3):
-            raise ValueError("%s: frames must be a uint8 tensor [K + 1, N, frame_record_bytes] (this trace keeps no frames?)" % what)
-        n = int(self.frames.shape[1])
-        if int(self.frames.shape[0]) * n > MAX_DRAW_RECORDS:
-            raise ValueError("%s: the store holds %d x %d records, draw_frames takes at most %d: draw from slices of `frames`"
-                             % (what, int(self.frames.shape[0]), n, MAX_DRAW_RECORDS))
-        dev = self.frames.device
-        t, i = (_instance_index(what, nm, [v] if isinstance(v, (int, np.integer)) else v, dev) for nm, v in (("t", t), ("i", i)))
-        if t.numel() != i.numel():
-            raise ValueError("%s: t and i must have one length, got %d and %d" % (what, t.numel(), i.numel()))
-        return env.draw_frames(FrameRecords(self.frames, self.frame_layout), pick=t * n + i, out=out, obs_format=obs_format)
-
-
-def check_rollout_trace(ro, steps, num_envs, action_dim, record_bytes, teacher, device=None):
-    """The argument checks of advance_traced(ro) / play(trace=ro), which need no handle: ValueError unless `ro` is a RolloutTrace whose tensors have the
-    shapes and dtypes of RolloutTrace's docstring for K = steps and N = num_envs, are contiguous, lie on `device` (if given) and are aligned for the
-    launches' vector stores (frames to 16 bytes, actions / labels to 8).  teacher=False (play): actions and labels are not looked at."""
-    what = "advance_traced" if teacher else "play(trace=...)"
-    if not isinstance(ro, RolloutTrace):
-        raise ValueError("%s: need the RolloutTrace new_rollout returned" % what)
-    K, N = int(steps), int(num_envs)
-    acts = (K, N) if action_dim == 1 else (K, N, 2)
-    want = [("frames", ro.frames, torch.uint8, (K + 1, N, int(record_bytes)), 16), ("reward", ro.reward, torch.float32, (K, N), 4), ("done", ro.done, torch.bool, (K, N), 1)]
-    if teacher:
-        want.append(("actions", ro.actions, torch.int32, acts, 8))
-        if ro.labels is not None:
-            want.append(("labels", ro.labels, torch.int32, acts, 8))
-    for name, t, dt, shape, align in want:
-        if t is None:  # not kept (include/memgym.h: every array may be NULL)
-            continue
-        if not (isinstance(t, torch.Tensor) and t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous()):
-            raise ValueError("%s: trace.%s must be a contiguous %s tensor of shape %s (a trace of %d steps of %d instances), got %s"
-                             % (what, name, dt, shape, K, N, "%s %s" % (t.dtype, tuple(t.shape)) if isinstance(t, torch.Tensor) else type(t).__name__))
-        if device is not None and t.device != device:
-            raise ValueError("%s: trace.%s is on %s, the handle on %s" % (what, name, t.device, device))
-        if t.data_ptr() % align:
-            raise ValueError("%s: trace.%s must be %d-byte aligned" % (what, name, align))
-
-
-MAX_PICK = (1 << 31) - 1  # include/memgym.h: a pick is an int32 -- mg_split_episodes refuses (steps + 1) * num_envs beyond it
-
-
-def check_split_episodes(done, length, num_envs, steps=None, starts=None, capacity=None, device=None):
-    """The argument checks of split_episodes, which need no handle: -> (done as a uint8 view [K, N], K, length, steps as an int32 tensor [N] or None,
-    starts as a uint8 view [N] or None, capacity as an int or None).  ValueError for a `done` that is no contiguous bool / uint8 tensor [K, N] with
-    K >= 1 and N = num_envs, a length below 1, (K + 1) * N beyond an int32, `steps` that is no int32 / int64 tensor [N], `starts` that is no contiguous
-    bool / uint8 tensor [N], a negative capacity, and anything that does not lie on `device` (if given)."""
-    what = "split_episodes"
-    if not (isinstance(done, torch.Tensor) and done.dtype in (torch.bool, torch.uint8) and done.dim() == 2):
-        raise ValueError("%s: done must be a contiguous bool or uint8 tensor [K, N]" % what)
-    K, N = int(done.shape[0]), int(done.shape[1])
-    if N != int(num_envs) or K < 1:
-        raise ValueError("%s: done is %s, need [K >= 1, %d] (the handle's instances)" % (what, tuple(done.shape), int(num_envs)))
-    if (K + 1) * N > MAX_PICK:
-        raise ValueError("%s: (K + 1) * N = %d does not fit the int32 of a pick: split slices of the rollout" % (what, (K + 1) * N))
-    if not done.is_contiguous():
-        raise ValueError("%s: done must be a contiguous bool or uint8 tensor [K, N]" % what)
-    if isinstance(length, bool) or not isinstance(length, (int, np.integer)) or length < 1 or length > MAX_PICK:
-        raise ValueError("%s: length must be an integer >= 1, got %r" % (what, length))
-    if device is not None and done.device != device:
-        raise ValueError("%s: done is on %s, the handle on %s" % (what, done.device, device))
-    if steps is not None:
-        if not (isinstance(steps, torch.Tensor) and steps.dtype in (torch.int32, torch.int64) and tuple(steps.shape) == (N,)):
-            raise ValueError("%s: steps must be an int32 or int64 tensor [%d] (e.g. what play() returned as steps_played)" % (what, N))
-        if device is not None and steps.device != device:
-            raise ValueError("%s: steps is on %s, the handle on %s" % (what, steps.device, device))
-        steps = steps.to(torch.int32).contiguous()
-    if starts is not None:
-        if not (isinstance(starts, torch.Tensor) and starts.dtype in (torch.bool, torch.uint8) and tuple(starts.shape) == (N,) and starts.is_contiguous()):
-            raise ValueError("%s: starts must be a contiguous bool or uint8 tensor [%d]" % (what, N))
-        if device is not None and starts.device != device:
-            raise ValueError("%s: starts is on %s, the handle on %s" % (what, starts.device, device))
-        starts = starts.view(torch.uint8)
-    if capacity is not None:
-        if isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer)) or capacity < 0 or capacity > MAX_PICK:
-            raise ValueError("%s: capacity must be an integer >= 0, got %r" % (what, capacity))
-        capacity = int(capacity)
-    return done.view(torch.uint8), K, int(length), steps, starts, capacity
-
-
-class EpisodeSequences:
-    """What VecMemoryGym.split_episodes returns (include/memgym.h: mg_split_episodes): a rollout of `steps` steps of `num_envs` instances cut into
-    episodes at done and chopped into sequences of at most `length` steps.
-        table    int32 [capacity, 4]   one row per sequence: instance, t0, len, flags (1: starts an episode, 2: ends with its episode's done), ordered
-                                       by (instance, t0); rows from the count on are untouched
-        count    int32 [1]             the true number of sequences, on the device (it may exceed the capacity: the table then holds the first `capacity`)
-    len(seqs) reads the count (a synchronisation); picks() and gather() do not."""
-    __slots__ = ("table", "count", "length", "steps", "num_envs", "_env")
-
-    def __init__(self, table, count, length, steps, num_envs, env=None):
-        self.table, self.count, self.length, self.steps, self.num_envs, self._env = table, count, int(length), int(steps), int(num_envs), env
-
-    @property
-    def capacity(self):
-        return int(self.table.shape[0])
-
-    def __len__(self):
-        s = int(self.count.item())
-        if s > self.capacity:
-            raise ValueError("EpisodeSequences: the rollout has %d sequences, the table holds %d: split again with capacity >= %d" % (s, self.capacity, s))
-        return s
-
-    def picks(self, sel=None, m=None):
-        """-> (pick int32 [M, L], mask bool [M, L]) (include/memgym.h: mg_sequence_picks): row j belongs to sequence sel[j] (sel=None: sequence j,
-        M = m, default len(self) -- which synchronises; m = capacity does not, rows beyond the count are padding).  pick[j, l] = (t0 + l) * N + instance
-        for l < len, -1 behind it: an index into the flattened [K + 1, N] frame store of the trace and into its flattened [K, N] action / label /
-        reward / done rows.  sel: an integer tensor / list [M]; an entry < 0 gives a padding row, an entry at or beyond the number of sequences the
-        table holds a padding row and error bit 512.  One launch on the current stream."""
-        what = "EpisodeSequences.picks"
-        env = self._env
-        if env is None:
-            raise ValueError("%s: these sequences belong to no handle" % what)
-        if sel is not None:
-            if m is not None:
-                raise ValueError("%s: give sel or m, not both" % what)
-            sel = _instance_index(what, "sel", sel, env.device)
-            M = sel.numel()
-        else:
-            M = len(self) if m is None else m
-            if isinstance(M, bool) or not isinstance(M, (int, np.integer)) or M < 0:
-                raise ValueError("%s: m must be an integer >= 0, got %r" % (what, m))
-            M = int(M)
-        if M * self.length > MAX_PICK:
-            raise ValueError("%s: %d rows of %d picks do not fit one call" % (what, M, self.length))
-        pick = torch.empty((M, self.length), dtype=torch.int32, device=env.device)
-        mask = torch.empty((M, self.length), dtype=torch.bool, device=env.device)
-        if M:
-            with torch.cuda.device(env.device):
-                _native.check(_native.LIB.mg_sequence_picks(env._h, self.table.data_ptr() if self.capacity else None, self.count.data_ptr(), self.capacity,
-                                                            None if sel is None else sel.data_ptr(), M, self.length, pick.data_ptr(), mask.data_ptr(),
-                                                            env._stream()), "mg_sequence_picks")
-        return pick, mask
-
-    def gather(self, x, sel=None):
-        """x [K, N, ...] (actions, labels, reward, done) or [K + 1, N, ...] (per-frame data) -> [M, L, ...], zero at the pads: x flattened over its
-        first two dimensions, indexed with picks(sel)."""
-        if not (isinstance(x, torch.Tensor) and x.dim() >= 2 and int(x.shape[0]) in (self.steps, self.steps + 1) and int(x.shape[1]) == self.num_envs):
-            raise ValueError("EpisodeSequences.gather: x must be a tensor [%d or %d, %d, ...]" % (self.steps, self.steps + 1, self.num_envs))
-        pick, mask = self.picks(sel)
-        rows = x.reshape((-1,) + tuple(x.shape[2:]))[pick.clamp(min=0).long()]
-        return torch.where(mask.reshape(mask.shape + (1,) * (x.dim() - 2)), rows, torch.zeros_like(rows))
-
-
-def _plain_int(what, name, v, least):
-    """v as an int; ValueError unless it is an integer (no bool, no float) in least .. MAX_PICK"""
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < least or v > MAX_PICK:
-        raise ValueError("%s: %s must be an integer >= %d, got %r" % (what, name, least, v))
-    return int(v)
-
-
-def _per_instance_int32(what, name, t, n, device):
-    """an int32 / int64 tensor [n] (on `device` if given) -> a contiguous int32 tensor; None stays None"""
-    if t is None:
-        return None
-    if not (isinstance(t, torch.Tensor) and t.dtype in (torch.int32, torch.int64) and tuple(t.shape) == (n,)):
-        raise ValueError("%s: %s must be an int32 or int64 tensor [%d]" % (what, name, n))
-    if device is not None and t.device != device:
-        raise ValueError("%s: %s is on %s, the handle on %s" % (what, name, t.device, device))
-    return t.to(torch.int32).contiguous()
-
-
-def check_episode_windows(done, window, num_envs, lag=0, back=0, steps=None, pos0=None, device=None):
-    """The argument checks of episode_positions / episode_windows, which need no handle: -> (done as a uint8 view [K, N], K, window, lag, back, steps as
-    an int32 tensor [N] or None, pos0 as an int32 tensor [N] or None).  ValueError for a `done` that is no contiguous bool / uint8 tensor [K, N] with
-    K >= 1 and N = num_envs, a window below 1, a negative lag or back, (back + K + 1) * N beyond an int32, `steps` / `pos0` that are no int32 / int64
-    tensors [N], and anything that does not lie on `device` (if given)."""
-    what = "episode_windows"
-    if not (isinstance(done, torch.Tensor) and done.dtype in (torch.bool, torch.uint8) and done.dim() == 2):
-        raise ValueError("%s: done must be a contiguous bool or uint8 tensor [K, N]" % what)
-    K, N = int(done.shape[0]), int(done.shape[1])
-    if N != int(num_envs) or K < 1:
-        raise ValueError("%s: done is %s, need [K >= 1, %d] (the handle's instances)" % (what, tuple(done.shape), int(num_envs)))
-    window, lag, back = _plain_int(what, "window", window, 1), _plain_int(what, "lag", lag, 0), _plain_int(what, "back", back, 0)
-    if (back + K + 1) * N > MAX_PICK:
-        raise ValueError("%s: (back + K + 1) * N = %d does not fit the int32 of a pick: take slices of the rollout" % (what, (back + K + 1) * N))
-    if not done.is_contiguous():
-        raise ValueError("%s: done must be a contiguous bool or uint8 tensor [K, N]" % what)
-    if device is not None and done.device != device:
-        raise ValueError("%s: done is on %s, the handle on %s" % (what, done.device, device))
-    return (done.view(torch.uint8), K, window, lag, back, _per_instance_int32(what, "steps", steps, N, device),
-            _per_instance_int32(what, "pos0", pos0, N, device))
-
-
-def _pick_tensor(what, name, t, device=None):
-    """An index argument of any shape -> a contiguous int32 tensor of that shape (on `device` if given); integer tensors, arrays and lists are taken"""
-    if not isinstance(t, torch.Tensor):
-        a = np.asarray(t)
-        if a.dtype.kind not in "iu":
-            raise ValueError("%s: %s must hold integers, got dtype %s" % (what, name, a.dtype))
-        t = torch.as_tensor(a.astype(np.int64))
-    if t.dtype not in (torch.int32, torch.int64):
-        raise ValueError("%s: %s must be an int32 or int64 tensor, got %s" % (what, name, t.dtype))
-    t = t.to(dtype=torch.int32) if device is None else t.to(device=device, dtype=torch.int32)
-    return t.contiguous()
-
-
-def check_gather_rows(x, pick, out=None, device=None):
-    """The argument checks of gather_rows, which need no handle: -> (x, pick as a contiguous int32 tensor or None, the result's shape, bytes of a row).
-    ValueError for an `x` that is no contiguous tensor [R, ...] with rows of at least one byte, a pick that holds no integers, more rows than x has
-    without a pick, and an `out` of another shape / dtype / device than the result or one that is not contiguous."""
-    what = "gather_rows"
-    if not (isinstance(x, torch.Tensor) and x.dim() >= 1 and x.is_contiguous()):
-        raise ValueError("%s: x must be a contiguous tensor [R, ...]" % what)
-    row_bytes = int(np.prod(x.shape[1:], dtype=np.int64)) * x.element_size()
-    if row_bytes < 1:
-        raise ValueError("%s: a row of x %s holds no byte" % (what, tuple(x.shape)))
-    if int(x.shape[0]) > MAX_PICK:
-        raise ValueError("%s: x has %d rows, a pick is an int32" % (what, int(x.shape[0])))
-    if device is not None and x.device != device:
-        raise ValueError("%s: x is on %s, the handle on %s" % (what, x.device, device))
-    if pick is not None:
-        pick = _pick_tensor(what, "pick", pick, x.device)
-    shape = ((int(x.shape[0]),) if pick is None else tuple(pick.shape)) + tuple(x.shape[1:])
-    if (x.shape[0] if pick is None else pick.numel()) > MAX_PICK:
-        raise ValueError("%s: more than %d rows in one call" % (what, MAX_PICK))
-    if out is not None and not (isinstance(out, torch.Tensor) and out.dtype == x.dtype and tuple(out.shape) == shape and out.is_contiguous()
-                                and out.device == x.device):
-        raise ValueError("%s: out must be a contiguous %s tensor of shape %s on %s" % (what, x.dtype, shape, x.device))
-    return x, pick, shape, row_bytes
-
-
-class EpisodeWindows:
-    """What VecMemoryGym.episode_windows returns (include/memgym.h: mg_episode_positions / mg_window_picks): the sliding memory windows of a rollout of
-    `steps` steps of `num_envs` instances.
-        pos      int32 [K + 1, N]   the steps instance i's episode had already taken at store row t (mg_episode_positions)
-        window   W, the rows of a window;  lag: the window of sample (t, i) ends at row t - lag;  back: rows of the previous trace a window may reach into
-    The window of sample s = t * N + i holds the rows max(t - pos[t, i], t - lag - W + 1, -back) .. t - lag, oldest first, pads behind them.  `carry`
-    is the next call's pos0.  Nothing here synchronises."""
-    __slots__ = ("pos", "window", "lag", "back", "steps", "num_envs", "_env")
-
-    def __init__(self, pos, window, lag, back, steps, num_envs, env=None):
-        self.pos, self.window, self.lag, self.back, self.steps, self.num_envs, self._env = pos, int(window), int(lag), int(back), int(steps), int(num_envs), env
-
-    @property
-    def carry(self):
-        """row K of pos: the positions behind the rollout's last step -- the pos0 of the next rollout's episode_windows"""
-        return self.pos[self.steps]
-
-    def picks(self, sel=None, m=None):
-        """-> (pick int32 [M, W], mask bool [M, W], len int32 [M]) (include/memgym.h: mg_window_picks): row j belongs to sample sel[j] = t * N + i
-        (sel=None: sample j, M = m, default (K + 1) * N: every sample, the bootstrap row included).  pick[j, l] = (back + lo + l) * N + i for l < len,
-        -1 behind it: an index into a flattened [back + K + 1, N] store whose first `back` rows are the last `back` rows of the previous rollout.
-        sel: an integer tensor / list [M]; an entry < 0 gives a padding row, an entry at or beyond (K + 1) * N a padding row and error bit 512.  One
-        launch on the current stream."""
-        what = "EpisodeWindows.picks"
-        env = self._env
-        if env is None:
-            raise ValueError("%s: these windows belong to no handle" % what)
-        samples = (self.steps + 1) * self.num_envs
-        if sel is not None:
-            if m is not None:
-                raise ValueError("%s: give sel or m, not both" % what)
-            sel = _instance_index(what, "sel", sel, env.device)
-            M = sel.numel()
-        else:
-            M = samples if m is None else m
-            if isinstance(M, bool) or not isinstance(M, (int, np.integer)) or M < 0 or M > samples:
-                raise ValueError("%s: m must be an integer in 0 .. %d, got %r" % (what, samples, m))
-            M = int(M)
-        if M * self.window > MAX_PICK:
-            raise ValueError("%s: %d rows of %d picks do not fit one call" % (what, M, self.window))
-        pick = torch.empty((M, self.window), dtype=torch.int32, device=env.device)
-        mask = torch.empty((M, self.window), dtype=torch.bool, device=env.device)
-        length = torch.empty((M,), dtype=torch.int32, device=env.device)
-        if M:
-            with torch.cuda.device(env.device):
-                _native.check(_native.LIB.mg_window_picks(env._h, self.pos.data_ptr(), self.steps, None if sel is None else sel.data_ptr(), M, self.window,
-                                                          self.lag, self.back, pick.data_ptr(), mask.data_ptr(), length.data_ptr(), env._stream()),
-                              "mg_window_picks")
-        return pick, mask, length
-
-    def store(self, x, prefix=None):
-        """The store the picks index, [(back + rows of x) * N, ...]: cat(prefix, x) flattened over its first two dimensions.  x: [K, N, ...] (actions,
-        rewards: a pick of row K is then out of range) or [K + 1, N, ...] (per-frame data: hidden states, values).  prefix: [back, N, ...], the last
-        `back` rows of the previous rollout's x in front of its row K_prev; required when back > 0.  ValueError otherwise."""
-        what = "EpisodeWindows.gather"
-        if not (isinstance(x, torch.Tensor) and x.dim() >= 2 and int(x.shape[0]) in (self.steps, self.steps + 1) and int(x.shape[1]) == self.num_envs):
-            raise ValueError("%s: x must be a tensor [%d or %d, %d, ...]" % (what, self.steps, self.steps + 1, self.num_envs))
-        if self.back > 0:
-            if prefix is None:
-                raise ValueError("%s: back = %d: a prefix [%d, %d, ...] is required (the last rows of the previous rollout)" % (what, self.back, self.back, self.num_envs))
-            if not (isinstance(prefix, torch.Tensor) and prefix.dtype == x.dtype and prefix.device == x.device
-                    and tuple(prefix.shape) == (self.back, self.num_envs) + tuple(x.shape[2:])):
-                raise ValueError("%s: prefix must be a %s tensor of shape %s on %s" % (what, x.dtype, (self.back, self.num_envs) + tuple(x.shape[2:]), x.device))
-            x = torch.cat((prefix, x), 0)
-        elif prefix is not None and int(prefix.shape[0]) != 0:
-            raise ValueError("%s: back = 0: there is no room for a prefix" % what)
-        return x.contiguous().view((-1,) + tuple(x.shape[2:]))
-
-    def gather(self, x, sel=None, prefix=None):
-        """x [K, N, ...] or [K + 1, N, ...] -> [M, W, ...], zero rows at the pads: gather_rows on store(x, prefix), indexed with picks(sel).  One launch
-        for the picks and one for the rows (include/memgym.h: mg_gather_rows_padded), on the current stream."""
-        rows = self.store(x, prefix)
-        if self._env is None:
-            raise ValueError("EpisodeWindows.gather: these windows belong to no handle")
-        return self._env.gather_rows(rows, self.picks(sel)[0])
-
-
-def check_window_frames(frames, windows, record_bytes):
-    """The layout checks of draw_windows, which need no handle: -> a FrameRecords or uint8 tensor for draw_frames_padded.  With back == 0 `frames` may be
-    the RolloutTrace the windows were made from (its K and N are checked); with back > 0 it must be a FrameRecords / uint8 store of
-    [back + K + 1, N, record_bytes] rows that the caller assembled.  ValueError otherwise."""
-    what = "draw_windows"
-    if not isinstance(windows, EpisodeWindows):
-        raise ValueError("%s: windows must be the EpisodeWindows episode_windows returned" % what)
-    if isinstance(frames, RolloutTrace):
-        if windows.back > 0:
-            raise ValueError("%s: back = %d: a trace holds no rows of the previous rollout; pass a FrameRecords / uint8 store of [%d + %d + 1, %d, %d] rows"
-                             % (what, windows.back, windows.back, windows.steps, windows.num_envs, int(record_bytes)))
-        if not (isinstance(frames.frames, torch.Tensor) and frames.frames.dim() == 3):
-            raise ValueError("%s: the trace keeps no frames" % what)
-        if (frames.steps, frames.num_envs) != (windows.steps, windows.num_envs):
-            raise ValueError("%s: the trace holds %d steps of %d instances, the windows were made from %d steps of %d"
-                             % (what, frames.steps, frames.num_envs, windows.steps, windows.num_envs))
-        return FrameRecords(frames.frames, frames.frame_layout)
-    rec = frames.records if isinstance(frames, FrameRecords) else frames
-    want = (windows.back + windows.steps + 1, windows.num_envs, int(record_bytes))
-    if not (isinstance(rec, torch.Tensor) and rec.dtype == torch.uint8 and tuple(rec.shape) == want and rec.is_contiguous()):
-        raise ValueError("%s: frames must be a contiguous uint8 store of shape %s (back + K + 1 rows of N records)" % (what, want))
-    return frames
-
-
-class VecMemoryGym:
+class VecMemoryGym(RecordCalls):
     metadata ={"render_modes": ["rgb_array", "debug_rgb_array"], "render_fps": 25}
 
-    OBS_FORMATS = {"u8_xyc": (0, torch.uint8, (84, 84, 3)), "f32_chw": (1, torch.float32, (3, 84, 84)),
-                   "f16_chw": (2, torch.float16, (3, 84, 84)), "bf16_chw": (3, torch.bfloat16, (3, 84, 84)),
-                   "u8_chw": (4, torch.uint8, (3, 84, 84))}
+    OBS_FORMATS = OBS_FORMATS
     # "same_step": an instance that finishes is reset inside the call (gymnasium 0.29's vector convention); "disabled": autoreset = False, the caller
     # resets with a masked reset(); "next_step": gymnasium >= 1.0's AutoresetMode.NEXT_STEP (include/memgym.h: mg_step_next), see step()
     AUTORESET_MODES = ("same_step", "next_step", "disabled")
@@ -733,16 +166,15 @@ class VecMemoryGym:
                 break
             self.info_names.append(nm.decode())
         self.aux = [torch.zeros(N, dtype=torch.float32, device=dev) for _ in self.info_names]
-        self._info = _native.InfoBuffers()
-        self._info.struct_size = C.sizeof(_native.InfoBuffers)
+        self._info = _native.new_struct(_native.InfoBuffers)
         self._err = C.c_int(0)
         self._info.ep_reward_dev = self.ep_reward.data_ptr()
         self._info.ep_length_dev = self.ep_length.data_ptr()
         for k, t in enumerate(self.aux):
             self._info.aux_dev[k] = t.data_ptr()
-        self._info.final_obs_dev = self.final_obs.data_ptr() if self.final_obs is not None else None
+        self._info.final_obs_dev = ptr(self.final_obs)
         self._info.reward64_dev = self.reward64.data_ptr()
-        self._info.gt64_dev = self.gt64.data_ptr() if self.gt64 is not None else None
+        self._info.gt64_dev = ptr(self.gt64)
         # What happens when ONE instance reaches a capacity of this build (128 path segments, 128 fall-off cells, 512 commands, 16 live
         # spotlights; the reference's lists are unbounded).  The kernels end that instance's episode and raise a sticky error bit either
         # way.  "raise" (default): step() turns the bit into a RuntimeError -- nothing that differs from the reference goes unnoticed.
@@ -752,7 +184,7 @@ class VecMemoryGym:
             raise ValueError("on_capacity must be 'raise' or 'truncate'")
         self.on_capacity = on_capacity
         self.capacity_u8 = torch.zeros(N, dtype=torch.uint8, device=dev) if on_capacity == "truncate" else None
-        self._info.capacity_dev = self.capacity_u8.data_ptr() if self.capacity_u8 is not None else None
+        self._info.capacity_dev = ptr(self.capacity_u8)
         # final_frames=True: the same convention WITHOUT frames (include/memgym.h: mg_info_buffers.final_frames_dev) -- the frame an episode ended on is
         # kept as its frame record, 16 / 64 / 128 bytes, so step(render=False) stays legal; draw_frames(info["final_frames"], pick=...) draws the rows
         self.final_frames = None
@@ -853,8 +285,7 @@ class VecMemoryGym:
             if not free:
                 raise NotImplementedError("more than %d different option sets alive in one handle" % _native.MG_MAX_OPTION_SETS)
             k = free[0]
-            while len(self._set_params) <= k:
-                self._set_params.append({})
+            self._room_for_set(k)
             # EVERY key is sent (an empty `have`): the library then checks each geometry key against the handle's geometry and
             # refuses a set whose agent_scale / arena_size / ... differs from it -- also when the value asked for is the
             # reference's default and the handle's is not (diffing against the defaults sent nothing in that case and
@@ -866,9 +297,22 @@ class VecMemoryGym:
                 self._set_params[k] = {}  # half-written: never matched by a later reset, rewritten in full when it is reused
                 raise
         if self._set_of is None:
-            self._set_of = torch.zeros(self.num_envs, dtype=torch.int32, device=self.device)
-            _native.check(_native.LIB.mg_bind_option_sets(self._h, self._set_of.data_ptr()), "mg_bind_option_sets")
+            self._bind_set_index(True)
         self._set_of[mask.to(device=self.device, dtype=torch.bool)] = k
+
+    def _room_for_set(self, k):
+        """`_set_params` reaches option set k: the slots it lacks are empty sets"""
+        while len(self._set_params) <= k:
+            self._set_params.append({})
+
+    def _bind_set_index(self, on):
+        """The per-instance option-set index `_set_of` (include/memgym.h: mg_bind_option_sets): on -- a new one, everybody under set 0, is bound;
+        off -- it is unbound and forgotten, the handle is back in its one-set launch arrangement."""
+        if on:
+            self._set_of = torch.zeros(self.num_envs, dtype=torch.int32, device=self.device)
+        _native.check(_native.LIB.mg_bind_option_sets(self._h, self._set_of.data_ptr() if on else None), "mg_bind_option_sets")
+        if not on:
+            self._set_of = None
 
     def _apply_options(self, options):
         params = process_reset_params(self.env_id, options)
@@ -877,8 +321,7 @@ class VecMemoryGym:
             # a reset of every instance: all of them run under these options.  The per-instance index is unbound again, so the
             # handle is back in its one-set launch arrangement (one-launch mortar step, fused resets, lazy segments), and the other
             # sets are forgotten: their geometry entries may be stale now, a later masked reset writes the set it needs in full.
-            _native.check(_native.LIB.mg_bind_option_sets(self._h, None), "mg_bind_option_sets")
-            self._set_of = None
+            self._bind_set_index(False)
         del self._set_params[1:]
         self.reset_params = params
         if self.env_id in ("MortarMayhemB-Grid-v0", "MortarMayhemB-v0"):  # mortar_mayhem_b_grid.py:149-153
@@ -931,11 +374,8 @@ class VecMemoryGym:
                 _native.check(_native.LIB.mg_render(self._h, self.obs.data_ptr(), self._stream()), "mg_render")
             self._swapped = self._stale = False
             self._clear_pending()
-            _native.check(_native.LIB.mg_reset(self._h, None if s is None else s.data_ptr(),
-                                               None if m is None else m.data_ptr(), self.obs.data_ptr(),
-                                               self.gt.data_ptr() if self.gt_dim else None, self._stream()), "mg_reset")
-            if self.gt64 is not None:
-                _native.check(_native.LIB.mg_ground_truth64(self._h, self.gt64.data_ptr(), self._stream()), "mg_ground_truth64")
+            _native.check(_native.LIB.mg_reset(self._h, ptr(s), ptr(m), self.obs.data_ptr(), self._p_gt, self._stream()), "mg_reset")
+            self._refresh_gt64()
             self._seeded = True
         info = {"ground_truth": self.gt if self.gt64 is None else self.gt64} if self.gt_dim else {}
         return self._obs(), info
@@ -970,17 +410,10 @@ class VecMemoryGym:
             raise ValueError("step(render=False) on a handle with final_observation=True: terminal observations are frames")
         m = None
         if mask is not None:
-            m = mask if isinstance(mask, torch.Tensor) else torch.as_tensor(mask)
-            if m.numel() != self.num_envs or m.dim() != 1:
-                raise ValueError("step(mask=...): the mask must have shape [%d], got %s" % (self.num_envs, tuple(m.shape)))
-            if m.dtype == torch.bool and m.device == self.device and m.is_contiguous():
-                m = m.view(torch.uint8)  # (the same bytes: True is 1)
-            elif not (m.dtype == torch.uint8 and m.device == self.device and m.is_contiguous()):
-                m = (m != 0).to(device=self.device, dtype=torch.uint8).contiguous()
+            m = self._mask_u8("step", mask)
         a = actions
         if not (isinstance(a, torch.Tensor) and a.dtype == torch.int32 and a.device == self.device and a.is_contiguous()):
-            a = a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a))
-            a = a.to(device=self.device, dtype=torch.int32).contiguous()
+            a = self._to_actions(a)
         assert a.numel() == self._n_actions, "actions must have shape [N] or [N, 2]"
         if torch.cuda.current_device() != self.device.index:
             with torch.cuda.device(self.device):
@@ -1007,6 +440,39 @@ class VecMemoryGym:
         """autoreset_mode="next_step": no instance is restarted by the next step()."""
         if self._next_step:
             self.done_u8.zero_()
+
+    def _mask_u8(self, what, mask):
+        """The mask of step(mask=...) / play(mask=...) -> a contiguous uint8 tensor [N] on the handle's device; ValueError for another shape."""
+        m = mask if isinstance(mask, torch.Tensor) else torch.as_tensor(mask)
+        if m.numel() != self.num_envs or m.dim() != 1:
+            raise ValueError("%s(mask=...): the mask must have shape [%d], got %s" % (what, self.num_envs, tuple(m.shape)))
+        if m.dtype == torch.bool and m.device == self.device and m.is_contiguous():
+            return m.view(torch.uint8)  # (the same bytes: True is 1)
+        if not (m.dtype == torch.uint8 and m.device == self.device and m.is_contiguous()):
+            m = (m != 0).to(device=self.device, dtype=torch.uint8).contiguous()
+        return m
+
+    def _to_actions(self, a):
+        """actions that are not yet a contiguous int32 tensor on the handle's device (step() and play() ask that themselves) -> one"""
+        a = a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a))
+        return a.to(device=self.device, dtype=torch.int32).contiguous()
+
+    def _refresh_gt64(self):
+        """ground_truth64=True: the float64 ground truth follows the states as they stand (one small launch)"""
+        if self.gt64 is not None:
+            _native.check(_native.LIB.mg_ground_truth64(self._h, self.gt64.data_ptr(), self._stream()), "mg_ground_truth64")
+
+    def _after_steps(self):
+        """The end of advance() / play(): `obs` is stale, and a device error bit raised so far is reported (step() does the same look inline)."""
+        self._stale = True
+        _native.LIB.mg_peek_errors(self._h, self._p_err)  # host-mapped word: no synchronisation
+        if self._err.value & ~self._tolerated:
+            self.check_errors()
+
+    def _teacher_args(self, eps, seed, step):
+        """(eps, seed, step) as the library takes them: a double and two 64-bit words; step=None is the handle's call counter"""
+        mask = (1 << 64) - 1
+        return float(eps), int(seed) & mask, int(self._expert_calls if step is None else step) & mask
 
     @property
     def autoreset_mode(self):
@@ -1056,9 +522,7 @@ class VecMemoryGym:
 
     def _trace_rows(self, ro, teacher):
         """frames[0] <- the current frames (save_frames); -> the mg_rollout_trace over frames[1:] and the other tensors of a checked RolloutTrace"""
-        ptr = lambda t: None if t is None else t.data_ptr()
-        rows = _native.RolloutTraceRows()
-        rows.struct_size = C.sizeof(_native.RolloutTraceRows)
+        rows = _native.new_struct(_native.RolloutTraceRows)
         if ro.frames is not None:
             self.save_frames(out=ro.frames[0])
             ro.frame_layout = self.frame_layout()
@@ -1102,35 +566,20 @@ class VecMemoryGym:
 
     def _advance(self, steps, eps, seed, step, render, stats, trace):
         if self._adv is None and stats:
-            N, dev = self.num_envs, self.device
-            t = {"reward": torch.zeros(N, dtype=torch.float64, device=dev), "episodes": torch.zeros(N, dtype=torch.int32, device=dev),
-                 "episode_reward": torch.zeros(N, dtype=torch.float64, device=dev), "episode_length": torch.zeros(N, dtype=torch.int64, device=dev)}
-            out = _native.AdvanceOut()
-            out.struct_size = C.sizeof(_native.AdvanceOut)
-            out.reward_sum_dev, out.episodes_dev = t["reward"].data_ptr(), t["episodes"].data_ptr()
-            out.ep_reward_sum_dev, out.ep_length_sum_dev = t["episode_reward"].data_ptr(), t["episode_length"].data_ptr()
-            for k, nm in enumerate(self.info_names):
-                t[nm] = torch.zeros(N, dtype=torch.float64, device=dev)
-                out.aux_sum_dev[k] = t[nm].data_ptr()
-            self._adv = (t, out)
-        mask = (1 << 64) - 1
+            self._adv = self._sum_tensors()
+        args = self._teacher_args(eps, seed, step)
+        out = C.byref(self._adv[1]) if stats else None
         with torch.cuda.device(self.device):
             self._clear_pending()
             if trace is not None:
                 rows = self._trace_rows(trace, True)
-                _native.check(_native.LIB.mg_advance_traced(self._h, steps, float(eps), int(seed) & mask, int(self._expert_calls if step is None else step) & mask,
-                                                            self._p_gt, C.byref(self._adv[1]) if stats else None, C.byref(rows), self._stream()), "mg_advance_traced")
+                _native.check(_native.LIB.mg_advance_traced(self._h, steps, *args, self._p_gt, out, C.byref(rows), self._stream()), "mg_advance_traced")
             else:
-                _native.check(_native.LIB.mg_advance(self._h, steps, float(eps), int(seed) & mask, int(self._expert_calls if step is None else step) & mask,
-                                                     self._p_gt, C.byref(self._adv[1]) if stats else None, self._stream()), "mg_advance")
-            if self.gt64 is not None:
-                _native.check(_native.LIB.mg_ground_truth64(self._h, self.gt64.data_ptr(), self._stream()), "mg_ground_truth64")
+                _native.check(_native.LIB.mg_advance(self._h, steps, *args, self._p_gt, out, self._stream()), "mg_advance")
+            self._refresh_gt64()
         if step is None:
             self._expert_calls += steps
-        self._stale = True
-        _native.LIB.mg_peek_errors(self._h, self._p_err)  # host-mapped word: no synchronisation
-        if self._err.value & ~self._tolerated:
-            self.check_errors()
+        self._after_steps()
         return (self.redraw() if render else None), (dict(self._adv[0]) if stats else None)
 
     def _sum_tensors(self):
@@ -1138,8 +587,7 @@ class VecMemoryGym:
         N, dev = self.num_envs, self.device
         t = {"reward": torch.zeros(N, dtype=torch.float64, device=dev), "episodes": torch.zeros(N, dtype=torch.int32, device=dev),
              "episode_reward": torch.zeros(N, dtype=torch.float64, device=dev), "episode_length": torch.zeros(N, dtype=torch.int64, device=dev)}
-        out = _native.AdvanceOut()
-        out.struct_size = C.sizeof(_native.AdvanceOut)
+        out = _native.new_struct(_native.AdvanceOut)
         out.reward_sum_dev, out.episodes_dev = t["reward"].data_ptr(), t["episodes"].data_ptr()
         out.ep_reward_sum_dev, out.ep_length_sum_dev = t["episode_reward"].data_ptr(), t["episode_length"].data_ptr()
         for k, nm in enumerate(self.info_names):
@@ -1171,21 +619,12 @@ class VecMemoryGym:
         anything is launched."""
         a = actions
         if not (isinstance(a, torch.Tensor) and a.dtype == torch.int32 and a.device == self.device and a.is_contiguous()):
-            a = a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a))
-            a = a.to(device=self.device, dtype=torch.int32).contiguous()
+            a = self._to_actions(a)
         want = (self.num_envs,) if self.action_dim == 1 else (self.num_envs, 2)
         if a.dim() != len(want) + 1 or tuple(a.shape[1:]) != want or a.shape[0] < 1:
             raise ValueError("play(actions): the tape must have shape [K, %s] with K >= 1, got %s" % (", ".join(str(x) for x in want), tuple(a.shape)))
         K = int(a.shape[0])
-        m = None
-        if mask is not None:
-            m = mask if isinstance(mask, torch.Tensor) else torch.as_tensor(mask)
-            if m.numel() != self.num_envs or m.dim() != 1:
-                raise ValueError("play(mask=...): the mask must have shape [%d], got %s" % (self.num_envs, tuple(m.shape)))
-            if m.dtype == torch.bool and m.device == self.device and m.is_contiguous():
-                m = m.view(torch.uint8)  # (the same bytes: True is 1)
-            elif not (m.dtype == torch.uint8 and m.device == self.device and m.is_contiguous()):
-                m = (m != 0).to(device=self.device, dtype=torch.uint8).contiguous()
+        m = None if mask is None else self._mask_u8("play", mask)
         ro = trace if not isinstance(trace, bool) and trace is not None else None
         if ro is not None:
             self._require_started("play(trace=...)")
@@ -1200,24 +639,18 @@ class VecMemoryGym:
             traces[K] = (torch.zeros((K, self.num_envs), dtype=torch.float32, device=self.device),
                          torch.zeros((K, self.num_envs), dtype=torch.uint8, device=self.device))
         rt, dt = traces[K] if trace else (None, None)
+        mode = _native.MG_PLAY_EPISODE if until_done else _native.MG_PLAY_THROUGH
+        steps_dev, out = (sums["steps"].data_ptr(), C.byref(out)) if stats else (None, None)
         with torch.cuda.device(self.device):
             self._clear_pending()
             if ro is not None:
                 rows = self._trace_rows(ro, False)
-                _native.check(_native.LIB.mg_play_traced(self._h, a.data_ptr(), K, _native.MG_PLAY_EPISODE if until_done else _native.MG_PLAY_THROUGH,
-                                                         None if m is None else m.data_ptr(), sums["steps"].data_ptr() if stats else None, self._p_gt,
-                                                         C.byref(out) if stats else None, C.byref(rows), self._stream()), "mg_play_traced")
+                _native.check(_native.LIB.mg_play_traced(self._h, a.data_ptr(), K, mode, ptr(m), steps_dev, self._p_gt, out, C.byref(rows), self._stream()),
+                              "mg_play_traced")
             else:
-                _native.check(_native.LIB.mg_play(self._h, a.data_ptr(), K, _native.MG_PLAY_EPISODE if until_done else _native.MG_PLAY_THROUGH,
-                                                  None if m is None else m.data_ptr(), None if rt is None else rt.data_ptr(),
-                                                  None if dt is None else dt.data_ptr(), sums["steps"].data_ptr() if stats else None, self._p_gt,
-                                                  C.byref(out) if stats else None, self._stream()), "mg_play")
-            if self.gt64 is not None:
-                _native.check(_native.LIB.mg_ground_truth64(self._h, self.gt64.data_ptr(), self._stream()), "mg_ground_truth64")
-        self._stale = True
-        _native.LIB.mg_peek_errors(self._h, self._p_err)  # host-mapped word: no synchronisation
-        if self._err.value & ~self._tolerated:
-            self.check_errors()
+                _native.check(_native.LIB.mg_play(self._h, a.data_ptr(), K, mode, ptr(m), ptr(rt), ptr(dt), steps_dev, self._p_gt, out, self._stream()), "mg_play")
+            self._refresh_gt64()
+        self._after_steps()
         st = dict(sums) if stats else ({} if trace else None)
         if trace:
             st["reward_trace"], st["done_trace"] = rt, dt.view(torch.bool)
@@ -1237,10 +670,8 @@ class VecMemoryGym:
             out = torch.empty(shape, dtype=torch.int32, device=self.device)
         elif not (isinstance(out, torch.Tensor) and out.dtype == torch.int32 and out.device == self.device and out.is_contiguous() and tuple(out.shape) == shape):
             raise ValueError("expert_actions: out must be a contiguous int32 tensor of shape %s on %s" % (shape, self.device))
-        mask = (1 << 64) - 1
         with torch.cuda.device(self.device):
-            _native.check(_native.LIB.mg_expert_actions(self._h, float(eps), int(seed) & mask, int(self._expert_calls if step is None else step) & mask,
-                                                        out.data_ptr(), self._stream()), "mg_expert_actions")
+            _native.check(_native.LIB.mg_expert_actions(self._h, *self._teacher_args(eps, seed, step), out.data_ptr(), self._stream()), "mg_expert_actions")
         self._expert_calls += 1
         return out
 
@@ -1266,10 +697,9 @@ class VecMemoryGym:
         nbytes = self.instance_bytes
         idx, k = check_instance_save(nbytes, self.num_envs, idx, out, self.device)
         records = out.records if out is not None else torch.empty((k, nbytes), dtype=torch.uint8, device=self.device)
-        if records.device != self.device or records.data_ptr() % 16:
-            raise ValueError("save_instances: out.records must be a 16-byte aligned tensor on %s" % (self.device,))
+        aligned_on("save_instances", "out.records", self.device, records)
         with torch.cuda.device(self.device):
-            _native.check(_native.LIB.mg_save_instances(self._h, None if idx is None else idx.data_ptr(), k, records.data_ptr(), self._stream()), "mg_save_instances")
+            _native.check(_native.LIB.mg_save_instances(self._h, ptr(idx), k, records.data_ptr(), self._stream()), "mg_save_instances")
             set_of = None
             if self._set_of is not None:  # the caller owns the set index (include/memgym.h): it travels beside the records
                 set_of = self._set_of.clone() if idx is None else self._set_of[idx.clamp(0, self.num_envs - 1).long()]
@@ -1277,260 +707,6 @@ class VecMemoryGym:
             out.layout, out.set_of = self.instance_layout, set_of
             return out
         return InstanceSnapshot(records, self.instance_layout, set_of)
-
-    # ------------------------------------------------------------------ frame records
-    @property
-    def frame_record_bytes(self):
-        return int(_native.LIB.mg_frame_record_bytes(self._h))
-
-    def frame_layout(self):
-        return int(_native.LIB.mg_frame_layout(self._h))
-
-    def save_frames(self, idx=None, out=None):
-        """Keep the CURRENT frames as their descriptors (include/memgym.h: mg_save_frames) -> FrameRecords over a uint8 tensor [k, frame_record_bytes]:
-        16 / 64 / 128 bytes per frame instead of 21,168 and more.  After step(render=False) the records hold the frames the step would have drawn.
-        idx: the instances, an integer tensor / list (None: all, in order); entries < 0 are skipped (their records keep their bytes).  out: a
-        FrameRecords or a uint8 tensor [k, frame_record_bytes] to write into -- a row block store[t] of a larger [T, N, bytes] store, so one store is
-        filled step by step.  One small launch on the current stream; nothing synchronises, nothing of the handle changes."""
-        self._require_started("save_frames")
-        nbytes = self.frame_record_bytes
-        idx, k, rows = check_frame_save(nbytes, self.num_envs, idx, out, self.device)
-        if rows is None:
-            out = rows = torch.empty((k, nbytes), dtype=torch.uint8, device=self.device)
-        if rows.device != self.device or rows.data_ptr() % 16:
-            raise ValueError("save_frames: out must be a 16-byte aligned tensor on %s" % (self.device,))
-        with torch.cuda.device(self.device):
-            _native.check(_native.LIB.mg_save_frames(self._h, None if idx is None else idx.data_ptr(), k, rows.data_ptr(), self._stream()), "mg_save_frames")
-        if isinstance(out, FrameRecords):
-            out.layout = self.frame_layout()
-            return out
-        return FrameRecords(out, self.frame_layout())
-
-    def draw_frames(self, records, pick=None, out=None, obs_format=None):
-        """Draw kept frames (include/memgym.h: mg_draw_frames): row j of the result is the frame of record pick[j] (pick=None: record j), in
-        `obs_format` (default: the handle's) -- bit for bit what `obs` showed when the record was saved, or what a handle of that format would have
-        shown.  records: a FrameRecords (its layout is checked: ValueError if stale, before anything is launched) or a plain uint8 tensor, viewed as
-        [n_records, frame_record_bytes].  pick: an integer tensor / list of any length, duplicates allowed; an entry outside the records leaves its row
-        untouched and raises error bit 512.  out: a contiguous tensor [count] + shape of the format to draw into (a network's input tensor).  One
-        raster launch on the current stream; nothing synchronises, nothing of the handle changes."""
-        self._require_started("draw_frames")
-        fmt = self.obs_format if obs_format is None else obs_format
-        rows, pick, count, (dt, shape) = check_frame_draw(records, self.frame_layout(), self.frame_record_bytes, pick, out, fmt, self.device)
-        if out is None:
-            out = torch.empty((count,) + shape, dtype=dt, device=self.device)
-        if rows.device != self.device or out.device != self.device or rows.data_ptr() % 16 or out.data_ptr() % 16:
-            raise ValueError("draw_frames: records and out must be 16-byte aligned tensors on %s" % (self.device,))
-        with torch.cuda.device(self.device):
-            _native.check(_native.LIB.mg_draw_frames(self._h, rows.data_ptr(), rows.shape[0], None if pick is None else pick.data_ptr(), count,
-                                                     self.OBS_FORMATS[fmt][0], out.data_ptr(), self._stream()), "mg_draw_frames")
-        return out
-
-    # ------------------------------------------------------------------ episode sequences
-    def split_episodes(self, done, length, steps=None, starts=None, capacity=None):
-        """Cut a rollout into episode sequences on the device (include/memgym.h: mg_split_episodes) -> EpisodeSequences.  done: a bool or uint8 tensor
-        [K, N], e.g. trace.done; every episode is cut at its done and chopped into sequences of at most `length` steps, ordered by (instance, t0).
-        steps: an integer tensor [N], the steps instance i took (play()'s steps_played; clamped to 0 .. K), None: K for all.  starts: a bool / uint8
-        tensor [N], whether the rollout's first step starts an episode of instance i (it only sets the flag of the first sequence), None: all do.
-        capacity: the rows of the table.  None allocates N * ceil(K / length) + int(done.sum()), which always suffices -- and READS done.sum() ON THE
-        HOST: the one place that synchronises.  An explicit capacity synchronises nothing; the count may then exceed it (len() raises, the table holds
-        the first `capacity` sequences).  Three small launches on the current stream; the handle's first call allocates an int32 per instance and
-        cannot be captured into a graph, every later one can."""
-        self._require_started("split_episodes")
-        d8, K, L, steps, starts, capacity = check_split_episodes(done, length, self.num_envs, steps, starts, capacity, self.device)
-        if capacity is None:
-            capacity = self.num_envs * ((K + L - 1) // L) + int(d8.sum())
-        table = torch.empty((capacity, 4), dtype=torch.int32, device=self.device)
-        count = torch.empty((1,), dtype=torch.int32, device=self.device)
-        with torch.cuda.device(self.device):
-            _native.check(_native.LIB.mg_split_episodes(self._h, d8.data_ptr(), K, None if steps is None else steps.data_ptr(),
-                                                        None if starts is None else starts.data_ptr(), L, table.data_ptr() if capacity else None,
-                                                        capacity, count.data_ptr(), self._stream()), "mg_split_episodes")
-        return EpisodeSequences(table, count, L, K, self.num_envs, self)
-
-    def draw_frames_padded(self, records, pick, out=None, obs_format=None):
-        """draw_frames with padding rows (include/memgym.h: mg_draw_frames_padded): a pick below 0 writes its row as zeros, every byte, and is no
-        error.  Everything else -- the arguments, the checks, a pick at or beyond the records (row untouched, error bit 512), the single raster
-        launch -- is draw_frames; pick=None equals it."""
-        self._require_started("draw_frames_padded")
-        fmt = self.obs_format if obs_format is None else obs_format
-        rows, pick, count, (dt, shape) = check_frame_draw(records, self.frame_layout(), self.frame_record_bytes, pick, out, fmt, self.device)
-        if out is None:
-            out = torch.empty((count,) + shape, dtype=dt, device=self.device)
-        if count == 0:  # nothing to draw (an empty tensor has no address to hand to the library)
-            return out
-        if rows.device != self.device or out.device != self.device or rows.data_ptr() % 16 or out.data_ptr() % 16:
-            raise ValueError("draw_frames_padded: records and out must be 16-byte aligned tensors on %s" % (self.device,))
-        with torch.cuda.device(self.device):
-            _native.check(_native.LIB.mg_draw_frames_padded(self._h, rows.data_ptr(), rows.shape[0], None if pick is None else pick.data_ptr(), count,
-                                                            self.OBS_FORMATS[fmt][0], out.data_ptr(), self._stream()), "mg_draw_frames_padded")
-        return out
-
-    def draw_sequences(self, frames, seqs, sel=None, out=None, obs_format=None):
-        """Frames of a minibatch of sequences -> (obs [M, L] + shape of the format, mask bool [M, L]): row (j, l) is the observation step t0 + l of
-        sequence sel[j] was played in (sel=None: all sequences, M = len(seqs)), zeros where the sequence is shorter than L and for entries of sel below
-        0.  frames: the RolloutTrace the sequences were cut from, or a FrameRecords / uint8 tensor over its [K + 1, N] frame store; its layout is
-        checked as draw_frames checks it, and a trace whose K or N is not the sequences' is refused.  out: a contiguous tensor [M, L] + shape to draw
-        into.  Two launches on the current stream: the picks, and the PAD form of the gather raster."""
-        what = "draw_sequences"
-        self._require_started(what)
-        if not isinstance(seqs, EpisodeSequences):
-            raise ValueError("%s: seqs must be the EpisodeSequences split_episodes returned" % what)
-        if isinstance(frames, RolloutTrace):
-            if not (isinstance(frames.frames, torch.Tensor) and frames.frames.dim() == 3):
-                raise ValueError("%s: the trace keeps no frames" % what)
-            if (frames.steps, frames.num_envs) != (seqs.steps, seqs.num_envs):
-                raise ValueError("%s: the trace holds %d steps of %d instances, the sequences were cut from %d steps of %d"
-                                 % (what, frames.steps, frames.num_envs, seqs.steps, seqs.num_envs))
-            frames = FrameRecords(frames.frames, frames.frame_layout)
-        fmt = self.obs_format if obs_format is None else obs_format
-        if fmt not in self.OBS_FORMATS:
-            raise ValueError("%s: obs_format must be one of %s" % (what, sorted(self.OBS_FORMATS)))
-        _, dt, shape = self.OBS_FORMATS[fmt]
-        n_rec = (frames.records if isinstance(frames, FrameRecords) else frames)
-        if isinstance(n_rec, torch.Tensor) and n_rec.dim() >= 2 and n_rec.numel() // max(1, int(n_rec.shape[-1])) < (seqs.steps + 1) * seqs.num_envs:
-            raise ValueError("%s: frames holds fewer than (%d + 1) * %d records" % (what, seqs.steps, seqs.num_envs))
-        pick, mask = seqs.picks(sel)
-        M, L = int(pick.shape[0]), seqs.length
-        if out is not None:
-            if not (isinstance(out, torch.Tensor) and out.dtype == dt and tuple(out.shape) == (M, L) + shape and out.is_contiguous()):
-                raise ValueError("%s: out must be a contiguous %s tensor of shape %s" % (what, dt, (M, L) + shape))
-            flat = out.view((M * L,) + shape)
-        else:
-            flat = None
-        flat = self.draw_frames_padded(frames, pick.view(-1), out=flat, obs_format=fmt)
-        return flat.view((M, L) + shape), mask
-
-    # ------------------------------------------------------------------ memory windows
-    def episode_positions(self, done, steps=None, pos0=None):
-        """-> int32 [K + 1, N] (include/memgym.h: mg_episode_positions): row t holds the steps instance i's episode had already taken when frame t of
-        the rollout's [K + 1, N] store was shown.  done: a bool or uint8 tensor [K, N], e.g. trace.done.  steps: an integer tensor [N], the steps
-        instance i took (play()'s steps_played), None: K for all.  pos0: an integer tensor [N], the positions at the rollout's first frame -- row K of
-        the previous rollout's result -- None: every instance starts an episode.  One small launch on the current stream; nothing synchronises,
-        nothing is allocated in the handle."""
-        self._require_started("episode_positions")
-        d8, K, _, _, _, steps, pos0 = check_episode_windows(done, 1, self.num_envs, 0, 0, steps, pos0, self.device)
-        pos = torch.empty((K + 1, self.num_envs), dtype=torch.int32, device=self.device)
-        with torch.cuda.device(self.device):
-            _native.check(_native.LIB.mg_episode_positions(self._h, d8.data_ptr(), K, None if steps is None else steps.data_ptr(),
-                                                           None if pos0 is None else pos0.data_ptr(), pos.data_ptr(), self._stream()), "mg_episode_positions")
-        return pos
-
-    def episode_windows(self, done, window, lag=0, back=0, steps=None, pos0=None):
-        """The sliding memory windows of a rollout (include/memgym.h: MEMORY WINDOWS) -> EpisodeWindows: episode_positions(done, steps, pos0) with the
-        window's shape.  window: the rows of a window.  lag: 0 -- the window of sample (t, i) ends with its own row t (windows of frames); 1 -- one row
-        earlier (memories of past hidden states).  back: how many rows of the previous rollout a window may reach into; its picks then index a store
-        of [back + K + 1, N] rows.  One small launch."""
-        self._require_started("episode_windows")
-        d8, K, window, lag, back, steps, pos0 = check_episode_windows(done, window, self.num_envs, lag, back, steps, pos0, self.device)
-        return EpisodeWindows(self.episode_positions(d8, steps, pos0), window, lag, back, K, self.num_envs, self)
-
-    def gather_rows(self, x, pick, out=None):
-        """Rows of a store by index, zero rows at the pads (include/memgym.h: mg_gather_rows_padded): x [R, ...] contiguous, of any dtype and row
-        length; pick: integers of any shape, or None (row j) -> pick.shape + x.shape[1:].  A pick below 0 gives a row of zeros; a pick at or beyond
-        R leaves its row as it was and raises error bit 512.  out: a contiguous tensor of the result's shape and x's dtype that shares no byte
-        with x.  One launch on the current stream; nothing synchronises."""
-        x, pick, shape, row_bytes = check_gather_rows(x, pick, out, self.device)
-        if out is None:
-            out = torch.empty(shape, dtype=x.dtype, device=self.device)
-        count = int(x.shape[0]) if pick is None else pick.numel()
-        if count:
-            with torch.cuda.device(self.device):
-                _native.check(_native.LIB.mg_gather_rows_padded(self._h, x.data_ptr(), int(x.shape[0]), row_bytes, None if pick is None else pick.data_ptr(),
-                                                                count, out.data_ptr(), self._stream()), "mg_gather_rows_padded")
-        return out
-
-    def draw_windows(self, frames, windows, sel=None, out=None, obs_format=None):
-        """Frames of a minibatch of windows -> (obs [M, W] + shape of the format, mask bool [M, W], len int32 [M]): row (j, l) is the l-th oldest frame
-        of the window of sample sel[j] (sel=None: every sample), zeros behind the window's len and for entries of sel below 0.  frames: with
-        back == 0 the RolloutTrace the windows were made from, or a FrameRecords / uint8 tensor [K + 1, N, frame_record_bytes]; with back > 0 a
-        FrameRecords / uint8 store [back + K + 1, N, frame_record_bytes] whose first `back` rows are the previous rollout's frames[K_prev - back : K_prev].
-        Its layout is checked as draw_sequences checks it.  out: a contiguous tensor [M, W] + shape to draw into.  Two launches on the current
-        stream: the picks, and the PAD form of the gather raster."""
-        what = "draw_windows"
-        self._require_started(what)
-        frames = check_window_frames(frames, windows, self.frame_record_bytes)
-        fmt = self.obs_format if obs_format is None else obs_format
-        if fmt not in self.OBS_FORMATS:
-            raise ValueError("%s: obs_format must be one of %s" % (what, sorted(self.OBS_FORMATS)))
-        _, dt, shape = self.OBS_FORMATS[fmt]
-        pick, mask, length = windows.picks(sel)
-        M, W = int(pick.shape[0]), windows.window
-        if out is not None:
-            if not (isinstance(out, torch.Tensor) and out.dtype == dt and tuple(out.shape) == (M, W) + shape and out.is_contiguous()):
-                raise ValueError("%s: out must be a contiguous %s tensor of shape %s" % (what, dt, (M, W) + shape))
-            flat = out.view((M * W,) + shape)
-        else:
-            flat = None
-        flat = self.draw_frames_padded(frames, pick.view(-1), out=flat, obs_format=fmt)
-        return flat.view((M, W) + shape), mask, length
-
-    # ------------------------------------------------------------------ debug-view records
-    DEBUG_SIZES = {84: (84, 84, 3), 336: (336, 336, 3)}  # draw_debug_frames: the debug surface [x][y][c], or the reference's debug_rgb_array [y][x][c]
-
-    def save_debug_frames(self, idx=None, out=None):
-        """Keep the GROUND-TRUTH (debug) view of a few instances as records (include/memgym.h: mg_save_debug_frames) -> DebugFrameRecords over a uint8
-        tensor [k, frame_record_bytes]: what render_debug() would draw for instance idx[j] right now, as 16 / 64 / 128 bytes.  It counts as one debug
-        render of the named instances and of no other (Mortar Mayhem ids: the view's clone of the command schedule advances for them alone).  idx: the
-        instances, an integer tensor / list (None: all, in order); entries < 0 are skipped (their records keep their bytes); entries must be
-        DISTINCT -- a list, array or CPU tensor that names an instance twice is refused, a device tensor is not looked at.  out: a
-        DebugFrameRecords or a uint8 tensor [k, frame_record_bytes] to write into -- a row block store[t] of a larger [T, k, bytes] store.  One small
-        launch on the current stream (Endless-MysteryPath-v0: behind the launch that generates owed path segments); nothing synchronises."""
-        self._require_started("save_debug_frames")
-        _distinct_host_index("save_debug_frames", idx)
-        nbytes = self.frame_record_bytes
-        if out is not None and isinstance(out, FrameRecords) and not isinstance(out, DebugFrameRecords):
-            raise ValueError("save_debug_frames: out holds frame records (save_frames), not debug-view records")
-        idx, k, rows = check_frame_save(nbytes, self.num_envs, idx, out, self.device)
-        if rows is None:
-            out = rows = torch.empty((k, nbytes), dtype=torch.uint8, device=self.device)
-        if rows.device != self.device or rows.data_ptr() % 16:
-            raise ValueError("save_debug_frames: out must be a 16-byte aligned tensor on %s" % (self.device,))
-        with torch.cuda.device(self.device):
-            _native.check(_native.LIB.mg_save_debug_frames(self._h, None if idx is None else idx.data_ptr(), k, rows.data_ptr(), self._stream()),
-                          "mg_save_debug_frames")
-        if isinstance(out, DebugFrameRecords):
-            out.layout = self.frame_layout()
-            return out
-        return DebugFrameRecords(out, self.frame_layout())
-
-    def draw_debug_frames(self, records, pick=None, out=None, size=336):
-        """Draw kept debug views (include/memgym.h: mg_draw_debug_frames): row j of the result is the view of record pick[j] (pick=None: record j).
-        size=336: uint8 [count, 336, 336, 3], bit for bit the row render_debug() gave when the record was saved; size=84: uint8 [count, 84, 84, 3], the
-        debug surface before its stretch, in the observation layout [x][y][c].  records: a DebugFrameRecords (its layout is checked: ValueError if
-        stale, before anything is launched) or a plain uint8 tensor, viewed as [n_records, frame_record_bytes].  pick: an integer tensor / list of any
-        length, duplicates allowed; an entry outside the records leaves its row untouched and raises error bit 512.  out: a contiguous uint8 tensor of
-        the result's shape to draw into.  One raster launch on the current stream; nothing synchronises, nothing of the handle changes."""
-        what = "draw_debug_frames"
-        self._require_started(what)
-        if size not in self.DEBUG_SIZES:
-            raise ValueError("%s: size must be 84 or 336" % what)
-        if isinstance(records, FrameRecords):
-            if not isinstance(records, DebugFrameRecords):
-                raise ValueError("%s: these are frame records (save_frames): draw_frames draws them" % what)
-            if records.layout != self.frame_layout():
-                raise ValueError("%s: the records (layout 0x%x) were saved from another handle, or before something changed that they would draw differently "
-                                 "(layout 0x%x now): debug-view records are valid for the handle and the atlas they were saved under"
-                                 % (what, records.layout, self.frame_layout()))
-            records = records.records
-        rows = _frame_rows(what, "records", records, self.frame_record_bytes)
-        if pick is not None:
-            pick = _instance_index(what, "pick", pick, self.device)
-        count = rows.shape[0] if pick is None else pick.numel()
-        if count > 0 and rows.shape[0] < 1:
-            raise ValueError("%s: no records to draw from" % what)
-        shape = (count,) + self.DEBUG_SIZES[size]
-        if out is None:
-            out = torch.empty(shape, dtype=torch.uint8, device=self.device)
-        elif not (isinstance(out, torch.Tensor) and out.dtype == torch.uint8 and tuple(out.shape) == shape and out.is_contiguous()):
-            raise ValueError("%s: out must be a contiguous uint8 tensor of shape %s" % (what, shape))
-        if count == 0:  # nothing to draw (an empty tensor has no address to hand to the library)
-            return out
-        if rows.device != self.device or out.device != self.device or rows.data_ptr() % 16 or out.data_ptr() % 16:
-            raise ValueError("%s: records and out must be 16-byte aligned tensors on %s" % (what, self.device))
-        with torch.cuda.device(self.device):
-            _native.check(_native.LIB.mg_draw_debug_frames(self._h, rows.data_ptr(), rows.shape[0], None if pick is None else pick.data_ptr(), count,
-                                                           int(size), out.data_ptr(), self._stream()), "mg_draw_debug_frames")
-        return out
 
     def _scatter_rows(self, dst, tgt, rows):
         """dst[tgt[j]] = rows[j]; tgt[j] == len(dst) names nobody (a skipped entry).  No host look."""
@@ -1553,8 +729,7 @@ class VecMemoryGym:
             raise ValueError("load_instances(render=False) on a handle with final_observation=True: terminal observations are frames")
         N = self.num_envs
         idx, rec = check_instance_load(snap, self.instance_layout, self.instance_bytes, N, idx, rec, self.device)
-        if snap.records.device != self.device or snap.records.data_ptr() % 16:
-            raise ValueError("load_instances: snapshot.records must be a 16-byte aligned tensor on %s" % (self.device,))
+        aligned_on("load_instances", "snapshot.records", self.device, snap.records)
         if snap.set_of is not None and self._set_of is None:
             raise ValueError("load_instances: the snapshot was taken under per-instance option sets, which a full reset has dropped since")
         k = snap.count
@@ -1575,8 +750,7 @@ class VecMemoryGym:
                 calls = [(pi[c:c + k], pr[c:c + k]) for c in range(0, total, k)]
             self._clear_pending()
             for ci, cr in calls:
-                _native.check(_native.LIB.mg_load_instances(self._h, None if ci is None else ci.data_ptr(), None if cr is None else cr.data_ptr(), k,
-                                                            snap.records.data_ptr(), obs_ptr, self._stream()), "mg_load_instances")
+                _native.check(_native.LIB.mg_load_instances(self._h, ptr(ci), ptr(cr), k, snap.records.data_ptr(), obs_ptr, self._stream()), "mg_load_instances")
             # what the handle keeps beside the state: the set index (the caller's, include/memgym.h) and the ground truth rows
             whole = idx is None and rec is None  # instance j <- record j for every j
             tgt = src = None
@@ -1613,8 +787,8 @@ class VecMemoryGym:
         """Instance dst[j] <- instance src[j] inside the handle: a save followed by a load through a scratch snapshot the handle keeps, so `src` and
         `dst` may overlap (a permutation in place).  Returns what load_instances returns."""
         self._require_started("copy_instances")
-        src = _instance_index("copy_instances", "src", src, self.device)
-        dst = _instance_index("copy_instances", "dst", dst, self.device)
+        src = index_tensor("copy_instances", "src", src, self.device)
+        dst = index_tensor("copy_instances", "dst", dst, self.device)
         if src.numel() != dst.numel():
             raise ValueError("copy_instances: src and dst must have the same length, got %d and %d" % (src.numel(), dst.numel()))
         if src.numel() == 0:
@@ -1716,18 +890,15 @@ class VecMemoryGym:
                 _native.LIB.mg_poll_errors(self._h, C.byref(C.c_int()))
             if sd.get("option_sets") is not None:
                 for k, p in enumerate(sd["option_sets"]):
-                    while len(self._set_params) <= k:
-                        self._set_params.append({})
+                    self._room_for_set(k)
                     if k > 0 and p:  # (an empty entry: a slot that was never filled or half-written when the checkpoint was taken)
                         self._set_params[k] = {}
                         self._write_set(k, process_reset_params(self.env_id, {kk: vv for kk, vv in p.items() if kk in DEFAULTS[self.env_id]}))
                 if self._set_of is None:
-                    self._set_of = torch.zeros(self.num_envs, dtype=torch.int32, device=self.device)
-                    _native.check(_native.LIB.mg_bind_option_sets(self._h, self._set_of.data_ptr()), "mg_bind_option_sets")
+                    self._bind_set_index(True)
                 self._set_of.copy_(torch.as_tensor(np.asarray(sd["set_of"], dtype=np.int32), device=self.device))
             elif self._set_of is not None:  # the checkpoint was taken with one option set: back to that arrangement
-                _native.check(_native.LIB.mg_bind_option_sets(self._h, None), "mg_bind_option_sets")
-                self._set_of = None
+                self._bind_set_index(False)
                 del self._set_params[1:]
             buf = np.ascontiguousarray(sd["blob"], dtype=np.uint8)
             _native.check(_native.LIB.mg_set_state(self._h, buf.ctypes.data, buf.size), "mg_set_state")
@@ -1801,163 +972,4 @@ class VecMemoryGym:
             pass
 
 
-try:  # a real gymnasium.Env when the host has gymnasium (the reference's CustomEnv(gym.Env), environment.py:3-7)
-    import gymnasium as _gym
-    _EnvBase = _gym.Env
-except Exception:  # gymnasium is not a dependency of the hot path
-    _gym = None
-    _EnvBase = object
-
-
-class MemoryGymEnv(_EnvBase):
-    """Single-instance environment with the reference's exact signatures (reset -> (obs, info); step -> 5-tuple of numpy
-    obs, Python float reward, bool, False, dict) -- what `gymnasium.make(id)` returns.  Subclasses gymnasium.Env when
-    gymnasium is importable; without it the same protocol surface (`unwrapped`, `spec`, `np_random`, `metadata`,
-    `render_mode`, spaces) is provided here, so code written against the reference runs either way.
-
-    Round 5: the single-instance fast path of the C ABI (include/memgym.h: mg_single_open / mg_single_reset / mg_single_step).
-    Observation, reward, done, ground truth and the end-of-episode record live in pinned host memory that is mapped into the
-    device; the kernels read the action from it and store their results straight into it, so step() is ONE native call (store the
-    action, enqueue the step's launches, wait for the stream) and a copy of the 21-KB frame -- no torch operation.  (Rounds 1-4: an
-    H2D action copy, two indexing kernels, three D2H copies and a stream synchronisation per step: 14 k steps/s.)"""
-
-    metadata = {"render_modes": ["rgb_array", "debug_rgb_array"], "render_fps": 25}
-    spec = None
-    env_id = None  # set by the per-id subclasses in memory_gym_amd.envs
-
-    def __init__(self, env_id=None, device=None, render_mode=None, capacity=None):
-        env_id = env_id or self.env_id
-        self.vec = VecMemoryGym(env_id, 1, device, render_mode, capacity=capacity)
-        self.vec.autoreset = False
-        self.action_space = self.vec.action_space
-        self.observation_space = self.vec.observation_space
-        self.has_ground_truth_info = self.vec.has_ground_truth_info
-        if self.has_ground_truth_info:
-            self.ground_truth_space = self.vec.ground_truth_space
-        self.render_mode = render_mode
-        self._np_random = None
-        io = _native.SingleIO()
-        io.struct_size = C.sizeof(_native.SingleIO)
-        with torch.cuda.device(self.vec.device):
-            _native.check(_native.LIB.mg_single_open(self.vec._h, C.byref(io)), "mg_single_open")
-        self._io = io
-
-        def view(ptr, ctype, shape):
-            return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(ctype)), shape=shape)
-        self._obs_host = view(io.obs, C.c_uint8, (84, 84, 3))
-        self._vec_host = view(io.vec, C.c_float, (self.vec.vec_dim,)) if self.vec.vec_dim else None
-        self._reward_host = view(io.reward, C.c_double, (1,))
-        self._done_host = view(io.done, C.c_uint8, (1,))
-        self._gt_host = view(io.gt, C.c_double, (max(self.vec.gt_dim, 1),))
-        self._ep_reward_host = view(io.ep_reward, C.c_double, (1,))
-        self._ep_length_host = view(io.ep_length, C.c_int32, (1,))
-        self._aux_host = [view(io.aux[k], C.c_float, (1,)) for k in range(len(self.vec.info_names))]
-        self._two_actions = self.vec.action_dim == 2
-        # (the launch stream is torch's CURRENT stream at every call, like the batched path: a handle cached at construction or at the last
-        # reset may be another stream than the caller's by now, or a released one -- ADVICE r5)
-        self._raw_stream = self.vec._raw_stream
-        self._step_fn, self._h, self._errword = _native.LIB.mg_single_step, self.vec._h, self.vec._err
-        if self.vec.vector_obs is not None:
-            # mg_single_open re-bound the handle's vector observation to the mapped block: `vec.vector_obs` (the batched tensor) is no
-            # longer written; this adapter's observations carry the vector from the mapped block
-            self.vec.vector_obs_stale = True
-        self._peek = _native.LIB.mg_peek_errors
-
-    # ---- gymnasium.Env protocol surface that exists with or without gymnasium
-    @property
-    def unwrapped(self):
-        return self
-
-    @property
-    def np_random(self):
-        """A numpy Generator like gymnasium.Env.np_random (the environment's own draws happen on the device, from the
-        PCG64 stream that reset(seed) seeds exactly like gymnasium does; this host-side generator is seeded alike)."""
-        if self._np_random is None:
-            self._np_random = np.random.Generator(np.random.PCG64(np.random.SeedSequence()))
-        return self._np_random
-
-    @np_random.setter
-    def np_random(self, value):
-        self._np_random = value
-
-    def _observation(self):
-        o = self._obs_host.copy()
-        if self._vec_host is not None:
-            o = {"visual_observation": o, "vector_observation": self._vec_host.copy()}
-        return o
-
-    @property
-    def max_episode_steps(self):
-        return self.vec.max_episode_steps
-
-    def reset(self, seed=None, return_info=True, options=None):
-        if seed is not None:  # gymnasium.Env.reset(seed): the host-side generator follows the same seed
-            self._np_random = np.random.Generator(np.random.PCG64(np.random.SeedSequence(int(seed))))
-        v = self.vec
-        with torch.cuda.device(v.device):
-            v._apply_options(options)
-            if seed is None and not v._seeded:  # first reset without a seed: OS entropy, like gymnasium's np_random(None)
-                seed = int(np.random.SeedSequence().generate_state(1, np.uint64)[0] >> np.uint64(1))
-            _native.check(_native.LIB.mg_single_reset(self._h, 0 if seed is None else int(seed), 0 if seed is None else 1, C.c_void_p(self._raw_stream())), "mg_single_reset")
-            v._seeded = True
-        out = {}
-        if v.gt_dim:
-            out["ground_truth"] = self._gt_host[:v.gt_dim].copy()
-        return self._observation(), out
-
-    def step(self, action):
-        if self._two_actions:
-            a0, a1 = int(action[0]), int(action[1])
-        else:
-            a0 = a1 = int(action)
-        rc = self._step_fn(self._h, a0, a1, self._raw_stream())
-        if rc != 0:  # negative: the call failed; positive: device error bits as they stand (include/memgym.h)
-            if rc < 0:
-                _native.check(rc, "mg_single_step")
-            if rc & ~self.vec._tolerated:
-                self.vec.check_errors()
-        r, d = float(self._reward_host[0]), bool(self._done_host[0])  # r: the reference's Python float, bit for bit
-        out = {}
-        if d:  # end of episode (rare): the reference's terminal info dict
-            out["reward"] = float(self._ep_reward_host[0])
-            out["length"] = int(self._ep_length_host[0])
-            for nm, a in zip(self.vec.info_names, self._aux_host):
-                out[nm] = float(a[0])
-        if self.vec.gt_dim:
-            out["ground_truth"] = self._gt_host[:self.vec.gt_dim].copy()
-        return self._observation(), r, d, False, out
-
-    def expert_action(self, eps=0.0, seed=0, step=None):
-        """The scripted teacher's action in the current state (VecMemoryGym.expert_actions with one instance): an int for Discrete ids, a
-        numpy int array of two for MultiDiscrete ids -- what step() takes.  Not a hot path (a launch and a copy to the host)."""
-        a = self.vec.expert_actions(eps, seed, step).cpu().numpy()
-        return a[0].copy() if self._two_actions else int(a[0])
-
-    def render(self):
-        if self.render_mode == "debug_rgb_array":
-            return self.vec.render_debug()[0].cpu().numpy()
-        return self._obs_host.transpose(1, 0, 2).copy()  # mortar_mayhem_grid.py:401-402
-
-    def state_dict(self):
-        return self.vec.state_dict()
-
-    def load_state_dict(self, sd):
-        self.vec.load_state_dict(sd)
-
-    def snapshot(self):
-        """The instance as it stands, in device memory (VecMemoryGym.save_instances) -- for restore()."""
-        return self.vec.save_instances()
-
-    def restore(self, snap):
-        """Put the instance back where snapshot() found it (VecMemoryGym.load_instances): the following steps give what the steps after the
-        snapshot gave.  -> the observation of that moment, as reset() returns it.  Not a hot path (a launch, a frame and a copy to the host)."""
-        v = self.vec
-        v.load_instances(snap, render=True)
-        torch.cuda.current_stream(v.device).synchronize()
-        self._obs_host[...] = v.obs[0].cpu().numpy()
-        if v.gt_dim:
-            self._gt_host[:v.gt_dim] = (v.gt64 if v.gt64 is not None else v.gt)[0].double().cpu().numpy()
-        return self._observation()
-
-    def close(self):
-        self.vec.close()
+from .single import MemoryGymEnv  # noqa: E402,F401  (the adapter is built on the class above; it keeps its name here too)

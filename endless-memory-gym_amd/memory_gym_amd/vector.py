@@ -89,9 +89,19 @@ class GymnasiumVectorEnv(_Base):
 
     # ------------------------------------------------------------------ conversions
     def _host(self, x):
+        if x is None:
+            return None
         if isinstance(x, dict):
             return {k: self._host(v) for k, v in x.items()}
         return x.cpu().numpy() if self.as_numpy else x
+
+    def _final_info(self, ep, d):
+        """gymnasium's host-side `final_info`: an object array [N] that holds the end-of-episode dict of sub-environment i where d[i], None elsewhere"""
+        finfo = np.full(self.num_envs, None, dtype=object)
+        host_ep = {k: v.cpu().numpy() for k, v in ep.items()}
+        for i in np.nonzero(d)[0]:
+            finfo[i] = {k: (int(v[i]) if k == "length" else float(v[i])) for k, v in host_ep.items()}
+        return finfo
 
     def reset(self, seed=None, options=None):
         obs, info = self.env.reset(seed=seed, options=options)
@@ -134,11 +144,7 @@ class GymnasiumVectorEnv(_Base):
             out = self._host({k: v for k, v in infos.items() if k != "final_frames"})
             out["final_frames"] = infos["final_frames"]
             if d.any():
-                finfo = np.full(self.num_envs, None, dtype=object)
-                host_ep = {k: v.cpu().numpy() for k, v in ep.items()}
-                for i in np.nonzero(d)[0]:
-                    finfo[i] = {k: (int(v[i]) if k == "length" else float(v[i])) for k, v in host_ep.items()}
-                out.update(final_info=finfo, _final_info=d.copy())
+                out.update(final_info=self._final_info(ep, d), _final_info=d.copy())
             return None, self.env.reward64.cpu().numpy(), term.cpu().numpy(), trunc.cpu().numpy(), out
         if not self.as_numpy:
             infos.update(final_observation=info["final_observation"], _final_observation=done, final_info=ep, _final_info=done)
@@ -148,13 +154,10 @@ class GymnasiumVectorEnv(_Base):
         if d.any():
             idx = np.nonzero(d)[0]
             fobs = np.full(self.num_envs, None, dtype=object)
-            finfo = np.full(self.num_envs, None, dtype=object)
             rows = info["final_observation"][torch.as_tensor(idx, device=done.device)].cpu().numpy()
-            host_ep = {k: v.cpu().numpy() for k, v in ep.items()}
             for j, i in enumerate(idx):
                 fobs[i] = rows[j]
-                finfo[i] = {k: (int(v[i]) if k == "length" else float(v[i])) for k, v in host_ep.items()}
-            out.update(final_observation=fobs, _final_observation=d.copy(), final_info=finfo, _final_info=d.copy())
+            out.update(final_observation=fobs, _final_observation=d.copy(), final_info=self._final_info(ep, d), _final_info=d.copy())
         return self._host(obs), self.env.reward64.cpu().numpy(), term.cpu().numpy(), trunc.cpu().numpy(), out  # (the reference's Python floats: doubles)
 
     def final_observations(self, info, out=None, obs_format=None):
@@ -215,20 +218,20 @@ class GymnasiumVectorEnv(_Base):
         """`steps` steps under the scripted teacher without a frame (VecMemoryGym.advance) -> (obs or None, stats); numpy with as_numpy.
         Episodes that end inside the call are NOT reported as `final_observation` / `final_info`: they are counted and summed in `stats`."""
         obs, st = self.env.advance(steps, eps=eps, seed=seed, step=step, render=render, stats=stats)
-        return (None if obs is None else self._host(obs)), (None if st is None else self._host(st))
+        return self._host(obs), self._host(st)
 
     def advance_traced(self, trace, eps=0.0, seed=0, step=None, render=True, stats=True):
         """VecMemoryGym.advance_traced: advance(trace.steps, ...) that keeps every step's frame record, action, label, reward and done in `trace`, a
         RolloutTrace (new_rollout) -> (obs or None, stats); numpy with as_numpy."""
         obs, st = self.env.advance_traced(trace, eps=eps, seed=seed, step=step, render=render, stats=stats)
-        return (None if obs is None else self._host(obs)), (None if st is None else self._host(st))
+        return self._host(obs), self._host(st)
 
     def play(self, actions, until_done=False, mask=None, render=True, stats=True, trace=False):
         """K steps of caller-supplied action sequences without a frame (VecMemoryGym.play) -> (obs or None, stats); numpy with as_numpy.
         Episodes that end inside the call are NOT reported as `final_observation` / `final_info`: they are counted and summed in `stats`.
         trace: False / True as in VecMemoryGym.play, or a RolloutTrace (new_rollout) that keeps every step's frame record, reward and done."""
         obs, st = self.env.play(actions, until_done=until_done, mask=mask, render=render, stats=stats, trace=trace)
-        return (None if obs is None else self._host(obs)), (None if st is None else self._host(st))
+        return self._host(obs), self._host(st)
 
     def save_instances(self, idx=None, out=None):
         """VecMemoryGym.save_instances: single instances to device memory -> InstanceSnapshot."""
@@ -236,13 +239,11 @@ class GymnasiumVectorEnv(_Base):
 
     def load_instances(self, snap, idx=None, rec=None, render=True):
         """VecMemoryGym.load_instances -> obs (numpy with as_numpy); this handle keeps terminal observations, so render=False is refused."""
-        obs = self.env.load_instances(snap, idx=idx, rec=rec, render=render)
-        return None if obs is None else self._host(obs)
+        return self._host(self.env.load_instances(snap, idx=idx, rec=rec, render=render))
 
     def copy_instances(self, src, dst, render=True):
         """VecMemoryGym.copy_instances -> obs (numpy with as_numpy)."""
-        obs = self.env.copy_instances(src, dst, render=render)
-        return None if obs is None else self._host(obs)
+        return self._host(self.env.copy_instances(src, dst, render=render))
 
     # gymnasium.vector.VectorEnv API surface used by trainers
     def step_async(self, actions):
