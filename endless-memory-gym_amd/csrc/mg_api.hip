@@ -9,6 +9,7 @@
 //   mg_api_single.hpp   the single-instance fast path (mg_single_open / mg_single_reset / mg_single_step)
 //   mg_api_state.hpp    checkpoints, profiling, error words, peer access, mg_debug_counter, mg_debug_rng / mg_debug_set_rng
 //   mg_api_windows.hpp  memory windows: mg_episode_positions / mg_window_picks / mg_gather_rows_padded (kernels: mg_windows.hpp)
+//   mg_api_targets.hpp  rollout targets: mg_rollout_targets / mg_sum_columns (kernels and arithmetic: mg_targets.hpp)
 //
 // Here, in this order: make_family / destroy_family; next_flags_kernel; then ONE block with C linkage: copy_rows_kernel and debug_stretch_kernel (their
 // symbols have always been the unmangled names), step_call (the body of mg_step and mg_step_masked), and the entry points -- mg_last_error, mg_create /
@@ -22,6 +23,7 @@
 #include "mg_api_rollout.hpp"
 #include "mg_api_single.hpp"
 #include "mg_api_state.hpp"
+#include "mg_api_targets.hpp"
 #include "mg_api_windows.hpp"
 #include "mg_expert.hpp"
 #include "mg_lab.hpp"

@@ -71,6 +71,7 @@ struct mg_env {
         mg::DevArray<int32_t> block_sum;  // [ceil(num_envs / SEQ_BLOCK)] the workgroup's sum, then the sum of the workgroups in front of it
     } seq;
     int64_t episode_positions = 0, window_picks = 0, row_gathers = 0;  // mg_debug_counter: mg_episode_positions / mg_window_picks / mg_gather_rows_padded calls
+    int64_t rollout_targets = 0;  // mg_debug_counter: mg_rollout_targets calls that were not refused
     struct Instances {
         bool ready = false;
         mg::DevArray<int32_t> claim;  // [num_envs] the entry of the current load that holds the instance

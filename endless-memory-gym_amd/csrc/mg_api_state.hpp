@@ -34,7 +34,7 @@ const HandleCounter HANDLE_COUNTERS[] = {
     {"masked_steps", &mg_env::masked_steps}, {"next_steps", &mg_env::next_steps},
     {"next_fused_steps", &mg_env::next_fused_steps}, {"final_frame_steps", &mg_env::final_frame_steps},
     {"episode_positions", &mg_env::episode_positions}, {"window_picks", &mg_env::window_picks},
-    {"row_gathers", &mg_env::row_gathers},
+    {"row_gathers", &mg_env::row_gathers}, {"rollout_targets", &mg_env::rollout_targets},
 };
 }  // namespace
 

@@ -1,5 +1,5 @@
 """What split_episodes and episode_windows return -- a rollout's episode sequences and its sliding memory windows -- with the argument checks that
-need no handle."""
+need no handle; and rollout_targets, the advantages and returns of a rollout, a function over the handle."""
 import numpy as np
 import torch
 
@@ -205,6 +205,134 @@ class EpisodeWindows:
         if self._env is None:
             raise ValueError("EpisodeWindows.gather: these windows belong to no handle")
         return self._env.gather_rows(rows, self.picks(sel)[0])
+
+
+def _unit_interval(what, name, v):
+    """v as a float; ValueError unless it is a number (no bool) in 0 .. 1"""
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0.0 <= float(v) <= 1.0:
+        raise ValueError("%s: %s must be a number in 0 .. 1, got %r" % (what, name, v))
+    return float(v)
+
+
+def check_rollout_targets(reward, done, value, num_envs, gamma=0.99, lam=0.95, steps=None, skip=None, truncated=None, final_value=None, device=None):
+    """The argument checks of rollout_targets, which need no handle: -> (reward, done as a uint8 view [K, N], value, K, gamma, lam, steps as an int32
+    tensor [N] or None, skip and truncated as uint8 views [K, N] or None, final_value).  ValueError for a `done` that is no contiguous bool / uint8
+    tensor [K, N] with K >= 1 and N = num_envs, (K + 1) * N beyond an int32, a `reward` / `final_value` that is no contiguous float32 tensor [K, N], a
+    `value` that is no contiguous float32 tensor [K + 1, N], `skip` / `truncated` that are no contiguous bool / uint8 tensors [K, N], `steps` that is no
+    int32 / int64 tensor [N], a final_value without truncated, gamma or lam outside 0 .. 1, and anything that does not lie on `device` (if given)."""
+    what = "rollout_targets"
+    K, N = done_rows(what, done, num_envs)
+    if (K + 1) * N > MAX_PICK:
+        raise ValueError("%s: (K + 1) * N = %d does not fit the int32 of a pick: take slices of the rollout" % (what, (K + 1) * N))
+    d8 = done_view(what, done)
+    same_device(what, "done", done, device)
+    for name, t, rows in (("reward", reward, K), ("value", value, K + 1), ("final_value", final_value, K)):
+        if t is None and name == "final_value":
+            continue
+        if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and tuple(t.shape) == (rows, N) and t.is_contiguous()):
+            raise ValueError("%s: %s must be a contiguous float32 tensor [%d, %d]" % (what, name, rows, N))
+        same_device(what, name, t, device)
+    flags = []
+    for name, t in (("skip", skip), ("truncated", truncated)):
+        if t is not None:
+            if not (isinstance(t, torch.Tensor) and t.dtype in (torch.bool, torch.uint8) and tuple(t.shape) == (K, N) and t.is_contiguous()):
+                raise ValueError("%s: %s must be a contiguous bool or uint8 tensor [%d, %d]" % (what, name, K, N))
+            same_device(what, name, t, device)
+            t = t.view(torch.uint8)
+        flags.append(t)
+    if final_value is not None and truncated is None:
+        raise ValueError("%s: final_value needs truncated (the ends that bootstrap from it)" % what)
+    gamma, lam = _unit_interval(what, "gamma", gamma), _unit_interval(what, "lam", lam)
+    return reward, d8, value, K, gamma, lam, per_instance_int32(what, "steps", steps, N, device), flags[0], flags[1], final_value
+
+
+class RolloutTargets:
+    """What rollout_targets returns (include/memgym.h: mg_rollout_targets / mg_sum_columns): the targets of a rollout of K steps of N
+    instances.
+        adv      float32 [K, N]   generalised advantage estimates, 0 where the row has no target
+        ret      float32 [K, N]   adv + value, the critic's target (lam = 1: the discounted return-to-go)
+        valid    bool    [K, N]   whether the row has a target
+    and with moments=True
+        columns  float64 [3, N]   per instance the count, the sum and the sum of squares of its valid advantages
+        moments  float64 [3]      the same over all instances, summed in mg_sum_columns' fixed order
+    mean() / std() / normalized() are torch expressions over `moments` on the device.  Nothing here synchronises."""
+    __slots__ = ("adv", "ret", "valid", "columns", "moments")
+
+    def __init__(self, adv, ret, valid, columns=None, moments=None):
+        self.adv, self.ret, self.valid, self.columns, self.moments = adv, ret, valid, columns, moments
+
+    def _need_moments(self, what):
+        if self.moments is None:
+            raise ValueError("RolloutTargets.%s: these targets were made without moments=True" % what)
+        return self.moments
+
+    def mean(self):
+        """the mean of the valid advantages, a float64 scalar on the device (nan where no row is valid)"""
+        m = self._need_moments("mean")
+        return m[1] / m[0]
+
+    def std(self):
+        """the standard deviation of the valid advantages (the population's: divided by the count), a float64 scalar on the device"""
+        m = self._need_moments("std")
+        mean = m[1] / m[0]
+        return (m[2] / m[0] - mean * mean).clamp(min=0.0).sqrt()
+
+    def normalized(self, eps=1e-8):
+        """(adv - mean()) / (std() + eps) as float32 [K, N], 0 where the row has no target"""
+        self._need_moments("normalized")
+        z = ((self.adv.double() - self.mean()) / (self.std() + eps)).float()
+        return torch.where(self.valid, z, torch.zeros_like(z))
+
+
+def check_targets_out(out, steps, num_envs, moments, device=None):
+    """ValueError unless `out` is a RolloutTargets whose tensors have the shapes and dtypes of its docstring for K = steps and N = num_envs, are
+    contiguous and lie on `device` (if given); with moments its columns and moments too."""
+    what = "rollout_targets"
+    if not isinstance(out, RolloutTargets):
+        raise ValueError("%s: out must be a RolloutTargets (what an earlier call returned)" % what)
+    want = [("adv", torch.float32, (steps, num_envs)), ("ret", torch.float32, (steps, num_envs)), ("valid", torch.bool, (steps, num_envs))]
+    if moments:
+        want += [("columns", torch.float64, (3, num_envs)), ("moments", torch.float64, (3,))]
+    for name, dt, shape in want:
+        t = getattr(out, name)
+        if not (isinstance(t, torch.Tensor) and t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous()):
+            raise ValueError("%s: out.%s must be a contiguous %s tensor of shape %s" % (what, name, dt, shape))
+        same_device(what, "out." + name, t, device)
+    return out
+
+
+def rollout_targets(env, reward, done, value, gamma=0.99, lam=0.95, steps=None, skip=None, truncated=None, final_value=None, out=None, moments=False):
+    """Advantages, returns and their valid mask of a rollout (include/memgym.h: mg_rollout_targets) -> RolloutTargets.  env: the VecMemoryGym handle
+    (of a GymnasiumVectorEnv: its `.env`).  reward: float32 [K, N] and
+    done: bool / uint8 [K, N], e.g. trace.reward / trace.done; value: float32 [K + 1, N], the critic's value of row t of the rollout's [K + 1, N]
+    frame store, row K the bootstrap value.  gamma, lam in 0 .. 1 (lam = 1: `ret` holds discounted returns-to-go).  steps: an integer tensor [N],
+    the steps instance i took (play()'s steps_played), None: K for all; rows beyond it have no target.
+    Same-step auto-reset needs nothing else: an episode that ends bootstraps from 0.  truncated: bool / uint8 [K, N], the ends that bootstrap from
+    the terminal observation's value instead; final_value: float32 [K, N], that value (the critic on final_observations() / final_frames).  Under
+    autoreset_mode="next_step" pass skip = the restart flags of step t (bool / uint8 [K, N]: the rows that reset instead of stepping have no
+    target and cut the recursion) and truncated WITHOUT final_value: the terminal observation is frame row t + 1, value[t + 1] its value.
+    moments=True also gives the per-instance and total count / sum / sum of squares of the valid advantages (a second small launch) for mean() /
+    std() / normalized().  out: a RolloutTargets of an earlier call with the same K, N and moments, to write into.  One launch on the current
+    stream; nothing synchronises, nothing is allocated in the handle: even the first call can be captured into a graph."""
+    env._require_started("rollout_targets")
+    reward, d8, value, K, gamma, lam, steps, skip, truncated, final_value = check_rollout_targets(reward, done, value, env.num_envs, gamma, lam, steps, skip,
+                                                                                                  truncated, final_value, env.device)
+    N = env.num_envs
+    if out is None:
+        adv, ret = (torch.empty((K, N), dtype=torch.float32, device=env.device) for _ in range(2))
+        out = RolloutTargets(adv, ret, torch.empty((K, N), dtype=torch.bool, device=env.device))
+        if moments:
+            out.columns = torch.empty((3, N), dtype=torch.float64, device=env.device)
+            out.moments = torch.empty((3,), dtype=torch.float64, device=env.device)
+    else:
+        check_targets_out(out, K, N, moments, env.device)
+    with torch.cuda.device(env.device):
+        _native.check(_native.LIB.mg_rollout_targets(env._h, reward.data_ptr(), d8.data_ptr(), value.data_ptr(), K, ptr(steps), ptr(skip), ptr(truncated),
+                                                     ptr(final_value), gamma, lam, out.adv.data_ptr(), out.ret.data_ptr(), out.valid.data_ptr(),
+                                                     out.columns.data_ptr() if moments else None, env._stream()), "mg_rollout_targets")
+        if moments:
+            _native.check(_native.LIB.mg_sum_columns(env._h, out.columns.data_ptr(), 3, out.moments.data_ptr(), env._stream()), "mg_sum_columns")
+    return out
 
 
 def check_window_frames(frames, windows, record_bytes):

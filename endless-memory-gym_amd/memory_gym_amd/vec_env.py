@@ -25,7 +25,8 @@ import torch
 
 from . import _native
 from ._args import MAX_PICK, aligned_on, index_tensor, ptr  # noqa: F401
-from .episodes import EpisodeSequences, EpisodeWindows, check_episode_windows, check_gather_rows, check_split_episodes, check_window_frames  # noqa: F401
+from .episodes import (EpisodeSequences, EpisodeWindows, RolloutTargets, check_episode_windows, check_gather_rows, check_rollout_targets,  # noqa: F401
+                       check_split_episodes, check_window_frames, rollout_targets)
 from .obs_memory import alloc_obs_buffer, is_balanced_buffer  # noqa: F401
 from .record_calls import RecordCalls
 from .records import (MAX_DRAW_RECORDS, OBS_FORMATS, DebugFrameRecords, FrameRecords, InstanceSnapshot, RolloutTrace, _distinct_host_index,  # noqa: F401

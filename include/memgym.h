@@ -662,6 +662,56 @@ int mg_window_picks(mg_env* env, const int32_t* pos_dev, int32_t steps, const in
 int mg_gather_rows_padded(mg_env* env, const void* src_dev, int64_t n_rows, int64_t row_bytes, const int32_t* pick_dev, int64_t count,
                           void* dst_dev, void* stream);
 
+/* ROLLOUT TARGETS: what a PPO trainer computes between "rollout done" and "first minibatch" -- generalised advantage estimates, returns, a mask of the
+ * rows that have a target, and the moments advantages are normalised with -- from a rollout's reward / done rows and the critic's values, on the device.
+ *   mg_rollout_targets   reward, done [steps][num_envs], value [steps + 1][num_envs] -> adv, ret, valid [steps][num_envs], col [3][num_envs]
+ *   mg_sum_columns       col [rows][num_envs] -> out [rows], summed in a fixed order
+ * Both are enqueue-only on `stream`, synchronise nothing, keep no scratch in the handle and allocate nothing -- so even a handle's first call can be
+ * captured into a HIP graph; the arrays are read at replay, gamma, lambda and steps are the captured values.  MG_STATE_VERSION is unchanged: no state
+ * is added.
+ * ARRAYS.  reward_dev (float32), done_dev, skip_dev, trunc_dev (one byte each) and final_value_dev (float32) are [steps][num_envs], step-major: what a
+ * trace holds; skip_dev, trunc_dev and final_value_dev are optional.  value_dev is float32 [steps + 1][num_envs]: row t is the critic's value of row t of
+ * the [steps + 1][num_envs] frame store (the convention of mg_sequence_picks: row 0 is the frame before the call's first step), row `steps` the bootstrap
+ * value.  adv_dev, ret_dev (float32 [steps][num_envs]), valid_dev (uint8 [steps][num_envs]) and col_dev (double [3][num_envs]) are each optional, but at
+ * least one of them must be given; a NULL output is not written.
+ * mg_rollout_targets, DEFINITION.  n_i as in mg_split_episodes: steps_of_dev clamped to 0 .. steps, NULL: steps.  Every arithmetic step below is one
+ * IEEE float32 operation, rounded to nearest and never fused.  gl = gamma * lambda, computed once on the host in float32.  For instance i start with
+ * a = 0 and walk t = steps - 1 down to 0:
+ *   t >= n_i, or skip_dev set and skip[t][i] != 0   the row has no target: adv = ret = 0, valid = 0, a = 0, and on to the next row;
+ *   v = value[t][i], r = reward[t][i];
+ *   done[t][i] != 0                                 carry = 0; nv = (trunc_dev set and trunc[t][i] != 0) ? (final_value_dev ? final_value[t][i]
+ *                                                   : value[t+1][i]) : 0;
+ *   otherwise                                       nv = value[t+1][i], carry = a;
+ *   delta = (r + gamma * nv) - v;  a = delta + gl * carry;
+ *   adv[t][i] = a, ret[t][i] = a + v, valid[t][i] = 1.
+ * The multiply by nv = 0 and the add are part of the definition: a reward of -0.0 on a terminal row gives what the loop gives.  lambda = 1 gives
+ * discounted returns-to-go in ret.  col_dev holds, for instance i, col[0][i] the count, col[1][i] the sum and col[2][i] the sum of squares of its valid
+ * adv values, accumulated in the walk's own order (t descending), each a rounded double operation: (double)a * (double)a, then the add.
+ * HOW THE CONVENTIONS MAP ON THE DEFINITION.
+ *   same-step auto-reset                     nothing but done: the next value row belongs to the new episode and is not looked at;
+ *   same-step auto-reset, truncated ends     additionally trunc_dev and final_value_dev, the critic's value of the terminal observation
+ *                                            (mg_info_buffers.final_obs_dev / final_frames_dev rows);
+ *   next-step auto-reset (mg_step_next)      skip[t] = the restart flags of call t -- the row after an episode's end is a reset row, not a transition:
+ *                                            it gives no target and does not leak into its neighbours -- and trunc_dev WITHOUT final_value_dev: the
+ *                                            terminal observation is frame row t + 1, so value[t+1] is its value.
+ * mg_sum_columns writes out[r] = the sum of col[r][0 .. num_envs - 1] in this FIXED order, which is part of the definition: 256 partial sums, partial
+ * l starting at 0.0 and adding instances l, l + 256, l + 512, ... ascending; then the halving tree part[l] += part[l + h] for l < h, h = 128, 64, ..., 1;
+ * out[r] = part[0].  Every add is one rounded double operation; no atomic is used.  num_envs is the handle's.  With rows = 3 and mg_rollout_targets'
+ * col_dev it gives the count, the sum and the sum of squares of all valid advantages.
+ * LAUNCHES: mg_rollout_targets is ONE launch, a lane per instance walking its column backwards in blocks of 16 rows whose loads are all issued before
+ * the first is used; the lanes of a wave read 256 neighbouring bytes of a float row and 64 of a flag row and store the same shapes; value[t+1] is the
+ * row loaded one step earlier.  No LDS, no atomic, no scratch.  mg_sum_columns is one small launch, a 256-lane workgroup per row.
+ * Errors (-1), mg_rollout_targets: before the first mg_reset / mg_set_state; a NULL reward_dev, done_dev or value_dev; all four outputs NULL;
+ * steps < 1; (steps + 1) * num_envs > INT32_MAX; gamma or lambda outside [0, 1] or NaN; final_value_dev without trunc_dev; an output range that shares
+ * a byte with an input range or with another output.  mg_sum_columns: rows < 1; a NULL col_dev or out_dev.
+ * mg_debug_counter "rollout_targets" counts the mg_rollout_targets calls that were not refused, on the host.
+ * OUT OF SCOPE: values in bf16 / f16; rows of a masked rollout in which an instance merely paused (those are not cuts: only steps_of_dev and skip_dev
+ * are understood); V-trace and other off-policy corrections; normalising inside the kernel (the moments are there for the caller to do it). */
+int mg_rollout_targets(mg_env* env, const float* reward_dev, const uint8_t* done_dev, const float* value_dev, int32_t steps,
+                       const int32_t* steps_of_dev, const uint8_t* skip_dev, const uint8_t* trunc_dev, const float* final_value_dev,
+                       float gamma, float lambda, float* adv_dev, float* ret_dev, uint8_t* valid_dev, double* col_dev, void* stream);
+int mg_sum_columns(mg_env* env, const double* col_dev, int32_t rows, double* out_dev, void* stream);
+
 /* DEBUG-VIEW RECORDS: keep the ground-truth view of a FEW instances and draw it later.  mg_render_debug draws every instance at once, from the current state,
  * synchronously: at 65,536 instances 22 GB of views and 1.4 GB of scratch to look at one of them.  But a debug view, like a frame, is a pure function of a
  * descriptor of the family's frame-descriptor type (16 / 64 / 128 B) and the handle's atlas -- the descriptor mg_render_debug fills for every instance before it
